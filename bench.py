@@ -11,12 +11,21 @@ one batch per rank: 2 generator forwards + 1 backward through the HIP attention 
 the PatchGAN discriminator + gradient penalty, two Adam updates, gradients all-reduced over
 RCCL by amk.dp.GradReducer.  Rank 0 prints ONE JSON line.
 
-Besides the step throughput the line carries
+A plain run sets up, warms up, times exactly --steps steps and prints the headline line.  With
+--full (one GPU) the line also carries what takes runs of its own:
   roofline     the dominant HIP kernel at the layer shape of this workload, timed live with HIP
                events on the launch stream: algorithmic FLOP per launch / average duration
                against the 157.3 TFLOP/s exact-f32 MFMA peak (MI355X_MICROARCH.md)
   kernels      the same figure for every hand-written kernel of the step
+  variants     the informational step variants (shared forward, split bf16, bf16 autocast, ...)
   cpu_baseline the CPU oracle's train step on this box's host cores (bounded sample), N=1 only
+(--no-kernels / --no-variants / --no-cpu-baseline drop parts of that.)
+
+--dump-outputs DIR (rank 0) writes, after the timed steps, what the last timed step computed as
+float32 / float64 .npy files: its losses, and the parameters and Adam first moments the step
+left (a fixed seeded sample of 2^21 values per array where there are more: 32 MB for the headline).
+Inputs and initial weights are seeded, so two builds run with the same arguments can be compared
+file by file.
 """
 import argparse
 import json
@@ -47,6 +56,11 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=32, help="images per GPU per step")
     ap.add_argument("--kernel-iters", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the kernel rooflines, the informational variants and blocks and the "
+                         "CPU baseline (one GPU); a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's losses, parameters and Adam first moments to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernels", action="store_true")
     ap.add_argument("--no-variants", action="store_true", help="skip the informational shared-forward variant")
@@ -60,7 +74,10 @@ def parse():
     ap.add_argument("--dp-overlap", default="auto", choices=["auto", "on", "off"],
                     help="all-reduces on a side stream under backward (on) or on the compute stream (off).  auto: on, except for a "
                          "graph-captured step with less than 256 MB of gradients (a forked graph is launched node by node by the host)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:   # a plain run: the headline steps and nothing else
+        args.no_cpu_baseline = args.no_kernels = args.no_variants = True
+    return args
 
 
 T_START = time.perf_counter()
@@ -508,6 +525,8 @@ def secondary_main(args, world, rank, dev, n_ranks_seen):
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": loss}, [("model", step.red.params, step.optim)])
     if rank == 0:
         emit({
             "metric": spec["metric"], "value": batch * world * args.steps / dt, "unit": "images/s", "n_gpus": world,
@@ -630,6 +649,38 @@ def emit(line):
     os.write(REAL_STDOUT, (json.dumps(line) + "\n").encode())
 
 
+DUMP_SAMPLE = 1 << 21   # elements kept per dumped array (8 MB in float32): a fixed seeded sample where there are more
+
+
+def first_moment(opt, p):
+    """Adam's exp_avg of parameter p (FlatAdam or torch.optim)."""
+    if hasattr(opt, "state_of"):
+        return opt.state_of(p)["exp_avg"]
+    st = opt.state.get(p, {})
+    return st["exp_avg"] if "exp_avg" in st else torch.zeros_like(p)
+
+
+def dump_outputs(out_dir, logs, groups):
+    """--dump-outputs: every scalar of `logs` as DIR/<name>.npy (float64, shape (1,)); for each (name, params, optimizer) of
+    `groups` the parameters and their Adam first moments, flattened in parameter order, as DIR/<name>_params.npy and
+    DIR/<name>_exp_avg.npy (float32), the same seeded sample of DUMP_SAMPLE positions for both where there are more."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in logs.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.array([float(v)], dtype=np.float64))
+    for name, params, opt in groups:
+        flat_p = torch.cat([p.detach().reshape(-1).float() for p in params])
+        flat_m = torch.cat([first_moment(opt, p).detach().reshape(-1).float() for p in params])
+        if flat_p.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(20240611)
+            idx = torch.randperm(flat_p.numel(), generator=g)[:DUMP_SAMPLE].sort().values.to(flat_p.device)
+            flat_p, flat_m = flat_p[idx], flat_m[idx]
+        np.save(os.path.join(out_dir, f"{name}_params.npy"), flat_p.cpu().numpy())
+        np.save(os.path.join(out_dir, f"{name}_exp_avg.npy"), flat_m.cpu().numpy())
+    note(f"outputs of the last timed step written to {out_dir}")
+
+
 REAL_STDOUT = 1
 
 
@@ -693,7 +744,7 @@ def main():
         tuning.enable_gemm_tuning()
     torch.manual_seed(0)  # identical init on every rank (and broadcast from rank 0 anyway)
     model = ViTVQGAN(VIT, CODEBOOK)
-    init_state = {k: v.detach().clone() for k, v in model.state_dict().items()} if rank == 0 else None
+    init_state = {k: v.detach().clone() for k, v in model.state_dict().items()} if rank == 0 and args.full else None
     model = model.to(dev)
     discr = NLayerDiscriminator(3, 64, 3).to(dev)
     # one rank: the device side of a step (both phases, both optimizers) is captured into a HIP graph after the
@@ -734,6 +785,7 @@ def main():
     from amk import ops as amk_ops
 
     host_enqueue = [None]
+    last_logs = [None]   # the losses of the last timed step (--dump-outputs)
 
     def timed_steps(n):
         sync()
@@ -745,6 +797,7 @@ def main():
                 # is the device's pace, not the host's)
                 host_enqueue[0] = (time.perf_counter() - t0) / (i + 1)
         sync()
+        last_logs[0] = logs
         return time.perf_counter() - t0, logs
 
     def max_over_ranks(x):
@@ -846,6 +899,9 @@ def main():
             graph_why = why
         note(f"data-parallel step: {graph_why}")
     note(f"timed {args.steps} steps in {dt:.3f}s")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_logs[0], [("generator", list(model.parameters()), trainer.g_optim),
+                                                       ("discriminator", list(discr.parameters()), trainer.d_optim)])
 
     # ---- a separate short instrumented pass (rank 0): HIP events on the launch stream around every
     # hot-path launch of real train steps -> the in-step kernel figures of `roofline` / `kernels_in_step`

@@ -159,6 +159,19 @@ def test_switchhead_small_matches_reference(variant):
             assert n == "W_d.0.weight" and g is None
 
 
+def _score_bias_terms(fx, w, x, h, d, agent_num, name):
+    """The per-score gradients whose sum is the gradient of the scalar score bias `name` (bias1 / bias2): the same
+    forward with that bias given as a leaf of the scores' own shape."""
+    B, T, _ = x.shape
+    pool = int(agent_num ** 0.5)
+    shape = (B, h, pool, T) if name == "bias1" else (B, h, T, pool)
+    ww = {k: v.detach() for k, v in w.items()}
+    ww[name] = w[name].detach().expand(shape).clone().requires_grad_(True)
+    out = ref_cpu.agent_attention(x.detach(), ww, h, d, agent_num)
+    (g,) = torch.autograd.grad((out * torch.from_numpy(fx["cot"])).sum(), [ww[name]])
+    return g
+
+
 def test_agent_small_matches_reference():
     fx = load_golden("agent_small")
     dim, h, d, agent_num = (int(v) for v in fx["dims"])
@@ -170,6 +183,16 @@ def test_agent_small_matches_reference():
     gs = _grads(out, torch.from_numpy(fx["cot"]), [x] + [w[n] for n in names])
     assert_close(gs[0], fx["gx"], TIGHT, "grad x")
     for n, g in zip(names, gs[1:]):
+        if n in ("bias1", "bias2"):
+            # a scalar added to every score of a softmax row: its gradient is zero in exact arithmetic (softmax is
+            # shift-invariant), so both sides hold the f32 rounding residue of a sum of terms of both signs, whose
+            # order follows the CPU's vector width.  TIGHT is taken relative to the size of those terms.
+            terms = _score_bias_terms(fx, w, x, h, d, agent_num, n)
+            bound = TIGHT * float(terms.abs().sum())
+            assert g.shape == fx["g:" + n].shape
+            assert abs(float(g) - float(fx["g:" + n])) <= bound, f"grad {n}: {float(g):.3e} vs {float(fx['g:' + n]):.3e}"
+            assert abs(float(terms.sum()) - float(fx["g:" + n])) <= bound, f"grad {n}: sum of its terms"
+            continue
         assert_close(g, fx["g:" + n], TIGHT, f"grad {n}")
 
 

@@ -6,7 +6,7 @@ ROUND=${ROUND:-r04}
 cd /tmp && export TMPDIR=/tmp
 O=$R/gpurun_out/${ROUND}prof
 mkdir -p $O
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- python3 $R/bench.py --steps 5 --warmup 3 --no-cpu-baseline --no-variants > $O/bench_profiled.json 2> $O/bench_profiled.err
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- python3 $R/bench.py --steps 5 --warmup 3 --full --no-cpu-baseline --no-variants > $O/bench_profiled.json 2> $O/bench_profiled.err
 echo "stats pass done"
 timeout -k 10 200 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_MFMA SQ_INSTS_VALU GRBM_GUI_ACTIVE --output-format csv -d $O/pmcA -o a -- python3 $R/tools/kbench.py --batch 32 --iters 5 > $O/pmcA.log 2>&1
 echo "pmc A done"

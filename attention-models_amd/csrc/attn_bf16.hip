@@ -60,6 +60,13 @@ __device__ __forceinline__ f32x16 zero16() {
   return z;
 }
 __device__ __forceinline__ float vmax(float a, float b, float pinf) { return __builtin_amdgcn_fmed3f(a, b, pinf); }
+// a * b - c with two roundings.  HIP contracts a plain a * b - c into one FMA (__fmul_rn / __fsub_rn included: they are
+// a * b and a - b), and an FMA leaves the rounding error of c = m * c2 in the exponent -- up to +-64 at the fill value's
+// 1.4e9, so a fully masked row lost its uniform weights (and overflowed to NaN over a long row of rescales)
+__device__ __forceinline__ float mul_sub_rn(float a, float b, float c) {
+#pragma clang fp contract(off)
+  return a * b - c;
+}
 // v_max3_f32 (this file is built with -fno-honor-nans -mno-amdgpu-ieee, see the Makefile: no canonicalising v_max in front)
 __device__ __forceinline__ float max3(float a, float b, float c) { return __builtin_fmaxf(__builtin_fmaxf(a, b), c); }
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -271,14 +278,14 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_fwd_kernel(Params p) {
       for (int r = 0; r < 16; ++r) {
         // MASKED: two rounded operations, so that s == m gives exactly 0 at any magnitude (a fused multiply-add leaves the
         // rounding error of m * c2, +-64 at the fill value's 1.4e9)
-        const float p0 = __builtin_amdgcn_exp2f(MASKED ? __fsub_rn(__fmul_rn(s0[r], c2), mc) : __builtin_fmaf(s0[r], c2, -mc));
-        const float p1 = __builtin_amdgcn_exp2f(MASKED ? __fsub_rn(__fmul_rn(s1[r], c2), mc) : __builtin_fmaf(s1[r], c2, -mc));
+        const float p0 = __builtin_amdgcn_exp2f(MASKED ? mul_sub_rn(s0[r], c2, mc) : __builtin_fmaf(s0[r], c2, -mc));
+        const float p1 = __builtin_amdgcn_exp2f(MASKED ? mul_sub_rn(s1[r], c2, mc) : __builtin_fmaf(s1[r], c2, -mc));
         s0[r] = p0;
         s1[r] = p1;
         lsum += p0 + p1;
       }
       if (__any(m_new != m_run)) {
-        const float alpha = __builtin_amdgcn_exp2f(MASKED ? __fsub_rn(__fmul_rn(m_run, c2), mc) : (m_run - m_new) * c2);
+        const float alpha = __builtin_amdgcn_exp2f(MASKED ? mul_sub_rn(m_run, c2, mc) : (m_run - m_new) * c2);
         l_run *= alpha;
   #pragma unroll
         for (int r = 0; r < 16; ++r) { o0[r] *= alpha; o1[r] *= alpha; }
@@ -529,7 +536,7 @@ __global__ __launch_bounds__(64 * BW, 1) void attn_bf16_bwd_kernel(Params p) {
           const bool filled = kfilled || ((cbits >> r) & 1u);
           const float tt = filled ? fill_raw : s[r];
           // (s * c2) - m with two rounded operations, as the forward formed it: exactly 0 where the fill is the row maximum
-          float pr = __builtin_amdgcn_exp2f(__fsub_rn(__fmul_rn(tt, c2), amk_attn::f4(m4, e))) * amk_attn::f4(l4, e);
+          float pr = __builtin_amdgcn_exp2f(mul_sub_rn(tt, c2, amk_attn::f4(m4, e))) * amk_attn::f4(l4, e);
           pr = kvalid ? pr : 0.f;
           s[r] = pr;                                 // a filled position still has its weight in P (dV), but passes no gradient
           dp[r] = filled ? 0.f : dp[r] * pr;

@@ -13,10 +13,26 @@ import os
 import pytest
 import torch
 
+import bf16_attention_ref as bref
 from oracle.fixture_recipe import seeded
 from util import GOLDEN, load_golden, rel_err, weights_of
 
 pytestmark = pytest.mark.gpu
+
+
+def _bhtd(q2, kv2, cot2, H, D=64):
+    """(B,I,H*D) q / cotangent and (B,J,2*H*D) kv -> q, k, v, d_o as (B,H,T,D) CPU tensors."""
+    B, I, _ = q2.shape
+    J = kv2.shape[1]
+    kv = kv2.cpu().float().view(B, J, 2, H, D)
+    split = lambda t: t.cpu().float().view(B, I, H, D).permute(0, 2, 1, 3)
+    return split(q2), kv[:, :, 0].permute(0, 2, 1, 3), kv[:, :, 1].permute(0, 2, 1, 3), split(cot2)
+
+
+def _got(o2, dq2, dkv2, H, D=64):
+    """The kernel's results as (B,H,T,D) CPU tensors (the same splits as _bhtd's)."""
+    dq, dk, dv, o = _bhtd(dq2, dkv2, o2, H, D)
+    return {"o": o, "dq": dq, "dk": dk, "dv": dv}
 
 
 def _core_ref(q, k, v, scale):
@@ -47,6 +63,8 @@ def test_bf16_core_forward_backward(device, B, H, I, J):
     assert rel_err(o.float(), o_ref2) < 5e-3          # bf16 rounding of P and of the output
     assert rel_err(dq.float(), gq) < 1e-2
     assert rel_err(dkv.float(), gkv) < 1e-2
+    # element-wise: within the bound that follows the kernels' rounding points (tests/bf16_attention_ref.py)
+    bref.assert_within(_got(o, dq, dkv, H), bref.reference(*_bhtd(q2, kv2, cot, H), D ** -0.5), f"core {B}x{H}x{I}x{J}")
     # reproducible: no atomics anywhere
     dq2, dkv2 = torch.autograd.grad((ops.attention_fused_kv(qd, kvd, H, D, D ** -0.5).float() * cot.to(device).float()).sum(), [qd, kvd])
     assert torch.equal(dq, dq2) and torch.equal(dkv, dkv2)
@@ -68,6 +86,9 @@ def test_bf16_lazy_reference_moves(device):
     o_ref = _core_ref(qr.view(B, I, H, D).permute(0, 2, 1, 3), kvr[:, :, 0].permute(0, 2, 1, 3), kvr[:, :, 1].permute(0, 2, 1, 3), D ** -0.5)
     o = ops.attention_fused_kv(q2.to(device), kv2.to(device), H, D, D ** -0.5)
     assert rel_err(o.float(), o_ref.permute(0, 2, 1, 3).reshape(B, I, H * D)) < 5e-3
+    qb, kb, vb, _ = _bhtd(q2, kv2, q2, H)
+    R = bref.reference(qb, kb, vb, torch.zeros_like(qb), D ** -0.5)
+    bref.assert_within({"o": o.cpu().float().view(B, I, H, D).permute(0, 2, 1, 3)}, R, "lazy reference", names=("o",))
 
 
 def _masked_ref(q, k, v, scale, key_mask, causal_mask):
@@ -125,6 +146,7 @@ def test_bf16_core_with_masks(device, B, H, I, J, kind):
     assert rel_err(o.float(), o_ref2) < 5e-3
     assert rel_err(dq.float(), gq) < 1e-2
     assert rel_err(dkv.float(), gkv) < 1e-2
+    bref.assert_within(_got(o, dq, dkv, H), bref.reference(*_bhtd(q2, kv2, cot, H), D ** -0.5, key_mask, causal), f"masks {kind}")
     if kind == "dead":   # the dead batch: exactly the mean of v over all keys, and no gradient through the scores
         vmean = kv2.float().view(B, J, 2, H, D)[0, :, 1].mean(0).reshape(1, H * D)
         assert rel_err(o[0].float().cpu(), vmean.expand(I, -1)) < 5e-3

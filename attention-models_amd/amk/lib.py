@@ -57,6 +57,8 @@ SIGNATURES = {
     "amk_vq_gather": (_I, [_P, _P, _L, _I, _I, _P, _P, _P]),
     "amk_agent_num_chunks": (_I, [_I]),
     "amk_agent_ws_floats": (_L, [_I, _I, _I, _I, _I]),
+    "amk_agent_num_chunks_dh": (_I, [_I, _I]),
+    "amk_agent_ws_floats_dh": (_L, [_I, _I, _I, _I, _I, _I]),
     "amk_agent_attn_fwd": (_I, [_P] * 10 + [_I] * 5 + [_L] * 12 + [_F, _P]),
     "amk_agent_attn_bwd": (_I, [_P] * 14 + [_I] * 5 + [_L] * 21 + [_F, _P]),
     "amk_agent_conv_grad_reduce": (_I, [_P, _P, _L, _I, _P, _P, _P]),

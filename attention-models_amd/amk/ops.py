@@ -904,7 +904,7 @@ class _AgentAttn(torch.autograd.Function):
         stats1 = torch.empty((B, H, P, 2), device=dev, dtype=torch.float32)
         cw, cb = conv_w.contiguous(), conv_b.contiguous()
         L = _lib.load()
-        ws = torch.empty((L.amk_agent_ws_floats(B, H, T, P, 0),), device=dev, dtype=torch.float32)
+        ws = torch.empty((max(L.amk_agent_ws_floats_dh(B, H, T, P, D, 0), 1),), device=dev, dtype=torch.float32)
         rc = L.amk_agent_attn_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(cw), _ptr(cb), _ptr(o), _ptr(agents), _ptr(vagent),
                                   _ptr(stats1), _ptr(ws), B, H, T, D, P, *_strides4(q), *_strides4(k), *_strides4(v), *_strides4(o),
                                   float(scale), _stream())
@@ -928,8 +928,8 @@ class _AgentAttn(torch.autograd.Function):
         dqkv = dqkv2.view(B, T, 3, H, D)
         dq, dk, dv = (dqkv[:, :, j].permute(0, 2, 1, 3) for j in range(3))
         L = _lib.load()
-        cells = B * H * L.amk_agent_num_chunks(T)
-        ws = torch.empty((L.amk_agent_ws_floats(B, H, T, P, 1),), device=dev, dtype=torch.float32)
+        cells = B * H * L.amk_agent_num_chunks_dh(T, D)
+        ws = torch.empty((max(L.amk_agent_ws_floats_dh(B, H, T, P, D, 1), 1),), device=dev, dtype=torch.float32)
         dw_part = torch.empty((cells, 9, D), device=dev, dtype=torch.float32)
         db_part = torch.empty((cells, D), device=dev, dtype=torch.float32)
         rc = L.amk_agent_attn_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(cw), _ptr(d_o), _ptr(agents), _ptr(vagent), _ptr(stats1),

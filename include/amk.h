@@ -334,14 +334,22 @@ int amk_moe_gate_grad(const float* d_out, const float* Y, const int64_t* ids, co
  * so they change nothing and receive zero gradient; they do not cross the ABI.
  * q,k,v,o addressed like amk_attn_fwd (T rows).  Saved for the backward: agents (B,H,P,D),
  * vagent (B,H,P,D), stats1 (B,H,P,2) = {row max, row sum} of the aggregation softmax.
- * D must be 64, P <= 16, P <= T.
- * The sequence is processed in chunks of 128 tokens, one workgroup per (batch, head, chunk);
- * sums over tokens go through per-chunk partials in the caller's workspace `ws`
- * (amk_agent_ws_floats(B,H,T,P,backward) floats, contents undefined on return) and are folded
- * in chunk order, so results are bitwise reproducible.
+ * D is 32, 64 or 128 (any other head dim: AMK_EUNSUPPORTED before any device work), P <= 16, P <= T.
+ * The sequence is processed in chunks of 128 tokens (64 at D = 128), one workgroup per
+ * (batch, head, chunk); sums over tokens go through per-chunk partials in the caller's workspace
+ * `ws` (amk_agent_ws_floats_dh(B,H,T,P,D,backward) floats, contents undefined on return) and are
+ * folded in chunk order, so results are bitwise reproducible.
+ *   head dim | chunk | backward chunk kernels
+ *   32       | 128   | LDS-staged (AMK_AGENT_STREAM does not apply)
+ *   64       | 128   | streaming for P <= 8 (AMK_AGENT_STREAM=0: LDS-staged), LDS-staged for P > 8
+ *   128      |  64   | LDS-staged (AMK_AGENT_STREAM does not apply)
+ * amk_agent_num_chunks / amk_agent_ws_floats are the D = 64 sizes; the _dh forms take the head
+ * dim and return 0 for an unsupported one.
  * -------------------------------------------------------------------------- */
 int amk_agent_num_chunks(int T);                                  /* ceil(T / 128); 0 for T <= 0 */
 int64_t amk_agent_ws_floats(int B, int H, int T, int P, int backward); /* workspace size in floats */
+int amk_agent_num_chunks_dh(int T, int D);                        /* ceil(T / chunk(D)) */
+int64_t amk_agent_ws_floats_dh(int B, int H, int T, int P, int D, int backward);
 
 int amk_agent_attn_fwd(const float* q, const float* k, const float* v, const float* conv_w, const float* conv_b,
                        float* o, float* agents, float* vagent, float* stats1, float* ws,
@@ -351,10 +359,10 @@ int amk_agent_attn_fwd(const float* q, const float* k, const float* v, const flo
                        float scale, void* stream);
 
 /* Backward of amk_agent_attn_fwd: dq, dk, dv fully overwritten (q/k/v-like addressing);
- * dconvw_part (B*H*NC, 9, D) and dconvb_part (B*H*NC, D), NC = amk_agent_num_chunks(T), are
+ * dconvw_part (B*H*NC, 9, D) and dconvb_part (B*H*NC, D), NC = amk_agent_num_chunks_dh(T, D), are
  * per-(batch, head, chunk) partial sums of the convolution weight / bias gradients (the caller
  * sums over the first axis; weight element [c][0][a][b] is partial [.., a*3+b, c]);
- * ws: amk_agent_ws_floats(B,H,T,P,1) floats. */
+ * ws: amk_agent_ws_floats_dh(B,H,T,P,D,1) floats. */
 int amk_agent_attn_bwd(const float* q, const float* k, const float* v, const float* conv_w, const float* d_o,
                        const float* agents, const float* vagent, const float* stats1,
                        float* dq, float* dk, float* dv, float* ws, float* dconvw_part, float* dconvb_part,

@@ -150,12 +150,13 @@ def _attn_forward(q, k, v, key_mask, causal_mask, scale, keep_scores=False):
     o = _new_bthd(B, H, I, D, q)
     stats = torch.empty((B, H, I, 2), device=q.device, dtype=torch.float32)
     L = _lib.load()
-    x6 = ATTENTION_FORWARD == "bf16x6" and D == 64  # head dims 32 / 128 run the plain f32 kernels
+    x6 = ATTENTION_FORWARD == "bf16x6" and D == 64  # every other head dim runs the plain f32 kernels
     ws = torch.empty((L.amk_attn_fwd_x6_ws_bytes(B, H, J),), device=q.device, dtype=torch.uint8) if x6 else None
     scores = None
     # (head dim 128: the score-keeping forward exists without masks, and its one-pass backward takes atomics only.  Head dim
     # 32 has both too, but recomputing wins there -- 0.618 against 0.609 of the f32 MFMA peak: the scores are 4 bytes per
-    # (query, key) against only 32 multiply-adds, 2.1 GB per launch at the benchmark shape -- so its scores are not kept)
+    # (query, key) against only 32 multiply-adds, 2.1 GB per launch at the benchmark shape -- so its scores are not kept.
+    # The other head dims, 96 to 256, have no score-keeping forward nor one-pass backward: they always recompute)
     det = DETERMINISTIC_ATTENTION_BACKWARD or torch.are_deterministic_algorithms_enabled()
     keepable = D == 64 or (D == 128 and key_mask is None and causal_mask is None and not det)
     if (keep_scores and keepable and not x6 and ATTENTION_KEEP_SCORES
@@ -210,7 +211,7 @@ def _attn_backward(q, k, v, o, stats, d_o, dq, dk, dv, key_mask, causal_mask, sc
         scores = None
     B, H, I, D = q.shape
     if D != 64 and stages & 64:
-        scores = None   # head dims 32 / 128 under the reproducible mode: the two recompute kernels (no kept scores)
+        scores = None   # head dims other than 64 under the reproducible mode: the two recompute kernels (no kept scores)
     J = k.shape[2]
     d_o = _as_kernel_view(d_o)
     L = _lib.load()

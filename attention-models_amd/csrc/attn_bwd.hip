@@ -392,7 +392,9 @@ static int attn_bwd_impl(const float* scores, const float* q, const float* k, co
                             float scale, int stages, void* stream) {
   AMK_CHECK_ARG(q && k && v && o && stats && d_o && dq && dk && dv && delta_ws, "amk_attn_bwd: null tensor pointer");
   AMK_CHECK_ARG(B > 0 && H > 0 && I > 0 && J > 0, "amk_attn_bwd: non-positive size B=%d H=%d I=%d J=%d", B, H, I, J);
-  AMK_CHECK_SUPPORTED(Dh == D || attn_gen_supported(Dh), "amk_attn_bwd: head dim %d not supported (32, 64, 128)", Dh);
+  AMK_CHECK_SUPPORTED(Dh == D || attn_gen_supported(Dh), "amk_attn_bwd: head dim %d not supported (a multiple of 32 from 32 to 256)", Dh);
+  AMK_CHECK_SUPPORTED(Dh == D || !scores || Dh == 32 || Dh == 128,
+                      "amk_attn_bwd_kept: kept scores exist for head dims 32, 64 and 128 only (head dim %d)", Dh);
   AMK_CHECK_SUPPORTED(Dh == D || !scores || !(stages & AMK_ATTN_BWD_DQ_REPRO),
                       "amk_attn_bwd_kept: kept scores with the reproducible dq exist for head dim %d only", D);
   BwdParams p;
@@ -424,7 +426,8 @@ static int attn_bwd_impl(const float* scores, const float* q, const float* k, co
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (Dh != D) {
     // head dims 32 / 128: the one-pass kernel of attn_bwd_fused_gen.hip (dq by atomics) when FUSED is asked for and the
-    // layout allows it, else the two recompute kernels of attn_generic.hip (always for the reproducible dq)
+    // layout allows it, else the two recompute kernels of attn_generic.h (always for the reproducible dq, and always for
+    // the other head dims, which have no one-pass kernel)
     if (stages & AMK_ATTN_BWD_FUSED) {
       if (stages & AMK_ATTN_BWD_DELTA) launch_attn_bwd_gen(p, Dh, AMK_ATTN_BWD_DELTA, st);
       if (!launch_attn_bwd_fused_gen(p, Dh, st)) {

@@ -538,8 +538,10 @@ static int attn_fwd_impl(void* x6_ws, bool x6, float* scores, const float* q, co
                          float scale, void* stream) {
   AMK_CHECK_ARG(q && k && v && o && stats, "amk_attn_fwd: null tensor pointer");
   AMK_CHECK_ARG(B > 0 && H > 0 && I > 0 && J > 0, "amk_attn_fwd: non-positive size B=%d H=%d I=%d J=%d", B, H, I, J);
-  AMK_CHECK_SUPPORTED(Dh == D || attn_gen_supported(Dh), "amk_attn_fwd: head dim %d not supported (32, 64, 128)", Dh);
+  AMK_CHECK_SUPPORTED(Dh == D || attn_gen_supported(Dh), "amk_attn_fwd: head dim %d not supported (a multiple of 32 from 32 to 256)", Dh);
   AMK_CHECK_SUPPORTED(Dh == D || !x6, "amk_attn_fwd_x6: the split-bf16 forward is built for head dim %d", D);
+  AMK_CHECK_SUPPORTED(Dh == D || !scores || Dh == 32 || Dh == 128,
+                      "amk_attn_fwd_keep: kept scores exist for head dims 32, 64 and 128 only (head dim %d)", Dh);
   AMK_CHECK_SUPPORTED(Dh == D || !scores || (!key_mask && !causal_mask),
                       "amk_attn_fwd_keep: for head dims 32 / 128 the score-keeping forward exists without masks only");
   FwdParams p;

@@ -65,10 +65,13 @@ const char* amk_last_error(void);
  * the (B,T,h*D) projection outputs are consumed in place (st = h*D, sh = D) as
  * well as (B,h,T,D) tensors (sh = T*D, st = D).  k and v likewise with J rows.
  * key_mask: uint8 (B,J) contiguous or NULL; causal_mask: uint8 (I,J) contiguous
- * or NULL.  stats: (B,H,I,2) contiguous.  D is 32, 64 or 128 (64: the tuned kernels and the split-bf16
- * forward; 32 / 128: csrc/attn_generic.hip -- forward, with kept scores when there is no mask -- and
- * csrc/attn_bwd_fused_gen.hip, the one-pass backward with dq by atomics; the reproducible backward of
- * those head dims is the two recompute kernels of csrc/attn_generic.hip).
+ * or NULL.  stats: (B,H,I,2) contiguous.  D is a multiple of 32 from 32 to 256; any other head dim is
+ * AMK_EUNSUPPORTED before any device work.  64: the tuned kernels and the split-bf16 forward; 32 / 128:
+ * csrc/attn_generic.h -- forward, with kept scores when there is no mask -- and csrc/attn_bwd_fused_gen.hip,
+ * the one-pass backward with dq by atomics; the reproducible backward of those head dims is the two recompute
+ * kernels of csrc/attn_generic.h.  96, 160, 192, 224, 256 (same library version, 0.4.0): the forward and the
+ * recompute backward of csrc/attn_generic.h only -- amk_attn_fwd_keep / amk_attn_bwd_kept return
+ * AMK_EUNSUPPORTED for them, and a FUSED request to amk_attn_bwd runs the recompute kernels.
  * -------------------------------------------------------------------------- */
 int amk_attn_fwd(const float* q, const float* k, const float* v, float* o, float* stats,
                  const uint8_t* key_mask, const uint8_t* causal_mask,

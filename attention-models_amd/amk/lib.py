@@ -106,6 +106,10 @@ SIGNATURES = {
     "amk_moe_combine_rows": (_I, [_P, _P, _P, _L, _I, _I, _I, _I, _I, _P, _P]),
     "amk_moe_gate_grad_rows": (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P, _P]),
     "amk_moe_gate_grad": (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _I, _P, _P]),
+    "amk_bnact_ws_floats": (_L, [_I, _I, _L]),
+    "amk_bnact_fwd": (_I, [_P, _P, _P, _I, _I, _L, _F, _F, _F] + [_P] * 7),
+    "amk_bnact_bwd": (_I, [_P] * 6 + [_I, _I, _L, _F] + [_P] * 6),
+    "amk_bnact_bwd_bwd": (_I, [_P] * 10 + [_I, _I, _L, _F] + [_P] * 5),
 }
 
 _lib = None

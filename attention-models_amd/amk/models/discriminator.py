@@ -1,8 +1,13 @@
 """PatchGAN discriminator used by the ViT-VQGAN train step (reference:
 models/utils/discriminator.py:6-54, constructed as NLayerDiscriminator(3, 64, 3) in
-trainers/vitgqgan.py:64).  Not a kernel target: convolutions / BatchNorm stay on MIOpen.
+trainers/vitgqgan.py:64).  The convolutions stay on MIOpen.
 It exists here because the benchmark step contains it; state_dict
 keys (``model.N.*``) match the reference layer order.
+
+The training-mode BatchNorm2d + LeakyReLU pairs of layers 3, 6 and 9 run on csrc/discr_norm.hip (ops.bn_leaky_relu:
+forward, backward and the gradient penalty's double backward, two launches each) instead of MIOpen's batch norm and
+ATen's composite double backward; eval mode, CPU tensors and bf16 autocast keep the modules (AMK_DISCR_NORM=aten
+keeps them everywhere).
 
 The gradient penalty of that step (trainers/vitgqgan.py:115-131) differentiates the
 discriminator's input gradient a second time.  ATen expresses the second derivative of a
@@ -20,6 +25,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.nn.grad import conv2d_input, conv2d_weight
 
+from .. import ops
+
 _INPUT_GRAD_ONLY = False
 
 
@@ -34,6 +41,11 @@ def input_grad_only():
         yield
     finally:
         _INPUT_GRAD_ONLY = old
+
+
+def input_grad_only_active():
+    """True inside ``input_grad_only()`` (read by the backward of ops.bn_leaky_relu)."""
+    return _INPUT_GRAD_ONLY
 
 
 class _ConvDataGrad(torch.autograd.Function):
@@ -110,4 +122,17 @@ class NLayerDiscriminator(nn.Module):
         self.model = nn.Sequential(*layers)
 
     def forward(self, x):
-        return self.model(x)
+        if ops.discr_norm_mode() != "amk":
+            return self.model(x)
+        layers = list(self.model)
+        i = 0
+        while i < len(layers):
+            m = layers[i]
+            nxt = layers[i + 1] if i + 1 < len(layers) else None
+            if isinstance(m, nn.BatchNorm2d) and isinstance(nxt, nn.LeakyReLU) and ops.bn_leaky_relu_ok(m, x):
+                x = ops.bn_leaky_relu(x, m, nxt.negative_slope)
+                i += 2
+            else:
+                x = m(x)
+                i += 1
+        return x

@@ -1623,3 +1623,117 @@ def swiglu_ffn(x, w12, b12, w3, b3):
         return linear(swiglu(ab), w3, b3)
     a, b = ab.chunk(2, dim=-1)
     return linear(torch.nn.functional.silu(a) * b, w3, b3)
+
+
+# ---------------------------------------------------------------------------- discriminator BatchNorm + LeakyReLU
+# AMK_DISCR_NORM: "amk" (default) = the training-mode BatchNorm2d + LeakyReLU pairs of NLayerDiscriminator run on
+# csrc/discr_norm.hip (forward, backward and the gradient penalty's double backward); "aten" = the modules as they are
+# (MIOpen batch norm, ATen's leaky_relu and its composite double backward).  Read per call, so one build A/Bs.
+def discr_norm_mode():
+    return os.environ.get("AMK_DISCR_NORM", "amk")
+
+
+def _bn_aligned(t):
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _bn_dims(x):
+    N, C, H, W = x.shape
+    return N, C, H * W
+
+
+def _bn_ws(x):
+    N, C, HW = _bn_dims(x)
+    return torch.empty(int(_lib.load().amk_bnact_ws_floats(N, C, HW)), device=x.device, dtype=torch.float32)
+
+
+class _BNActGrad(torch.autograd.Function):
+    """(gx, dgamma, dbeta) of z = leaky_relu(batch_norm(x), slope) for a given gz; differentiable in gz, x and gamma
+    (its backward is the double backward the gradient penalty takes)."""
+
+    @staticmethod
+    def forward(ctx, gz, x, weight, bias, mean, rstd, slope):
+        gz = _bn_aligned(gz)
+        N, C, HW = _bn_dims(x)
+        L = _lib.load()
+        gx = torch.empty_like(x)
+        sums = torch.empty((2, C), device=x.device, dtype=torch.float32)
+        dw = torch.empty_like(weight)
+        db = torch.empty_like(bias)
+        _lib.check(L.amk_bnact_bwd(_ptr(gz), _ptr(x), _ptr(weight), _ptr(bias), _ptr(mean), _ptr(rstd), N, C, HW,
+                                   float(slope), _ptr(gx), _ptr(sums), _ptr(dw), _ptr(db), _ptr(_bn_ws(x)), _stream()),
+                   "amk_bnact_bwd")
+        ctx.save_for_backward(gz, x, weight, bias, mean, rstd, sums)
+        ctx.slope = slope
+        ctx.set_materialize_grads(False)   # absent gradients of dgamma / dbeta cost nothing
+        return gx, dw, db
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, ggx, ggw, ggb):
+        gz, x, weight, bias, mean, rstd, sums = ctx.saved_tensors
+        if ggx is None and ggw is None and ggb is None:
+            return None, None, None, None, None, None, None
+        ggx = torch.zeros_like(x) if ggx is None else _bn_aligned(ggx)
+        N, C, HW = _bn_dims(x)
+        g_gz = torch.empty_like(x)
+        g_x = torch.empty_like(x)
+        g_w = torch.empty_like(weight) if ctx.needs_input_grad[2] else None
+        _lib.check(_lib.load().amk_bnact_bwd_bwd(
+            _ptr(ggx), _ptr(ggw.contiguous() if ggw is not None else None), _ptr(ggb.contiguous() if ggb is not None else None),
+            _ptr(gz), _ptr(x), _ptr(weight), _ptr(bias), _ptr(mean), _ptr(rstd), _ptr(sums), N, C, HW, float(ctx.slope),
+            _ptr(g_gz), _ptr(g_x), _ptr(g_w), _ptr(_bn_ws(x)), _stream()), "amk_bnact_bwd_bwd")
+        return (g_gz if ctx.needs_input_grad[0] else None, g_x if ctx.needs_input_grad[1] else None, g_w,
+                None, None, None, None)
+
+
+class _BNAct(torch.autograd.Function):
+    """z = leaky_relu(batch_norm(x, training=True), slope) with the running statistics updated in place."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, eps, momentum, slope):
+        N, C, HW = _bn_dims(x)
+        L = _lib.load()
+        z = torch.empty_like(x)
+        mean = torch.empty(C, device=x.device, dtype=torch.float32)
+        rstd = torch.empty(C, device=x.device, dtype=torch.float32)
+        _lib.check(L.amk_bnact_fwd(_ptr(x), _ptr(weight), _ptr(bias), N, C, HW, float(eps), float(momentum), float(slope),
+                                   _ptr(z), _ptr(mean), _ptr(rstd), _ptr(running_mean), _ptr(running_var),
+                                   _ptr(_bn_ws(x)), _stream()), "amk_bnact_fwd")
+        ctx.save_for_backward(x, weight, bias, mean, rstd)
+        ctx.slope = slope
+        ctx.set_materialize_grads(False)
+        return z
+
+    @staticmethod
+    def backward(ctx, gz):
+        if gz is None:
+            return (None,) * 8
+        x, weight, bias, mean, rstd = ctx.saved_tensors
+        from .models.discriminator import input_grad_only_active   # (lazy: the models package imports this module)
+
+        gx, dw, db = _BNActGrad.apply(gz, x, weight, bias, mean, rstd, ctx.slope)
+        if input_grad_only_active():
+            dw = db = None
+        return (gx if ctx.needs_input_grad[0] else None, dw if ctx.needs_input_grad[1] else None,
+                db if ctx.needs_input_grad[2] else None, None, None, None, None, None)
+
+
+def bn_leaky_relu_ok(bn, x):
+    """True when (bn, LeakyReLU) can run on amk_bnact_*: training-mode statistics with running averages and an affine
+    transform, an f32 contiguous NCHW HIP tensor outside autocast.  Everything else (eval, CPU, bf16 autocast) keeps
+    the modules."""
+    return (bn.training and bn.track_running_stats and bn.affine and bn.momentum is not None
+            and bn.running_mean is not None and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+            and x.is_contiguous() and x.numel() > 0 and x.shape[0] * x.shape[2] * x.shape[3] > 1
+            and not torch.is_autocast_enabled() and bn.weight.dtype == torch.float32)
+
+
+def bn_leaky_relu(x, bn, slope):
+    """leaky_relu(bn(x), slope) for a training-mode nn.BatchNorm2d (see bn_leaky_relu_ok)."""
+    _require_device(x, bn.weight, bn.bias)
+    if bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+    return _BNAct.apply(_bn_aligned(x), bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum,
+                        float(slope))

@@ -1,0 +1,456 @@
+// Training-mode BatchNorm2d + LeakyReLU of the PatchGAN discriminator, f32 NCHW, for gfx950:
+// forward, first-order backward and the double backward the gradient penalty needs.
+//
+// ATen runs this stack as MIOpen batch-norm kernels plus separate LeakyReLU passes, and the
+// double backward as ~80 small reductions and element-wise launches per layer.  Here every entry
+// point is two launches: a reduction over the channel's data into per-workgroup partials, then an
+// apply pass over the same tensors (which the Infinity Cache still holds) that folds the partials
+// in a fixed order and writes the outputs.  No float atomics: results are bitwise reproducible.
+//
+// Notation (per channel c, n = N*HW): mu, var biased batch statistics, r = (var + eps)^-1/2,
+// xh = (x - mu) r, y = gamma xh + beta, z = y > 0 ? y : slope y, s = dz/dy.  y is recomputed from x.
+//
+// Work split: a channel is cut into S segments -- runs of whole planes, or for planes larger than
+// SEG pieces of one plane -- and workgroup (s, c) owns segment s of channel c in every kernel.  A
+// plane (n, c) starts at element (n C + c) HW, which is only 4-byte aligned when HW is odd: each
+// plane is walked as a scalar head, an aligned float4 body and a scalar tail.
+#include "amk_common.h"
+
+namespace amk_bn {
+
+constexpr int BLOCK = 256;
+constexpr int WAVES = BLOCK / 64;
+constexpr int64_t SEG = 4096;  // target elements per workgroup segment
+
+struct Geo {
+  int N, C;
+  int64_t HW;
+  int PP;     // whole planes per segment (Q == 1)
+  int Q;      // pieces per plane (PP == 1)
+  int64_t L;  // elements per piece (Q > 1)
+  int S;      // segments per channel
+};
+
+static Geo make_geo(int N, int C, int64_t HW) {
+  Geo g;
+  g.N = N; g.C = C; g.HW = HW;
+  if (HW <= SEG) {
+    g.PP = (int)(SEG / HW);
+    if (g.PP > N) g.PP = N;
+    g.Q = 1; g.L = HW;
+    g.S = (N + g.PP - 1) / g.PP;
+  } else {
+    g.PP = 1;
+    g.Q = (int)((HW + SEG - 1) / SEG);
+    g.L = (((HW + g.Q - 1) / g.Q) + 3) & ~(int64_t)3;
+    g.S = N * g.Q;
+  }
+  return g;
+}
+
+struct Seg {
+  int p0, p1;
+  int64_t e0, e1;
+};
+
+__device__ __forceinline__ Seg seg_of(const Geo& g, int s) {
+  Seg r;
+  if (g.Q == 1) {
+    r.p0 = s * g.PP; r.p1 = min(g.N, r.p0 + g.PP);
+    r.e0 = 0; r.e1 = g.HW;
+  } else {
+    r.p0 = s / g.Q; r.p1 = r.p0 + 1;
+    r.e0 = min(g.HW, (int64_t)(s % g.Q) * g.L);
+    r.e1 = min(g.HW, r.e0 + g.L);
+  }
+  return r;
+}
+
+__device__ __forceinline__ float seg_count(const Geo& g, int s) {
+  const Seg r = seg_of(g, s);
+  return (float)((int64_t)(r.p1 - r.p0) * (r.e1 - r.e0));
+}
+
+template <int W> struct Width { static constexpr int value = W; };
+
+template <int W>
+__device__ __forceinline__ void ld(const float* p, float (&v)[W]) {
+  if constexpr (W == 4) {
+    const float4 t = *reinterpret_cast<const float4*>(p);
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+  } else {
+    v[0] = *p;
+  }
+}
+
+template <int W>
+__device__ __forceinline__ void st(float* p, const float (&v)[W]) {
+  if constexpr (W == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  else *p = v[0];
+}
+
+// Calls f(Width<4>, off) for every aligned 4-element run and f(Width<1>, off) for every edge element
+// of segment s of channel c; `off` indexes the (N, C, HW) tensor.  Tensor bases are 16-byte aligned.
+template <class F>
+__device__ __forceinline__ void seg_walk(const Geo& g, int c, int s, F&& f) {
+  const Seg r = seg_of(g, s);
+  const int64_t len = r.e1 - r.e0;
+  const int t = threadIdx.x;
+  for (int p = r.p0; p < r.p1; ++p) {
+    const int64_t base = ((int64_t)p * g.C + c) * g.HW + r.e0;
+    const int head = (int)min((int64_t)((4 - (base & 3)) & 3), len);
+    const int64_t nv = (len - head) >> 2;
+    const int tail = (int)(len - head - 4 * nv);
+    for (int64_t i = t; i < nv; i += BLOCK) f(Width<4>{}, base + head + 4 * i);
+    if (t < head) f(Width<1>{}, base + t);
+    else if (t < head + tail) f(Width<1>{}, base + 4 * nv + t);
+  }
+}
+
+struct Sum {
+  template <int K>
+  __device__ __forceinline__ void operator()(float (&a)[K], const float (&b)[K]) const {
+#pragma unroll
+    for (int k = 0; k < K; ++k) a[k] += b[k];
+  }
+};
+
+// Chan's merge of (count, mean, M2) triples
+struct Chan {
+  __device__ __forceinline__ void operator()(float (&a)[3], const float (&b)[3]) const {
+    const float n = a[0] + b[0];
+    if (b[0] == 0.f) return;
+    if (a[0] == 0.f) { a[0] = b[0]; a[1] = b[1]; a[2] = b[2]; return; }
+    const float d = b[1] - a[1], f = b[0] / n;
+    a[1] += d * f;
+    a[2] += b[2] + d * d * a[0] * f;
+    a[0] = n;
+  }
+};
+
+// Fixed-order block reduction: a butterfly inside each wave (lane 0's result is used), then every
+// thread folds the WAVES wave results in order, so all threads return the same value.
+template <int K, class Op>
+__device__ __forceinline__ void block_reduce(float (&v)[K], Op op, float* lds) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    float w[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) w[k] = __shfl_xor(v[k], o, 64);
+    op(v, w);
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) lds[wave * K + k] = v[k];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < K; ++k) v[k] = lds[k];
+#pragma unroll
+  for (int w = 1; w < WAVES; ++w) {
+    float u[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) u[k] = lds[w * K + k];
+    op(v, u);
+  }
+  __syncthreads();
+}
+
+// Sum of the S per-segment partials part[(c S + j) K + k] in a fixed order.
+template <int K>
+__device__ __forceinline__ void fold_sums(const float* __restrict__ part, const Geo& g, int c, float (&v)[K],
+                                          float* lds) {
+#pragma unroll
+  for (int k = 0; k < K; ++k) v[k] = 0.f;
+  for (int j = threadIdx.x; j < g.S; j += BLOCK) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] += part[((int64_t)c * g.S + j) * K + k];
+  }
+  block_reduce<K>(v, Sum{}, lds);
+}
+
+// ---------------------------------------------------------------- forward
+// part (C, S, 2): per-segment mean and M2, each from two passes over the segment (the second hits L2).
+__global__ __launch_bounds__(BLOCK) void stats_kernel(const float* __restrict__ x, Geo g, float* __restrict__ part) {
+  __shared__ float lds[WAVES * 3];
+  const int s = blockIdx.x, c = blockIdx.y;
+  float v[1] = {0.f};
+  seg_walk(g, c, s, [&](auto w, int64_t off) {
+    constexpr int W = decltype(w)::value;
+    float xv[W];
+    ld<W>(x + off, xv);
+#pragma unroll
+    for (int k = 0; k < W; ++k) v[0] += xv[k];
+  });
+  block_reduce<1>(v, Sum{}, lds);
+  const float cnt = seg_count(g, s);
+  const float mean = cnt > 0.f ? v[0] / cnt : 0.f;
+  float q[1] = {0.f};
+  seg_walk(g, c, s, [&](auto w, int64_t off) {
+    constexpr int W = decltype(w)::value;
+    float xv[W];
+    ld<W>(x + off, xv);
+#pragma unroll
+    for (int k = 0; k < W; ++k) { const float d = xv[k] - mean; q[0] += d * d; }
+  });
+  block_reduce<1>(q, Sum{}, lds);
+  if (threadIdx.x == 0) {
+    part[((int64_t)c * g.S + s) * 2] = mean;
+    part[((int64_t)c * g.S + s) * 2 + 1] = q[0];
+  }
+}
+
+__global__ __launch_bounds__(BLOCK) void fwd_apply_kernel(
+    const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta, Geo g,
+    const float* __restrict__ part, float eps, float momentum, float slope, float* __restrict__ z,
+    float* __restrict__ mean_out, float* __restrict__ rstd_out, float* __restrict__ run_mean,
+    float* __restrict__ run_var) {
+  __shared__ float lds[WAVES * 3];
+  const int s = blockIdx.x, c = blockIdx.y;
+  float a[3] = {0.f, 0.f, 0.f};
+  for (int j = threadIdx.x; j < g.S; j += BLOCK) {
+    const float b[3] = {seg_count(g, j), part[((int64_t)c * g.S + j) * 2], part[((int64_t)c * g.S + j) * 2 + 1]};
+    Chan{}(a, b);
+  }
+  block_reduce<3>(a, Chan{}, lds);
+  const float n = a[0], mu = a[1], var = a[2] / n;
+  const float r = rsqrtf(var + eps);
+  const float scale = gamma[c] * r, shift = beta[c] - mu * scale;
+  if (s == 0 && threadIdx.x == 0) {
+    mean_out[c] = mu;
+    rstd_out[c] = r;
+    if (run_mean) run_mean[c] = (1.f - momentum) * run_mean[c] + momentum * mu;
+    if (run_var) run_var[c] = (1.f - momentum) * run_var[c] + momentum * (a[2] / (n - 1.f));
+  }
+  seg_walk(g, c, s, [&](auto w, int64_t off) {
+    constexpr int W = decltype(w)::value;
+    float xv[W];
+    ld<W>(x + off, xv);
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      const float y = fmaf(xv[k], scale, shift);
+      xv[k] = y > 0.f ? y : slope * y;
+    }
+    st<W>(z + off, xv);
+  });
+}
+
+// Per-channel constants of the backward kernels.
+struct Chn {
+  float mu, r, scale, shift;
+};
+
+__device__ __forceinline__ Chn chn(const float* gamma, const float* beta, const float* mean, const float* rstd, int c) {
+  Chn h;
+  h.mu = mean[c]; h.r = rstd[c];
+  h.scale = gamma[c] * h.r;
+  h.shift = beta[c] - h.mu * h.scale;
+  return h;
+}
+
+// ---------------------------------------------------------------- first-order backward
+// part (C, S, 2): per-segment sums of gy and gy * xh, gy = s * gz.
+__global__ __launch_bounds__(BLOCK) void bwd_reduce_kernel(
+    const float* __restrict__ gz, const float* __restrict__ x, const float* __restrict__ gamma,
+    const float* __restrict__ beta, const float* __restrict__ mean, const float* __restrict__ rstd, Geo g, float slope,
+    float* __restrict__ part) {
+  __shared__ float lds[WAVES * 3];
+  const int s = blockIdx.x, c = blockIdx.y;
+  const Chn h = chn(gamma, beta, mean, rstd, c);
+  float v[2] = {0.f, 0.f};
+  seg_walk(g, c, s, [&](auto w, int64_t off) {
+    constexpr int W = decltype(w)::value;
+    float xv[W], gv[W];
+    ld<W>(x + off, xv);
+    ld<W>(gz + off, gv);
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      const float gy = fmaf(xv[k], h.scale, h.shift) > 0.f ? gv[k] : slope * gv[k];
+      v[0] += gy;
+      v[1] += gy * ((xv[k] - h.mu) * h.r);
+    }
+  });
+  block_reduce<2>(v, Sum{}, lds);
+  if (threadIdx.x == 0) {
+    part[((int64_t)c * g.S + s) * 2] = v[0];
+    part[((int64_t)c * g.S + s) * 2 + 1] = v[1];
+  }
+}
+
+// gx = gamma r (gy - Sgy/n - xh Sgyx/n); sums (2, C) = (Sgy, Sgyx), dbeta = Sgy, dgamma = Sgyx.
+__global__ __launch_bounds__(BLOCK) void bwd_apply_kernel(
+    const float* __restrict__ gz, const float* __restrict__ x, const float* __restrict__ gamma,
+    const float* __restrict__ beta, const float* __restrict__ mean, const float* __restrict__ rstd, Geo g, float slope,
+    const float* __restrict__ part, float* __restrict__ gx, float* __restrict__ sums, float* __restrict__ dgamma,
+    float* __restrict__ dbeta) {
+  __shared__ float lds[WAVES * 3];
+  const int s = blockIdx.x, c = blockIdx.y;
+  const Chn h = chn(gamma, beta, mean, rstd, c);
+  float v[2];
+  fold_sums<2>(part, g, c, v, lds);
+  if (s == 0 && threadIdx.x == 0) {
+    sums[c] = v[0];
+    sums[g.C + c] = v[1];
+    if (dbeta) dbeta[c] = v[0];
+    if (dgamma) dgamma[c] = v[1];
+  }
+  const float inv_n = 1.f / (float)((double)g.N * (double)g.HW);
+  const float A = v[0] * inv_n, B = v[1] * inv_n;
+  seg_walk(g, c, s, [&](auto w, int64_t off) {
+    constexpr int W = decltype(w)::value;
+    float xv[W], gv[W];
+    ld<W>(x + off, xv);
+    ld<W>(gz + off, gv);
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      const float gy = fmaf(xv[k], h.scale, h.shift) > 0.f ? gv[k] : slope * gv[k];
+      const float xh = (xv[k] - h.mu) * h.r;
+      xv[k] = h.scale * (gy - A - xh * B);
+    }
+    st<W>(gx + off, xv);
+  });
+}
+
+// ---------------------------------------------------------------- double backward
+// part (C, S, 3): per-segment sums of ggx, ggx * xh, ggx * gy.
+__global__ __launch_bounds__(BLOCK) void bwd_bwd_reduce_kernel(
+    const float* __restrict__ ggx, const float* __restrict__ gz, const float* __restrict__ x,
+    const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ mean,
+    const float* __restrict__ rstd, Geo g, float slope, float* __restrict__ part) {
+  __shared__ float lds[WAVES * 3];
+  const int s = blockIdx.x, c = blockIdx.y;
+  const Chn h = chn(gamma, beta, mean, rstd, c);
+  float v[3] = {0.f, 0.f, 0.f};
+  seg_walk(g, c, s, [&](auto w, int64_t off) {
+    constexpr int W = decltype(w)::value;
+    float xv[W], gv[W], qv[W];
+    ld<W>(x + off, xv);
+    ld<W>(gz + off, gv);
+    ld<W>(ggx + off, qv);
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      const float gy = fmaf(xv[k], h.scale, h.shift) > 0.f ? gv[k] : slope * gv[k];
+      v[0] += qv[k];
+      v[1] += qv[k] * ((xv[k] - h.mu) * h.r);
+      v[2] += qv[k] * gy;
+    }
+  });
+  block_reduce<3>(v, Sum{}, lds);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) part[((int64_t)c * g.S + s) * 3 + k] = v[k];
+  }
+}
+
+// A = Sgy/n, B = Sgyx/n, C = Sggx/n, D = Sggxx/n, E = Sggxgy/n:
+//   g_gz = s [gamma r (ggx - C - xh D) + gg_gamma xh + gg_beta]
+//   g_x  = -gamma r^2 [xh (E - AC - 3BD) + B (ggx - C) + D (gy - A)] + gg_gamma r (gy - A - xh B)
+//   g_gamma = n r (E - AC - BD)
+__global__ __launch_bounds__(BLOCK) void bwd_bwd_apply_kernel(
+    const float* __restrict__ ggx, const float* __restrict__ gg_gamma, const float* __restrict__ gg_beta,
+    const float* __restrict__ gz, const float* __restrict__ x, const float* __restrict__ gamma,
+    const float* __restrict__ beta, const float* __restrict__ mean, const float* __restrict__ rstd,
+    const float* __restrict__ sums, Geo g, float slope, const float* __restrict__ part, float* __restrict__ g_gz,
+    float* __restrict__ g_x, float* __restrict__ g_gamma) {
+  __shared__ float lds[WAVES * 3];
+  const int s = blockIdx.x, c = blockIdx.y;
+  const Chn h = chn(gamma, beta, mean, rstd, c);
+  float v[3];
+  fold_sums<3>(part, g, c, v, lds);
+  const float n = (float)((double)g.N * (double)g.HW), inv_n = 1.f / n;
+  const float A = sums[c] * inv_n, B = sums[g.C + c] * inv_n;
+  const float Cc = v[0] * inv_n, D = v[1] * inv_n, E = v[2] * inv_n;
+  const float ggg = gg_gamma ? gg_gamma[c] : 0.f, ggb = gg_beta ? gg_beta[c] : 0.f;
+  if (s == 0 && threadIdx.x == 0 && g_gamma) g_gamma[c] = n * h.r * (E - A * Cc - B * D);
+  const float k1 = E - A * Cc - 3.f * B * D;       // coefficient of xh in g_x's bracket
+  const float gr2 = h.scale * h.r;                  // gamma r^2
+  const float gr = ggg * h.r;
+  seg_walk(g, c, s, [&](auto w, int64_t off) {
+    constexpr int W = decltype(w)::value;
+    float xv[W], gv[W], qv[W];
+    ld<W>(x + off, xv);
+    ld<W>(gz + off, gv);
+    ld<W>(ggx + off, qv);
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      const bool pos = fmaf(xv[k], h.scale, h.shift) > 0.f;
+      const float gy = pos ? gv[k] : slope * gv[k];
+      const float xh = (xv[k] - h.mu) * h.r;
+      const float q = qv[k] - Cc;
+      const float t = h.scale * (q - xh * D) + ggg * xh + ggb;
+      gv[k] = pos ? t : slope * t;
+      xv[k] = gr * (gy - A - xh * B) - gr2 * (xh * k1 + B * q + D * (gy - A));
+    }
+    st<W>(g_gz + off, gv);
+    st<W>(g_x + off, xv);
+  });
+}
+
+}  // namespace amk_bn
+
+using namespace amk_bn;
+
+static bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+#define AMK_BN_SHAPE(what)                                                                       \
+  AMK_CHECK_ARG(N > 0 && C > 0 && HW > 0, what ": non-positive size");                           \
+  AMK_CHECK_SUPPORTED(C <= 65535 && (int64_t)N * HW <= ((int64_t)1 << 31),                       \
+                      what ": shape N %d C %d HW %lld not supported", N, C, (long long)HW)
+
+extern "C" int64_t amk_bnact_ws_floats(int N, int C, int64_t HW) {
+  if (N <= 0 || C <= 0 || HW <= 0) return 0;
+  return (int64_t)C * make_geo(N, C, HW).S * 3;
+}
+
+extern "C" int amk_bnact_fwd(const float* x, const float* gamma, const float* beta, int N, int C, int64_t HW,
+                             float eps, float momentum, float slope, float* z, float* mean, float* rstd,
+                             float* running_mean, float* running_var, float* ws, void* stream) {
+  AMK_CHECK_ARG(x && gamma && beta && z && mean && rstd && ws, "amk_bnact_fwd: null pointer");
+  AMK_BN_SHAPE("amk_bnact_fwd");
+  AMK_CHECK_ARG(N * HW > 1, "amk_bnact_fwd: a channel needs more than one value");
+  AMK_CHECK_ARG(a16(x) && a16(z), "amk_bnact_fwd: x and z must be 16-byte aligned");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const Geo g = make_geo(N, C, HW);
+  const dim3 grid(g.S, C), block(BLOCK);
+  hipLaunchKernelGGL(stats_kernel, grid, block, 0, st, x, g, ws);
+  hipLaunchKernelGGL(fwd_apply_kernel, grid, block, 0, st, x, gamma, beta, g, ws, eps, momentum, slope, z, mean, rstd,
+                     running_mean, running_var);
+  AMK_CHECK_LAUNCH("amk_bnact_fwd");
+  return AMK_OK;
+}
+
+extern "C" int amk_bnact_bwd(const float* gz, const float* x, const float* gamma, const float* beta,
+                             const float* mean, const float* rstd, int N, int C, int64_t HW, float slope, float* gx,
+                             float* sums, float* dgamma, float* dbeta, float* ws, void* stream) {
+  AMK_CHECK_ARG(gz && x && gamma && beta && mean && rstd && gx && sums && ws, "amk_bnact_bwd: null pointer");
+  AMK_BN_SHAPE("amk_bnact_bwd");
+  AMK_CHECK_ARG(a16(gz) && a16(x) && a16(gx), "amk_bnact_bwd: gz, x and gx must be 16-byte aligned");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const Geo g = make_geo(N, C, HW);
+  const dim3 grid(g.S, C), block(BLOCK);
+  hipLaunchKernelGGL(bwd_reduce_kernel, grid, block, 0, st, gz, x, gamma, beta, mean, rstd, g, slope, ws);
+  hipLaunchKernelGGL(bwd_apply_kernel, grid, block, 0, st, gz, x, gamma, beta, mean, rstd, g, slope, ws, gx, sums,
+                     dgamma, dbeta);
+  AMK_CHECK_LAUNCH("amk_bnact_bwd");
+  return AMK_OK;
+}
+
+extern "C" int amk_bnact_bwd_bwd(const float* ggx, const float* gg_gamma, const float* gg_beta, const float* gz,
+                                 const float* x, const float* gamma, const float* beta, const float* mean,
+                                 const float* rstd, const float* sums, int N, int C, int64_t HW, float slope,
+                                 float* g_gz, float* g_x, float* g_gamma, float* ws, void* stream) {
+  AMK_CHECK_ARG(ggx && gz && x && gamma && beta && mean && rstd && sums && g_gz && g_x && ws,
+                "amk_bnact_bwd_bwd: null pointer");
+  AMK_BN_SHAPE("amk_bnact_bwd_bwd");
+  AMK_CHECK_ARG(a16(ggx) && a16(gz) && a16(x) && a16(g_gz) && a16(g_x),
+                "amk_bnact_bwd_bwd: ggx, gz, x, g_gz and g_x must be 16-byte aligned");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const Geo g = make_geo(N, C, HW);
+  const dim3 grid(g.S, C), block(BLOCK);
+  hipLaunchKernelGGL(bwd_bwd_reduce_kernel, grid, block, 0, st, ggx, gz, x, gamma, beta, mean, rstd, g, slope, ws);
+  hipLaunchKernelGGL(bwd_bwd_apply_kernel, grid, block, 0, st, ggx, gg_gamma, gg_beta, gz, x, gamma, beta, mean, rstd,
+                     sums, g, slope, ws, g_gz, g_x, g_gamma);
+  AMK_CHECK_LAUNCH("amk_bnact_bwd_bwd");
+  return AMK_OK;
+}

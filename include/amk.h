@@ -612,6 +612,35 @@ int amk_gemm_bf16(int op, int epi, const void* a, int64_t lda, const void* w, in
 int amk_gemm_bf16_swiglu_bwd(const void* dy, int64_t lddy, const void* w3, int64_t ldw, const void* ab, int64_t ldab,
                              void* dab, int64_t lddab, int64_t M, int H, int K, void* stream);
 
+/* --------------------------------------------------------------------------
+ * Training-mode BatchNorm2d + LeakyReLU(slope) of the PatchGAN discriminator (csrc/discr_norm.hip), f32, contiguous
+ * NCHW x (N, C, HW); reference: models/utils/discriminator.py (BatchNorm2d followed by LeakyReLU(0.2)).
+ * Per channel, n = N HW: mu and var are the biased batch statistics, r = (var + eps)^-1/2, xh = (x - mu) r,
+ * y = gamma xh + beta, z = y > 0 ? y : slope y, s = dz/dy (1 or slope).  y is recomputed from x, never stored.
+ *   fwd     : z; mean, rstd (C) for the backward; running_mean / running_var (C, may be NULL) updated as torch does
+ *             (momentum m; the variance term unbiased, var n / (n - 1)).
+ *   bwd     : gy = s gz, Sgy = sum gy, Sgyx = sum gy xh;  gx = gamma r (gy - Sgy/n - xh Sgyx/n);
+ *             sums (2, C) = (Sgy, Sgyx) for bwd_bwd; dbeta = Sgy and dgamma = Sgyx (C, each may be NULL).
+ *   bwd_bwd : the derivative of bwd given ggx and the optional gg_gamma, gg_beta (C, NULL = 0): with A = Sgy/n,
+ *             B = Sgyx/n, C = sum ggx/n, D = sum ggx xh/n, E = sum ggx gy/n
+ *               g_gz = s [gamma r (ggx - C - xh D) + gg_gamma xh + gg_beta]
+ *               g_x  = -gamma r^2 [xh (E - AC - 3BD) + B (ggx - C) + D (gy - A)] + gg_gamma r (gy - A - xh B)
+ *               g_gamma = n r (E - AC - BD) (may be NULL); the beta gradient is zero.
+ * Any HW; the (N, C, HW) tensors 16-byte aligned; reductions through ordered per-workgroup partials in ws
+ * (amk_bnact_ws_floats(N, C, HW) floats), no atomics: bitwise reproducible.  Two launches per entry point.
+ * -------------------------------------------------------------------------- */
+int64_t amk_bnact_ws_floats(int N, int C, int64_t HW);
+int amk_bnact_fwd(const float* x, const float* gamma, const float* beta, int N, int C, int64_t HW, float eps,
+                  float momentum, float slope, float* z, float* mean, float* rstd, float* running_mean,
+                  float* running_var, float* ws, void* stream);
+int amk_bnact_bwd(const float* gz, const float* x, const float* gamma, const float* beta, const float* mean,
+                  const float* rstd, int N, int C, int64_t HW, float slope, float* gx, float* sums, float* dgamma,
+                  float* dbeta, float* ws, void* stream);
+int amk_bnact_bwd_bwd(const float* ggx, const float* gg_gamma, const float* gg_beta, const float* gz, const float* x,
+                      const float* gamma, const float* beta, const float* mean, const float* rstd, const float* sums,
+                      int N, int C, int64_t HW, float slope, float* g_gz, float* g_x, float* g_gamma, float* ws,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@ models/vitvqgan.py:20-34 under cfg/vitvqgan.yaml:73 (mixed_precision: bf16).
 import pytest
 import torch
 
+import bf16_dense_ref as bref
 from oracle.fixture_recipe import seeded
 from util import rel_err
 
@@ -26,10 +27,13 @@ def test_tn_bf16(device, M, N, K, want_bias):
     dw, db = dense.gemm_tn_bf16(y.to(device), x.to(device), want_bias=want_bias)
     assert dw.dtype == torch.float32 and dw.shape == (N, K)
     assert rel_err(dw, y.double().t() @ x.double()) < TOL
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
     if want_bias:
         assert rel_err(db, y.double().sum(0)) < TOL
+        bref.assert_within({"dw": dw, "db": db}, bref.ref_tn(y, x, cus), ("dw", "db"), f"tn {M}x{N}x{K}")
     else:
         assert db is None
+        bref.assert_within({"dw": dw}, bref.ref_tn(y, x, cus), ("dw",), f"tn {M}x{N}x{K}")
     again = dense.gemm_tn_bf16(y.to(device), x.to(device), want_bias=want_bias)
     assert torch.equal(dw, again[0]), "the chunked sum must be bitwise reproducible"
 
@@ -44,6 +48,8 @@ def test_tn_bf16_strided_rows(device):
     dw, db = dense.gemm_tn_bf16(y, x, want_bias=True)
     assert rel_err(dw, y.double().cpu().t() @ x.double().cpu()) < TOL
     assert rel_err(db, y.double().cpu().sum(0)) < TOL
+    bref.assert_within({"dw": dw, "db": db}, bref.ref_tn(y, x, torch.cuda.get_device_properties(0).multi_processor_count),
+                       ("dw", "db"), "tn strided")
 
 
 def test_tn_bf16_refuses(device):
@@ -105,6 +111,7 @@ def test_nt_bf16(device, M, N, K, bias):
     # exactly the correctly rounded result wherever the fp32 sum is not at a rounding boundary
     exact = (out.cpu() == ref.float().bfloat16()).float().mean().item()
     assert exact > 0.99
+    bref.assert_within({"c": out}, bref.ref_gemm(a, w, b), ("c",), f"nt {M}x{N}x{K}")
 
 
 @pytest.mark.parametrize("M,N,K", FWD_SHAPES)
@@ -116,6 +123,7 @@ def test_nn_bf16(device, M, N, K):
     out = dense.gemm_nn_bf16(a.to(device), w.to(device))
     assert rel_err(out.float(), ref) < TOL16
     assert (out.cpu() == ref.float().bfloat16()).float().mean().item() > 0.99
+    bref.assert_within({"c": out}, bref.ref_gemm(a, w, nn=True), ("c",), f"nn {M}x{N}x{K}")
 
 
 @pytest.mark.parametrize("M,H,K", [(100, 64, 32), (300, 104, 40), (1000, 1368, 256), (129, 40, 256), (4096, 8, 64)])
@@ -130,10 +138,13 @@ def test_nt_swiglu_bf16(device, M, H, K, keep):
     g_ref = F.silu(ab_ref[:, :H]) * ab_ref[:, H:]
     g, ab = dense.gemm_nt_swiglu_bf16(a.to(device), w12.to(device), b12.to(device), keep_ab=keep)
     assert g.shape == (M, H) and rel_err(g.float(), g_ref) < TOL16
+    R = bref.ref_swiglu_fwd(a, w12, b12)
     if keep:
         assert rel_err(ab.float(), ab_ref) < TOL16
+        bref.assert_within({"g": g, "ab": ab}, R, ("g", "ab"), f"swiglu {M}x{H}x{K}")
     else:
         assert ab is None
+        bref.assert_within({"g": g}, R, ("g",), f"swiglu {M}x{H}x{K}")
 
 
 def test_swiglu_ffn_under_autocast(device):
@@ -190,6 +201,7 @@ def test_nn_swiglu_backward_bf16(device, M, H, K):
     g = F.silu(abr[:, :H]) * abr[:, H:]
     (ref,) = torch.autograd.grad(g, abr, dy.double().cpu() @ w3.double().cpu())
     assert rel_err(out.float(), ref) < 2e-2
+    bref.assert_within({"dab": out}, bref.ref_swiglu_bwd(dy, w3, ab), ("dab",), f"swiglu bwd {M}x{H}x{K}")
 
 
 def test_swiglu_ffn_under_autocast_no_grad(device):

@@ -14,7 +14,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle.fixture_recipe import seeded
-from util import rel_err
+from util import assert_close, rel_err
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-5
@@ -41,13 +41,13 @@ def test_nt(device, M, N, K, mode):
     if use_ln:
         mean, rstd = dense.row_stats(ad)
         assert rel_err(mean, a.double().mean(1)) < 1e-5 or a.double().mean(1).abs().max() < 1e-6
-        assert rel_err(rstd, 1.0 / torch.sqrt(a.double().var(1, unbiased=False) + 1e-5)) < TOL
+        assert_close(rstd, 1.0 / torch.sqrt(a.double().var(1, unbiased=False) + 1e-5), TOL)
         ln = (mean, rstd, gam.to(device), bet.to(device))
         src = _ln(a, gam, bet)
     ref = src @ w.double().t() + (b.double() if use_b else 0.0) + (r.double() if use_r else 0.0)
     out = dense.gemm_nt(ad, w.to(device), b.to(device) if use_b else None, resid=r.to(device) if use_r else None, ln=ln)
     assert out.shape == (M, N)
-    assert rel_err(out, ref) < TOL
+    assert_close(out, ref, TOL)
 
 
 @pytest.mark.parametrize("M,N1,N2,K", [(300, 128, 256, 64), (1000, 512, 1024, 256), (64, 256, 100, 40)])
@@ -64,8 +64,8 @@ def test_nt_two_projections(device, M, N1, N2, K, use_ln):
         ln = (*dense.row_stats(ad), gam.to(device), bet.to(device))
         src = _ln(a, gam, bet)
     c1, c2 = dense.gemm_nt(ad, w1.to(device), None, w2=w2.to(device), bias2=b2.to(device), ln=ln)
-    assert rel_err(c1, src @ w1.double().t()) < TOL
-    assert rel_err(c2, src @ w2.double().t() + b2.double()) < TOL
+    assert_close(c1, src @ w1.double().t(), TOL)
+    assert_close(c2, src @ w2.double().t() + b2.double(), TOL)
 
 
 @pytest.mark.parametrize("M,H,K", [(100, 64, 32), (300, 100, 40), (1000, 1368, 256), (129, 36, 256)])
@@ -83,9 +83,9 @@ def test_nt_swiglu(device, M, H, K, use_ln, keep):
     ab_ref = src @ w12.double().t() + b12.double()
     g_ref = F.silu(ab_ref[:, :H]) * ab_ref[:, H:]
     g, ab = dense.gemm_nt_swiglu(ad, w12.to(device), b12.to(device), ln=ln, keep_ab=keep)
-    assert rel_err(g, g_ref) < TOL
+    assert_close(g, g_ref, TOL)
     if keep:
-        assert rel_err(ab, ab_ref) < TOL
+        assert_close(ab, ab_ref, TOL)
     else:
         assert ab is None
 
@@ -99,7 +99,7 @@ def test_nn(device, M, N, K):
         pytest.skip("NN wants output widths that are multiples of 4")
     dy, w = seeded((M, K), 1 + K), seeded((K, N), 2 + N) * K ** -0.5
     out = dense.gemm_nn(dy.to(device), w.to(device))
-    assert rel_err(out, dy.double() @ w.double()) < TOL
+    assert_close(out, dy.double() @ w.double(), TOL)
 
 
 @pytest.mark.parametrize("M,K1,K2,N", [(300, 64, 128, 256), (1000, 512, 1024, 256), (70, 40, 24, 36), (257, 32, 8, 128)])
@@ -109,7 +109,7 @@ def test_nn_two_segments(device, M, K1, K2, N):
     a1, a2 = seeded((M, K1), 1), seeded((M, K2), 2)
     w1, w2 = seeded((K1, N), 3) * K1 ** -0.5, seeded((K2, N), 4) * K2 ** -0.5
     out = dense.gemm_nn(a1.to(device), w1.to(device), a2=a2.to(device), w2=w2.to(device))
-    assert rel_err(out, a1.double() @ w1.double() + a2.double() @ w2.double()) < TOL
+    assert_close(out, a1.double() @ w1.double() + a2.double() @ w2.double(), TOL)
 
 
 @pytest.mark.parametrize("M,H,K", [(100, 64, 32), (300, 100, 40), (1000, 1368, 256)])
@@ -122,7 +122,7 @@ def test_nn_swiglu_backward(device, M, H, K):
     g = F.silu(abr[:, :H]) * abr[:, H:]
     (ref,) = torch.autograd.grad(g, abr, d_out.double() @ w3.double())
     out = dense.gemm_nn(d_out.to(device), w3.to(device), swiglu_ab=ab.to(device))
-    assert rel_err(out, ref) < TOL
+    assert_close(out, ref, TOL)
 
 
 @pytest.mark.parametrize("M,N,K", SHAPES + [(5000, 256, 512), (40000, 128, 128)])
@@ -142,8 +142,8 @@ def test_tn(device, M, N, K, use_ln):
         src = _ln(x, gam, bet)
     dw, dw2, db = dense.gemm_tn(dy.to(device), xd, ln=ln, want_bias=True)
     assert dw2 is None
-    assert rel_err(dw, dy.double().t() @ src) < TOL
-    assert rel_err(db, dy.double().sum(0)) < TOL
+    assert_close(dw, dy.double().t() @ src, TOL)
+    assert_close(db, dy.double().sum(0), TOL)
     again = dense.gemm_tn(dy.to(device), xd, ln=ln, want_bias=True)
     assert torch.equal(dw, again[0]) and torch.equal(db, again[2]), "the chunked sum must be bitwise reproducible"
 
@@ -158,9 +158,9 @@ def test_tn_two_gradients(device, M, N1, N2, K):
     ln = (*dense.row_stats(xd), gam.to(device), bet.to(device))
     src = _ln(x, gam, bet)
     dw1, dw2, db = dense.gemm_tn(y1.to(device), xd, y2=y2.to(device), ln=ln, want_bias=True)
-    assert rel_err(dw1, y1.double().t() @ src) < TOL
-    assert rel_err(dw2, y2.double().t() @ src) < TOL
-    assert rel_err(db, torch.cat([y1.double().sum(0), y2.double().sum(0)])) < TOL
+    assert_close(dw1, y1.double().t() @ src, TOL)
+    assert_close(dw2, y2.double().t() @ src, TOL)
+    assert_close(db, torch.cat([y1.double().sum(0), y2.double().sum(0)]), TOL)
 
 
 def test_refuses_cpu_and_bad_shapes(device):

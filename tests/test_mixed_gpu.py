@@ -7,6 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import bf16_dense_ref as bref
 from oracle.fixture_recipe import seeded
 from util import rel_err
 
@@ -29,6 +30,7 @@ def test_swiglu_bf16(device, M, H):
     assert g.dtype == torch.bfloat16
     assert rel_err(out.float(), ref) < 4e-3
     assert rel_err(g.float(), gref) < 8e-3
+    bref.assert_within({"g": out, "dab": g}, bref.ref_swiglu_mixed(ab, cot), ("g", "dab"), f"swiglu {M}x{H}")
 
 
 @pytest.mark.parametrize("M,D", [(5, 4), (1000, 256), (130, 1024), (33, 768)])
@@ -67,3 +69,11 @@ def test_add_layernorm_mixed(device, M, D, x_bf16, residual):
     if residual:
         assert gs[1].dtype == torch.float32 and rel_err(gs[1], g_ref[1]) < 2e-5
     assert rel_err(gs[-2], g_ref[2]) < 2e-5 and rel_err(gs[-1], g_ref[3]) < 2e-5
+    # per element: dh_in is ch with a residual; without one h is x itself (its gradient adds ch outside the kernel)
+    R = bref.ref_ln(x, r if residual else None, w, b, cy, ch if residual else None)
+    got = {"y": y, "dgamma": gs[-2], "dbeta": gs[-1]}
+    if residual:
+        got.update({"h": h, "dh": gs[1]})
+        if x_bf16:
+            got["dh16"] = gs[0]
+    bref.assert_within(got, R, tuple(got), f"mixed ln M{M} D{D}")

@@ -1199,6 +1199,9 @@ __global__ __launch_bounds__(256, 2) void grouped_wgrad_wide_kernel(GemmParams g
 __global__ __launch_bounds__(256) void combine_kernel(const float* __restrict__ Y, const int64_t* __restrict__ ids,
                                                       const float* __restrict__ scale, int64_t G, int outer, int k,
                                                       int N, int v_div, int E, float* __restrict__ out) {
+  // no contraction in this kernel: the products below are rounded on their own.  (__fmul_rn / __fadd_rn do not say
+  // that here: the HIP headers define them as plain * and +, and the default -ffp-contract=fast made v_pk_fma of them.)
+#pragma clang fp contract(off)
   const int nv = N >> 2;
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (idx >= G * nv) return;
@@ -1219,10 +1222,11 @@ __global__ __launch_bounds__(256) void combine_kernel(const float* __restrict__ 
       const float w = scale ? scale[p] : 1.f;
       const float4 y = ld4(Y + (v_div ? (p / v_div) * E + ids[p] : p) * N + c);
       // res += w * y with separate rounding of the product, as the eager reference does
-      acc.x = __fadd_rn(acc.x, __fmul_rn(w, y.x));
-      acc.y = __fadd_rn(acc.y, __fmul_rn(w, y.y));
-      acc.z = __fadd_rn(acc.z, __fmul_rn(w, y.z));
-      acc.w = __fadd_rn(acc.w, __fmul_rn(w, y.w));
+      const float4 wy = make_float4(w * y.x, w * y.y, w * y.z, w * y.w);
+      acc.x = acc.x + wy.x;
+      acc.y = acc.y + wy.y;
+      acc.z = acc.z + wy.z;
+      acc.w = acc.w + wy.w;
     }
     if (outer == 1) { tot = acc; }
     else { tot.x += acc.x; tot.y += acc.y; tot.z += acc.z; tot.w += acc.w; }

@@ -2,11 +2,14 @@
 not multiples of the 128-wide tiles, more than 64 experts (the unit decode walks the experts 64 at a time),
 experts without pairs, row divisors that are not powers of two, with and without scale / bias -- against a float64
 loop over the pairs (what the reference's per-expert Python loop computes: models/moe.py:27-36,
-models/switchhead_attention.py:63-88)."""
+models/switchhead_attention.py:63-88).  Every result is also held element by element to the two tiers of
+tests/moe_ref.py, whose vectorised references are compared with the pair loops here."""
 import ctypes
 
 import pytest
 import torch
+
+import moe_ref as ref
 
 pytestmark = pytest.mark.gpu
 
@@ -62,24 +65,29 @@ def test_grouped_gemms_vs_pair_loop(device, case):
     sc = scale.cpu().double()
     Ac, Wc, bc, Gc, Xc = (t.cpu().double() for t in (A, W, bias, Gm, X))
 
-    def close(got, want, what):
+    def close(got, want, what, R, name, kernel):
         err = float((got.cpu().double() - want).abs().max())
-        ref = max(float(want.abs().max()), 1e-6)
-        assert err <= 2e-5 * ref, f"{what}: abs err {err:.3e} at scale {ref:.3e}"
+        scale = max(float(want.abs().max()), 1e-6)
+        assert err <= 2e-5 * scale, f"{what}: abs err {err:.3e} at scale {scale:.3e}"
+        # the vectorised fp64 reference is the pair loop (two fp64 summation orders), and every element is within both tiers
+        assert float((R[name].cpu().reshape(want.shape) - want).abs().max()) <= 1e-12 * float(R["S_" + name].max()), what
+        ref.assert_within(got, R, name, kernel, what)
+
+    off, perm = r["offsets"], r["perm"]
 
     # forward: Y[p] = A[p / a_div] W_e^T + b_e
     Y = torch.full((P, N), float("nan"), device=dev)
     L_.check(L.amk_grouped_gemm_nt(ptr(A), Kd, a_div, ptr(W), ptr(bias), ptr(r["offsets"]), ptr(r["perm"]), P, E, N, Kd, ptr(Y), st),
              "amk_grouped_gemm_nt")
     want = torch.stack([Ac[p // a_div] @ Wc[int(ids[p])].t() + bc[int(ids[p])] for p in range(P)])
-    close(Y, want, "grouped_nt")
+    close(Y, want, "grouped_nt", ref.ref_nt(A, Kd, a_div, W, bias, off, perm, P, E, N, Kd), "y", "nt")
 
     # input gradient: Y[p] = s[p] * G[p / a_div] W_e
     Y2 = torch.full((P, Kd), float("nan"), device=dev)
     L_.check(L.amk_grouped_gemm_nn(ptr(Gm), N, a_div, ptr(W), ptr(scale), ptr(r["offsets"]), ptr(r["perm"]), P, E, N, Kd, ptr(Y2), st),
              "amk_grouped_gemm_nn")
     want = torch.stack([sc[p] * (Gc[p // a_div] @ Wc[int(ids[p])]) for p in range(P)])
-    close(Y2, want, "grouped_nn")
+    close(Y2, want, "grouped_nn", ref.ref_nn(Gm, N, a_div, W, scale, off, perm, P, E, N, Kd), "y", "nn")
 
     # the accumulating forms: pair p adds into row p / y_div of a zeroed output (wide shapes only)
     for y_div in (k, 4 * k):
@@ -89,14 +97,14 @@ def test_grouped_gemms_vs_pair_loop(device, case):
                                                ptr(Ya), y_div, st), "amk_grouped_gemm_nt_acc")
             want_a = torch.zeros(Ya.shape, dtype=torch.float64)
             want_a.index_add_(0, torch.arange(P) // y_div, torch.stack([Ac[p // a_div] @ Wc[int(ids[p])].t() + bc[int(ids[p])] for p in range(P)]))
-            close(Ya, want_a, f"grouped_nt_acc y_div={y_div}")
+            close(Ya, want_a, f"grouped_nt_acc y_div={y_div}", ref.ref_nt(A, Kd, a_div, W, bias, off, perm, P, E, N, Kd, y_div), "y", "nt_acc")
         if Kd >= 128 and N % 32 == 0:
             Yb = torch.zeros(((P - 1) // y_div + 1, Kd), device=dev)
             L_.check(L.amk_grouped_gemm_nn_acc(ptr(Gm), N, a_div, ptr(W), ptr(scale), ptr(r["offsets"]), ptr(r["perm"]), P, E, N, Kd,
                                                ptr(Yb), y_div, st), "amk_grouped_gemm_nn_acc")
             want_b2 = torch.zeros(Yb.shape, dtype=torch.float64)
             want_b2.index_add_(0, torch.arange(P) // y_div, want)
-            close(Yb, want_b2, f"grouped_nn_acc y_div={y_div}")
+            close(Yb, want_b2, f"grouped_nn_acc y_div={y_div}", ref.ref_nn(Gm, N, a_div, W, scale, off, perm, P, E, N, Kd, y_div), "y", "nn_acc")
 
     # weight gradient (with and without the scale)
     for use_scale in (True, False):
@@ -110,5 +118,6 @@ def test_grouped_gemms_vs_pair_loop(device, case):
             s = sc[p] if use_scale else 1.0
             want_w[int(ids[p])] += s * torch.outer(Gc[p // a_div], Xc[p // x_div])
             want_b[int(ids[p])] += s * Gc[p // a_div]
-        close(dW, want_w, f"grouped_wgrad dW (scale={use_scale})")
-        close(db, want_b, f"grouped_wgrad dbias (scale={use_scale})")
+        R = ref.ref_wgrad(Gm, N, a_div, X, Kd, x_div, scale if use_scale else None, off, perm, P, E, N, Kd)
+        close(dW, want_w, f"grouped_wgrad dW (scale={use_scale})", R, "dw", "dw")
+        close(db, want_b, f"grouped_wgrad dbias (scale={use_scale})", R, "db", "db")

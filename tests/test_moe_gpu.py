@@ -7,7 +7,7 @@ import torch
 
 from oracle import ref_cpu
 from oracle.fixture_recipe import seeded, seeded_params
-from util import assert_close, load_golden, weights_of
+from util import assert_close, elementwise_violations, load_golden, weights_of
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-5
@@ -102,6 +102,9 @@ def assert_close_abs(a, b, tol, what):
     scale = max(float(b.abs().max()), 1e-3)
     err = float((a - b).abs().max())
     assert err <= tol * scale * 5, f"{what}: abs err {err:.3e} vs scale {scale:.3e}"
+    if b.numel() > 1:   # and element by element, as util.assert_close does (the reference here is an f32 oracle or a golden file)
+        n, worst = elementwise_violations(a, b)
+        assert n == 0, f"{what}: {n} elements off by more than 1e-4 relative + 1e-5 * max (worst {worst:.2f}x the bound)"
 
 
 @pytest.mark.parametrize("variant", ["self", "self_keymask"])

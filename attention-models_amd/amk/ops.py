@@ -199,18 +199,30 @@ def _attn_forward(q, k, v, key_mask, causal_mask, scale, keep_scores=False):
 DETERMINISTIC_ATTENTION_BACKWARD = os.environ.get("AMK_DETERMINISTIC", "0") == "1"
 ATTENTION_BACKWARD_TWO_KERNEL = False
 
+# amk_attn_bwd `stages`: the AMK_ATTN_BWD_* defines of include/amk.h (tests/test_abi.py holds the two together)
+ATTN_BWD_DELTA = 1
+ATTN_BWD_DKDV = 2
+ATTN_BWD_DQ = 4
+ATTN_BWD_FUSED = 8
+ATTN_BWD_ALL = 7          # delta + dK/dV + dQ: reproducible
+ATTN_BWD_FAST = 9         # delta + fused
+ATTN_BWD_KEYS128 = 16
+ATTN_BWD_KEYS256 = 32
+ATTN_BWD_DQ_REPRO = 64
+ATTN_BWD_FAST_REPRO = 73  # delta + fused + reproducible dq
+
 
 def _attn_backward(q, k, v, o, stats, d_o, dq, dk, dv, key_mask, causal_mask, scale, stages=None, delta=None,
                    scores=None):
     if stages is None:
         det = DETERMINISTIC_ATTENTION_BACKWARD or torch.are_deterministic_algorithms_enabled()
-        stages = 7 if ATTENTION_BACKWARD_TWO_KERNEL else (73 if det else 9)
-    if stages & 8 and not stages & 48:
-        stages |= {128: 16, 256: 32}.get(ATTENTION_BACKWARD_KEYS, 0)
-    if not stages & 8:
+        stages = ATTN_BWD_ALL if ATTENTION_BACKWARD_TWO_KERNEL else (ATTN_BWD_FAST_REPRO if det else ATTN_BWD_FAST)
+    if stages & ATTN_BWD_FUSED and not stages & (ATTN_BWD_KEYS128 | ATTN_BWD_KEYS256):
+        stages |= {128: ATTN_BWD_KEYS128, 256: ATTN_BWD_KEYS256}.get(ATTENTION_BACKWARD_KEYS, 0)
+    if not stages & ATTN_BWD_FUSED:
         scores = None
     B, H, I, D = q.shape
-    if D != 64 and stages & 64:
+    if D != 64 and stages & ATTN_BWD_DQ_REPRO:
         scores = None   # head dims other than 64 under the reproducible mode: the two recompute kernels (no kept scores)
     J = k.shape[2]
     d_o = _as_kernel_view(d_o)
@@ -220,7 +232,8 @@ def _attn_backward(q, k, v, o, stats, d_o, dq, dk, dv, key_mask, causal_mask, sc
         delta = torch.empty((need,), device=q.device, dtype=torch.float32)
 
     def call(st):
-        fn, head = (L.amk_attn_bwd_kept, (_ptr(scores),)) if scores is not None and st & 8 else (L.amk_attn_bwd, ())
+        kept = scores is not None and st & ATTN_BWD_FUSED
+        fn, head = (L.amk_attn_bwd_kept, (_ptr(scores),)) if kept else (L.amk_attn_bwd, ())
         rc = fn(
             *head, _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(stats), _ptr(d_o),
             _ptr(dq), _ptr(dk), _ptr(dv), _ptr(delta), _ptr(key_mask), _ptr(causal_mask),
@@ -231,12 +244,12 @@ def _attn_backward(q, k, v, o, stats, d_o, dq, dk, dv, key_mask, causal_mask, sc
         )
         _lib.check(rc, "amk_attn_bwd")
 
-    if KERNEL_EVENTS is not None and (stages & 1) and (stages & ~1):
-        call(1)  # delta on its own so that the events bracket the main kernel(s) only
-        name = "attn_bwd_dkdv+dq" if not stages & 8 else ("attn_bwd_fused_kernel(kept scores)" if scores is not None
-                                                            else "attn_bwd_fused_kernel")
+    if KERNEL_EVENTS is not None and (stages & ATTN_BWD_DELTA) and (stages & ~ATTN_BWD_DELTA):
+        call(ATTN_BWD_DELTA)  # delta on its own so that the events bracket the main kernel(s) only
+        name = "attn_bwd_dkdv+dq" if not stages & ATTN_BWD_FUSED else (
+            "attn_bwd_fused_kernel(kept scores)" if scores is not None else "attn_bwd_fused_kernel")
         with _timed(name):
-            call(stages & ~1)
+            call(stages & ~ATTN_BWD_DELTA)
     else:
         call(stages)
 

@@ -113,6 +113,10 @@ struct RowStagerT {
 };
 typedef RowStagerT<TILE> RowStager;
 
+// what the f32 entry points ask of every tensor: float4 accesses
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline bool strides_ok(const Strides& s) { return (s.sb % 4 == 0) && (s.st % 4 == 0) && (s.sh % 4 == 0); }
+
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 __device__ __forceinline__ float f4(const float4& v, int e) {
@@ -126,8 +130,8 @@ void launch_attn_fwd_x6(const FwdParams& p, int64_t nwg, hipStream_t st);
 bool launch_attn_bwd_fused(const BwdParams& p, int keys_per_wg, hipStream_t st);
 int fused_keys_per_wg(int J, int keys_per_wg);
 
-// attn_generic.hip / attn_generic.h: head dims 32, 96, 128, 160, 192, 224, 256 (forward + the two recompute kernels of
-// the backward)
+// attn_generic.hip / attn_generic.h: the forward for head dims 32, 96, 128, 160, 192, 224, 256 (attn_gen_supported),
+// and the backward's delta and two recompute kernels for those and for 64 (stages: the DELTA, DKDV and DQ bits)
 bool attn_gen_supported(int Dh);
 void launch_attn_fwd_gen(const FwdParams& p, int Dh, int64_t nwg, hipStream_t st);
 void launch_attn_bwd_gen(const BwdParams& p, int Dh, int stages, hipStream_t st);

@@ -520,13 +520,11 @@ __global__ __launch_bounds__(WG, 2) void attn_fwd_plain_kernel(FwdParams p) {
 
 using namespace amk_attn;
 
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 // AMK_ATTN_FWD_PLAIN=0: unmasked calls go through the mask-capable kernel as well (A/B measurements)
 static bool getenv_plain() {   // (read per call: tools/ab_attn_fwd.py flips it inside one process)
   const char* e = getenv("AMK_ATTN_FWD_PLAIN");
   return !(e && e[0] == '0');
 }
-static bool strides_ok(const Strides& s) { return (s.sb % 4 == 0) && (s.st % 4 == 0) && (s.sh % 4 == 0); }
 
 static int attn_fwd_impl(void* x6_ws, bool x6, float* scores, const float* q, const float* k, const float* v, float* o, float* stats,
                          const uint8_t* key_mask, const uint8_t* causal_mask,

@@ -1,10 +1,11 @@
-// Softmax attention for head dims other than 64 (the reference takes any dim_head,
-// models/softmax_attention.py:23): the kernels of attn_fwd.hip / attn_bwd.hip with the head dim as
-// a template parameter, any multiple of 32 up to 256.  Same arithmetic, layouts, masks, statistics and MFMA
-// structure (exact-f32 v_mfma_f32_32x32x2_f32, the reduction axis on the lane, accumulators reused
-// as the next product's B operand); the D = 64 instantiations of attn_fwd.hip / attn_bwd.hip stay the tuned
-// ones (software-pipelined operand reads, kept scores, the one-pass backward) -- these are the
-// plain form: forward, and the two reproducible recompute kernels for the backward.
+// Softmax attention with the head dim as a template parameter, any multiple of 32 up to 256 (the reference takes
+// any dim_head, models/softmax_attention.py:23): the plain form of the forward, and the backward's three reproducible
+// recompute kernels (delta, dK/dV, dQ; no atomics).  Exact-f32 v_mfma_f32_32x32x2_f32, the reduction axis on the
+// lane, accumulators reused as the next product's B operand.
+// The backward kernels serve every head dim, 64 included (instantiated by attn_bwd.hip, next to the dispatch).  The
+// forward here serves the head dims other than 64: the D = 64 forward is the tuned one of attn_fwd.hip
+// (software-pipelined operand reads, kept scores), and the one-pass backwards are attn_bwd_fused.hip (64) and
+// attn_bwd_fused_gen.hip (32 / 128).
 // attn_generic.hip instantiates D = 32 and 128 and dispatches; attn_generic_dNNN.hip one further head dim each
 // (separate translation units, so the build compiles them in parallel).
 #pragma once
@@ -46,6 +47,19 @@ struct GenGeom {
   static constexpr int PK_FWD = DH == 256 ? 8 : 0;
   static constexpr int PK_DQ = DH == 256 ? 16 : 0;
   static constexpr int PK_DK = DH == 256 ? 20 : (DH == 224 ? 12 : (DH == 192 ? 8 : 0));
+  // Head dim 64 has registers to spare in the recompute backward and runs it at two waves per SIMD (the causal
+  // dK / dV, which carries the mask bits on top of both accumulators, at one).  Three refinements keep it inside that
+  // budget and off the VALU; the other head dims sit at the limits above and stay without them:
+  static constexpr int WAVES_DQ = DH <= 64 ? 2 : 1;
+  static constexpr int waves_dkdv(bool causal) { return DH <= 32 || (DH == 64 && !causal) ? 2 : 1; }
+  // a wave-uniform branch around the fill handling where no key of the tile (dQ) or of the wave (dK / dV) is filled
+  // (without it the unmasked dK / dV spills at two waves)
+  static constexpr bool SKIP_FILLS = DH == 64;
+  // the causal-mask bytes of a tile gathered once into one bit word per 32-row sub-tile, tested per element
+  static constexpr bool MASK_BITS = DH == 64;
+  // dK / dV: the products of one P / dS column issue as all of dV's tiles, then dK's, not tile by tile (0.3 % of the
+  // kernel at the ViT-VQGAN layer shape, measured)
+  static constexpr bool DV_FIRST = DH == 64;
 };
 
 // LDS slots for the last PK float4 of one lane's register row: private to the lane (written and read by the same
@@ -482,7 +496,7 @@ __global__ __launch_bounds__(256) void attn_bwd_delta_gen_kernel(BwdParams p) {
 // ------------------------------------------------------------------------------------------------
 // dQ: query on the lane (the forward's skeleton)
 template <int DH, bool CAUSAL>
-__global__ __launch_bounds__(WG, (DH <= 32 ? 2 : 1)) void attn_bwd_dq_gen_kernel(BwdParams p) {
+__global__ __launch_bounds__(WG, GenGeom<DH>::WAVES_DQ) void attn_bwd_dq_gen_kernel(BwdParams p) {
   using G = GenGeom<DH>;
   constexpr int HD = G::HD, LS = G::LS, NT = G::NT, TL = G::TL, NS = G::NS;
   __shared__ __attribute__((aligned(16))) float smem[2 * TL * LS + TL];
@@ -568,6 +582,20 @@ __global__ __launch_bounds__(WG, (DH <= 32 ? 2 : 1)) void attn_bwd_dq_gen_kernel
     commit();
     __syncthreads();
     if (PF && t + 1 < ntile) prefetch(j0 + TL);
+    unsigned cbits[NS] = {};
+    if constexpr (CAUSAL && G::MASK_BITS) {
+      if (qvalid) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+#pragma unroll
+          for (int u = 0; u < NS; ++u) {
+            const int j = j0 + 32 * u + acc_row(r, hf);
+            if (j < p.J && cmrow[j]) cbits[u] |= 1u << r;
+          }
+      }
+    }
+    bool plain = false;   // wave-uniform: nothing in this tile is filled
+    if constexpr (G::SKIP_FILLS && !CAUSAL) plain = kmask == nullptr && j0 + TL <= p.J;
 #pragma unroll
     for (int u = 0; u < NS; ++u) {
       f32x16 s = zero16(), dp = zero16();
@@ -584,21 +612,31 @@ __global__ __launch_bounds__(WG, (DH <= 32 ? 2 : 1)) void attn_bwd_dq_gen_kernel
           dp = mfma32(f4(c, e), s4 < CUT ? greg[4 * s4 + e] : f4(gk, e), dp);
         }
       }
+      if (plain) {  // dS^T = P^T o (dP^T - delta)
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const float4 f = ld4(&Kfill[32 * u + 8 * g + 4 * hf]);
+        for (int r = 0; r < 16; ++r) {
+          const float pr = __builtin_amdgcn_exp2f(s[r] - m_q) * linv_q;
+          s[r] = pr * (dp[r] - delta_q);
+        }
+      } else {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int r = 4 * g + e;
-          const float fe = f4(f, e);
-          bool filled = fe != 0.f;
-          float tt = filled ? fe : s[r];
-          if (CAUSAL) {
-            const int j = j0 + 32 * u + acc_row(r, hf);
-            if (qvalid && j < p.J && cmrow[j]) { tt = AMK_FILL_MASKED; filled = true; }
+        for (int g = 0; g < 4; ++g) {
+          const float4 f = ld4(&Kfill[32 * u + 8 * g + 4 * hf]);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int r = 4 * g + e;
+            const float fe = f4(f, e);
+            bool filled = fe != 0.f;
+            float tt = filled ? fe : s[r];
+            if constexpr (CAUSAL && G::MASK_BITS) {
+              if ((cbits[u] >> r) & 1u) { tt = AMK_FILL_MASKED; filled = true; }
+            } else if (CAUSAL) {
+              const int j = j0 + 32 * u + acc_row(r, hf);
+              if (qvalid && j < p.J && cmrow[j]) { tt = AMK_FILL_MASKED; filled = true; }
+            }
+            const float pr = __builtin_amdgcn_exp2f(tt - m_q) * linv_q;
+            s[r] = filled ? 0.f : pr * (dp[r] - delta_q);  // dS^T (no gradient through fills)
           }
-          const float pr = __builtin_amdgcn_exp2f(tt - m_q) * linv_q;
-          s[r] = filled ? 0.f : pr * (dp[r] - delta_q);  // dS^T (no gradient through fills)
         }
       }
 #pragma unroll
@@ -624,7 +662,7 @@ __global__ __launch_bounds__(WG, (DH <= 32 ? 2 : 1)) void attn_bwd_dq_gen_kernel
 // dK, dV: key on the lane (a wave owns 32 keys; k, v in registers).  PART = DKDV_DV / DKDV_DK computes one of the two
 // (what the other needs alone -- v rows, dP, the deltas -- is dead code there and drops out).
 template <int DH, bool CAUSAL, int PART = DKDV_BOTH>
-__global__ __launch_bounds__(WG, (DH <= 32 ? 2 : 1)) void attn_bwd_dkdv_gen_kernel(BwdParams p) {
+__global__ __launch_bounds__(WG, GenGeom<DH>::waves_dkdv(CAUSAL)) void attn_bwd_dkdv_gen_kernel(BwdParams p) {
   using G = GenGeom<DH>;
   constexpr int HD = G::HD, LS = G::LS, NT = G::NT, TL = G::TL, NS = G::NS;
   __shared__ __attribute__((aligned(16))) float smem[2 * TL * LS + 3 * TL];
@@ -663,6 +701,8 @@ __global__ __launch_bounds__(WG, (DH <= 32 ? 2 : 1)) void attn_bwd_dkdv_gen_kern
   float kfill = 0.f;
   if (!kvalid) kfill = -INFINITY;
   else if (p.key_mask && p.key_mask[(int64_t)b * p.J + kj] == 0) kfill = AMK_FILL_MASKED;
+  bool plain = false;   // wave-uniform: none of this wave's keys is filled
+  if constexpr (G::SKIP_FILLS && !CAUSAL) plain = __all(kfill == 0.f);
 
   const float* qbase = p.q + (int64_t)b * p.qs.sb + (int64_t)h * p.qs.sh;
   const float* gbase = p.d_o + (int64_t)b * p.dos.sb + (int64_t)h * p.dos.sh;
@@ -713,6 +753,18 @@ __global__ __launch_bounds__(WG, (DH <= 32 ? 2 : 1)) void attn_bwd_dkdv_gen_kern
     commit();
     __syncthreads();
     if (PF && t + 1 < ntile) prefetch(i0 + TL);
+    unsigned cbits[NS] = {};
+    if constexpr (CAUSAL && G::MASK_BITS) {
+      if (kvalid) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+#pragma unroll
+          for (int u = 0; u < NS; ++u) {
+            const int i = i0 + 32 * u + acc_row(r, hf);
+            if (i < p.I && cmcol[(int64_t)i * p.J]) cbits[u] |= 1u << r;
+          }
+      }
+    }
 #pragma unroll
     for (int u = 0; u < NS; ++u) {
       f32x16 s = zero16(), dp = zero16();
@@ -737,25 +789,42 @@ __global__ __launch_bounds__(WG, (DH <= 32 ? 2 : 1)) void attn_bwd_dkdv_gen_kern
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int r = 4 * g + e;
+          if (plain) {
+            const float pr = __builtin_amdgcn_exp2f(s[r] - f4(m4, e)) * f4(l4, e);
+            s[r] = pr;                                    // P
+            dp[r] = pr * (dp[r] - f4(d4, e));             // dS
+            continue;
+          }
           bool filled = kfill != 0.f;
           float tt = filled ? kfill : s[r];
-          if (CAUSAL) {
+          if constexpr (CAUSAL && G::MASK_BITS) {
+            if ((cbits[u] >> r) & 1u) { tt = AMK_FILL_MASKED; filled = true; }
+          } else if (CAUSAL) {
             const int i = i0 + 32 * u + acc_row(r, hf);
             if (kvalid && i < p.I && cmcol[(int64_t)i * p.J]) { tt = AMK_FILL_MASKED; filled = true; }
           }
           const float pr = __builtin_amdgcn_exp2f(tt - f4(m4, e)) * f4(l4, e);
-          s[r] = pr;
-          dp[r] = filled ? 0.f : pr * (dp[r] - f4(d4, e));
+          s[r] = pr;                                      // P
+          dp[r] = filled ? 0.f : pr * (dp[r] - f4(d4, e));  // dS (no gradient through fills)
         }
       }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float* gc = &Gs[(32 * u + acc_row(r, hf)) * LS + ln];
         const float* qc = &Qs[(32 * u + acc_row(r, hf)) * LS + ln];
+        if constexpr (G::DV_FIRST) {
 #pragma unroll
-        for (int n = 0; n < NT; ++n) {
-          if (PART != DKDV_DK) dv[n] = mfma32(gc[32 * n], s[r], dv[n]);
-          if (PART != DKDV_DV) dk[n] = mfma32(qc[32 * n], dp[r], dk[n]);
+          for (int n = 0; n < NT; ++n)
+            if (PART != DKDV_DK) dv[n] = mfma32(gc[32 * n], s[r], dv[n]);
+#pragma unroll
+          for (int n = 0; n < NT; ++n)
+            if (PART != DKDV_DV) dk[n] = mfma32(qc[32 * n], dp[r], dk[n]);
+        } else {
+#pragma unroll
+          for (int n = 0; n < NT; ++n) {
+            if (PART != DKDV_DK) dv[n] = mfma32(gc[32 * n], s[r], dv[n]);
+            if (PART != DKDV_DV) dk[n] = mfma32(qc[32 * n], dp[r], dk[n]);
+          }
         }
       }
     }
@@ -812,11 +881,14 @@ void launch_bwd_gen_dh(const BwdParams& p, int stages, hipStream_t st) {
   }
 }
 
+// (head dim 64 has the backward launcher only: its forward is attn_fwd.hip's)
+#define AMK_ATTN_GEN_BWD_INSTANTIATE(DH) template void launch_bwd_gen_dh<DH>(const BwdParams& p, int stages, hipStream_t st);
+#define AMK_ATTN_GEN_BWD_EXTERN(DH) extern AMK_ATTN_GEN_BWD_INSTANTIATE(DH)
 #define AMK_ATTN_GEN_INSTANTIATE(DH)                                                            \
   template void launch_fwd_gen_dh<DH>(const FwdParams& p, int64_t nwg, hipStream_t st);        \
-  template void launch_bwd_gen_dh<DH>(const BwdParams& p, int stages, hipStream_t st);
+  AMK_ATTN_GEN_BWD_INSTANTIATE(DH)
 #define AMK_ATTN_GEN_EXTERN(DH)                                                                 \
   extern template void launch_fwd_gen_dh<DH>(const FwdParams& p, int64_t nwg, hipStream_t st); \
-  extern template void launch_bwd_gen_dh<DH>(const BwdParams& p, int stages, hipStream_t st);
+  AMK_ATTN_GEN_BWD_EXTERN(DH)
 
 }  // namespace amk_attn

@@ -123,9 +123,11 @@ int amk_attn_fwd_x6(const float* q, const float* k, const float* v, float* o, fl
  * `stages` selects the launches.  bit 0: delta = rowsum(dO*O) into delta_ws (must have run
  * before any other bit).  Then EITHER bit 3 (AMK_ATTN_BWD_FUSED): one pass, each of the five
  * products computed once, dq accumulated with f32 atomics (dq must be the dense (B,I,H,D) layout;
- * it is zeroed here; dq differs in the last bits from run to run; falls back to the two-kernel
- * path when a causal mask is given or dq is strided) -- OR bits 1 and 2: two recompute kernels,
- * dK/dV and dQ, no atomics, bitwise reproducible.  Profilers time one stage by passing its bit. */
+ * it is zeroed here; dq differs in the last bits from run to run; key and causal masks are taken;
+ * falls back to the two-kernel path when dq is strided, and at the head dims that have no one-pass
+ * kernel: it exists for 32, 64 and 128) -- OR bits 1 and 2: two recompute kernels, dK/dV and dQ,
+ * no atomics, bitwise reproducible, one template family for every head dim.  Profilers time one
+ * stage by passing its bit. */
 #define AMK_ATTN_BWD_DELTA 1
 #define AMK_ATTN_BWD_DKDV 2
 #define AMK_ATTN_BWD_DQ 4
@@ -159,8 +161,9 @@ int amk_attn_bwd(const float* q, const float* k, const float* v, const float* o,
                  float scale, int stages, void* stream);
 /* amk_attn_bwd reading the scores amk_attn_fwd_keep left (same q, k, masks, scale): the fused pass skips
  * its S = QK^T product; the results are those of amk_attn_bwd bit for bit (dq up to the atomics' order).
- * `stages` must contain AMK_ATTN_BWD_FUSED; when the fused pass cannot run (causal mask, strided dq) the
- * two recompute kernels run and the scores are not read. */
+ * `stages` must contain AMK_ATTN_BWD_FUSED; when the fused pass cannot run (strided dq) the two recompute
+ * kernels run and the scores are not read at head dim 64; head dims 32 / 128 refuse that call
+ * (AMK_EUNSUPPORTED). */
 int amk_attn_bwd_kept(const float* scores, const float* q, const float* k, const float* v, const float* o,
                       const float* stats, const float* d_o,
                       float* dq, float* dk, float* dv, float* delta_ws,

@@ -23,6 +23,19 @@ def test_library_exports_every_declared_symbol():
     assert L.amk_arch() == b"gfx950"
 
 
+def test_attn_bwd_stage_names_equal_the_header_defines():
+    """ops.ATTN_BWD_* are the AMK_ATTN_BWD_* defines of include/amk.h, every one of them and value for value."""
+    import re
+
+    from amk import ops
+
+    with open(amk_lib.HEADER_PATH) as f:
+        defines = {m[1]: int(m[2]) for m in re.finditer(r"^#define AMK_(ATTN_BWD_\w+)\s+(\d+)\b", f.read(), re.M)}
+    assert {"ATTN_BWD_DELTA", "ATTN_BWD_DKDV", "ATTN_BWD_DQ", "ATTN_BWD_FUSED", "ATTN_BWD_DQ_REPRO"} <= set(defines)
+    in_ops = {n: getattr(ops, n) for n in dir(ops) if n.startswith("ATTN_BWD_")}
+    assert in_ops == defines
+
+
 def test_argument_errors_are_reported_not_crashed():
     L = amk_lib.load()
     null = ctypes.c_void_p(0)

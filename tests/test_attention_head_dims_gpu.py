@@ -213,13 +213,20 @@ def test_autocast_dim_head_96(device):
     assert err < 2e-2, err
 
 
-@pytest.mark.parametrize("D", NEW_DIMS)
-def test_launches_generic_kernels(device, D):
-    """The forward and backward run the head-dim kernels themselves, not a padded D = 128 / 256 path."""
+@pytest.mark.parametrize("D", NEW_DIMS + [64])
+def test_launches_generic_kernels(device, D, monkeypatch):
+    """The forward and backward run the head-dim kernels themselves, not a padded D = 128 / 256 path.  Head dim 64 has
+    its own forward and one-pass backward; its reproducible two-kernel backward is the D = 64 instantiation of the same
+    recompute kernels, and no hand-written copy of them runs."""
     from torch.profiler import ProfilerActivity, profile
 
     from amk import ops
 
+    kernels = ["attn_bwd_delta_gen_kernel", "attn_bwd_dkdv_gen_kernel", "attn_bwd_dq_gen_kernel"]
+    if D == 64:
+        monkeypatch.setattr(ops, "ATTENTION_BACKWARD_TWO_KERNEL", True)
+    else:
+        kernels.append("attn_fwd_gen_plain_kernel")
     q, k, v = (seeded((1, 2, 100, D), s).to(device).requires_grad_(True) for s in (1, 2, 3))
     with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
         o = ops.attention(q, k, v, D ** -0.5)
@@ -227,8 +234,10 @@ def test_launches_generic_kernels(device, D):
         torch.cuda.synchronize()
     names = [e.name for e in prof.events()]
     tag = f"<{D},"
-    for kernel in ("attn_fwd_gen_plain_kernel", "attn_bwd_delta_gen_kernel", "attn_bwd_dkdv_gen_kernel", "attn_bwd_dq_gen_kernel"):
+    for kernel in kernels:
         hits = [n for n in names if kernel in n]
         assert hits, (kernel, sorted(set(names))[:40])
         assert all(tag in n or f"<{D}>" in n or f"ILi{D}E" in n for n in hits), hits
     assert not any("attn_bf16" in n for n in names)
+    for old in ("attn_bwd_delta_kernel", "attn_bwd_dkdv_kernel", "attn_bwd_dq_kernel"):
+        assert not any(old in n for n in names), (old, [n for n in names if old in n])

@@ -1251,12 +1251,9 @@ extern "C" int amk_agent_attn_bwd(const float* q, const float* k, const float* v
                           span_ok(p.dqs, H, T, Dh) && span_ok(p.dks, H, T, Dh) && span_ok(p.dvs, H, T, Dh),
                       "amk_agent_attn_bwd: one batch entry of a tensor must span less than 2 GiB with non-negative strides");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  static int stream_mode = -1;   // AMK_AGENT_STREAM=0: the LDS-staged chunk kernels also for P <= 8 (head dim 64)
-  if (stream_mode < 0) {
-    const char* e = getenv("AMK_AGENT_STREAM");
-    stream_mode = e ? atoi(e) : 1;
-  }
-  const bool streaming = stream_mode && P <= 8;
+  // AMK_AGENT_STREAM=0: the LDS-staged chunk kernels also for P <= 8 (head dim 64); read per call, like AMK_MOE_NARROW
+  const char* e = getenv("AMK_AGENT_STREAM");
+  const bool streaming = (e ? atoi(e) : 1) && P <= 8;
   if (Dh == 32) agent_bwd_launch<32>(p, st, streaming);
   else if (Dh == 128) agent_bwd_launch<128>(p, st, streaming);
   else agent_bwd_launch<64>(p, st, streaming);

@@ -349,6 +349,7 @@ int amk_moe_gate_grad(const float* d_out, const float* Y, const int64_t* ids, co
  *   32       | 128   | LDS-staged (AMK_AGENT_STREAM does not apply)
  *   64       | 128   | streaming for P <= 8 (AMK_AGENT_STREAM=0: LDS-staged), LDS-staged for P > 8
  *   128      |  64   | LDS-staged (AMK_AGENT_STREAM does not apply)
+ * AMK_AGENT_STREAM is read on every call of amk_agent_attn_bwd.
  * amk_agent_num_chunks / amk_agent_ws_floats are the D = 64 sizes; the _dh forms take the head
  * dim and return 0 for an unsupported one.
  * -------------------------------------------------------------------------- */

@@ -43,9 +43,17 @@ class BiDirectionalTransformer(nn.Module):
         if isinstance(m, (nn.Linear, nn.Embedding)):
             nn.init.trunc_normal_(m.weight.data, 0.0, 0.02)
 
-    def forward(self, x):
+    def hidden(self, x):
         x = self.input_proj(x) + self.pos_enc
-        return self.linear(self.final_norm(self.decoder(self.init_norm(x))))
+        return self.decoder(self.init_norm(x))
+
+    def forward(self, x):
+        return self.linear(self.final_norm(self.hidden(x)))
+
+    def loss_from_hidden(self, hidden, target, ignore_index=-1):
+        """The training loss from the hidden states without the logits in memory: final_norm, then the fused logits +
+        cross-entropy head on the rows whose target is not ignore_index (csrc/ce_head.hip)."""
+        return ops.linear_cross_entropy(self.final_norm(hidden), self.linear.weight, target, ignore_index)
 
 
 class MaskGitTransformer(nn.Module):
@@ -75,6 +83,9 @@ class MaskGitTransformer(nn.Module):
         with torch.no_grad():
             x = self.vq.encode_imgs(imgs)
         x, tgt, mask = self.fill_mask(x)
+        bt = self.bidirectional_transformer
+        if self.training and ops.ce_head_ok(bt.pos_enc, bt.linear.weight):
+            return bt.loss_from_hidden(bt.hidden(x), tgt, -1)
         output = self.bidirectional_transformer(x)
         if not self.training:  # (models/maskgit.py:176-185) fill the masked positions greedily and decode
             pred = output.argmax(dim=-1)

@@ -56,10 +56,17 @@ class BidirectionalDecoder(nn.Module):
         elif isinstance(module, nn.Embedding):
             nn.init.trunc_normal_(module.weight, std=0.02)
 
-    def forward(self, img_token_indices, context=None, context_mask=None):
+    def hidden(self, img_token_indices, context=None, context_mask=None):
         x = self.token_emb(img_token_indices) + self.pos_enc
-        x = self.decoder(dec_in=x, context=context, context_mask=context_mask)
-        return self.linear(self.final_norm(x))
+        return self.decoder(dec_in=x, context=context, context_mask=context_mask)
+
+    def forward(self, img_token_indices, context=None, context_mask=None):
+        return self.linear(self.final_norm(self.hidden(img_token_indices, context, context_mask)))
+
+    def loss_from_hidden(self, hidden, target, ignore_index=-1):
+        """The training loss from the decoder's hidden states without the logits in memory: final_norm, then the fused
+        logits + cross-entropy head on the rows whose target is not ignore_index (csrc/ce_head.hip)."""
+        return ops.linear_cross_entropy(self.final_norm(hidden), self.linear.weight, target, ignore_index)
 
 
 class MUSE(nn.Module):
@@ -97,6 +104,8 @@ class MUSE(nn.Module):
             tokens = self.vq.encode_imgs(imgs)
         inp, tgt = self.fill_mask(tokens)
         keep = torch.rand((ctx.shape[0], 1, 1), device=ctx.device) < self.embeds_drop_prob
+        if ops.ce_head_ok(ctx, self.decoder.linear.weight):
+            return self.decoder.loss_from_hidden(self.decoder.hidden(inp, context=ctx * keep), tgt, self.ignore_index)
         logits = self.decoder(inp, context=ctx * keep)
         return F.cross_entropy(logits.transpose(1, 2), tgt, ignore_index=self.ignore_index)
 

@@ -1750,3 +1750,97 @@ def bn_leaky_relu(x, bn, slope):
         bn.num_batches_tracked.add_(1)
     return _BNAct.apply(_bn_aligned(x), bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum,
                         float(slope))
+
+
+# ---------------------------------------------------------------------------- masked-token loss head
+# Logits + cross-entropy on the valid rows only (csrc/ce_head.hip) in place of F.linear + F.cross_entropy at the end of
+# the Muse / MaskGit train step: the (rows, vocabulary) logits, their log-softmax and their gradient are never written.
+# Measured at the Muse head (8192 rows, 8192 words, dim 1024, cosine-schedule targets; tools/kbench_ce_head.py,
+# profiles/kbench_ce_head.log): 3.89 ms against 22.45 ms forward + backward, 336 MB against 805 MB of peak memory above the
+# inputs; bench.py --model muse 195.4 against 215.6 ms per step.  So the switch ships on.  Read once per process.
+CE_HEAD = os.environ.get("AMK_CE_HEAD", "1") != "0"
+
+
+def ce_head_ok(x, weight):
+    """The models' gate: the switch is on, f32 HIP tensors, no autocast (a bf16-MFMA variant is the follow-up)."""
+    return (CE_HEAD and x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32
+            and not torch.is_autocast_enabled() and x.shape[-1] % 4 == 0 and x.numel() > 0)
+
+
+def _row_major_view(t2):
+    """t2 (rows, cols) as the kernels take it: unit column stride, row stride a multiple of 4, 16-byte aligned."""
+    if t2.stride(1) != 1 or t2.stride(0) % 4 or t2.stride(0) < t2.shape[1] or t2.data_ptr() % 16:
+        t2 = t2.contiguous()
+        if t2.data_ptr() % 16:
+            t2 = t2.clone()
+    return t2
+
+
+class _LinearCrossEntropy(torch.autograd.Function):
+    """mean over the rows with target != ignore_index of logsumexp(x W^T) - (x W^T)[target]; saves lse, the compacted row
+    list and the device-side count -- the number of valid rows is never read on the host."""
+
+    @staticmethod
+    def forward(ctx, x, weight, target, ignore_index):
+        K = x.shape[-1]
+        x2 = _row_major_view(x.reshape(-1, K))
+        w2 = _row_major_view(weight)
+        t = target.reshape(-1).contiguous()
+        M, V = x2.shape[0], w2.shape[0]
+        if t.shape[0] != M or w2.shape[1] != K:
+            raise RuntimeError(f"linear_cross_entropy: x {tuple(x.shape)}, weight {tuple(weight.shape)}, target "
+                               f"{tuple(target.shape)} do not fit")
+        L = _lib.load()
+        dev = x2.device
+        nbytes = L.amk_ce_head_fwd_ws_bytes(M, V, K)
+        ws = torch.empty(max(nbytes // 4, 4), device=dev, dtype=torch.float32)
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        lse = torch.empty(M, device=dev, dtype=torch.float32)
+        rows = torch.empty(M, device=dev, dtype=torch.int32)
+        count = torch.empty(1, device=dev, dtype=torch.int32)
+        with _timed(f"ce_head_fwd M{M} V{V} K{K}"):
+            _lib.check(L.amk_ce_head_fwd(_ptr(x2), x2.stride(0), _ptr(w2), w2.stride(0), _ptr(t), int(ignore_index), M, V, K,
+                                         _ptr(loss), _ptr(lse), _ptr(rows), _ptr(count), _ptr(ws), nbytes, _stream()),
+                       "amk_ce_head_fwd")
+        ctx.save_for_backward(x2, w2, t, lse, rows, count)
+        ctx.ignore_index = int(ignore_index)
+        ctx.x_shape = x.shape
+        ctx.weight = weight
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_loss):
+        x2, w2, t, lse, rows, count = ctx.saved_tensors
+        M, K = x2.shape
+        V = w2.shape[0]
+        L = _lib.load()
+        dev = x2.device
+        d = d_loss.reshape(1).to(torch.float32).contiguous()   # stays on the device
+        dx = torch.empty(M, K, device=dev, dtype=torch.float32)
+        wr, wv = _claim(ctx.weight) if ctx.needs_input_grad[1] else (None, None)
+        if wv is not None and (wv.stride(-1) != 1 or wv.data_ptr() % 16 or wv.shape != w2.shape or wv.stride(0) % 4):
+            wr, wv = None, None   # (not reached with the reducer's views: ALIGN-ed, contiguous)
+        dw = wv if wv is not None else torch.empty(V, K, device=dev, dtype=torch.float32)
+        nbytes = L.amk_ce_head_bwd_ws_bytes(M, V, K)
+        ws = torch.empty(max(nbytes // 4, 4), device=dev, dtype=torch.float32)
+        with _timed(f"ce_head_bwd M{M} V{V} K{K}"):
+            _lib.check(L.amk_ce_head_bwd(_ptr(x2), x2.stride(0), _ptr(w2), w2.stride(0), _ptr(t), ctx.ignore_index, M, V, K,
+                                         _ptr(d), _ptr(lse), _ptr(rows), _ptr(count), _ptr(dx), dx.stride(0),
+                                         _ptr(dw), dw.stride(0), _ptr(ws), nbytes, _stream()),
+                       "amk_ce_head_bwd")
+        if wv is not None:
+            wr.wrote(ctx.weight)
+            dw = None
+        return dx.view(ctx.x_shape), dw, None, None
+
+
+def linear_cross_entropy(x, weight, target, ignore_index=-100):
+    """F.cross_entropy(F.linear(x, weight).flatten(0, -2), target.flatten(), ignore_index=ignore_index) as one op that
+    never writes the logits: x (..., K) f32, weight (V, K), target (...) int64 -> scalar f32 (mean over the rows whose
+    target is not ignore_index; NaN when there is none).  A target outside [0, V) that is not ignore_index poisons the
+    loss (NaN) instead of raising: raising would need the host to read device data.  Once differentiable."""
+    _require_device(x, weight, target)
+    if target.dtype != torch.int64:
+        raise RuntimeError(f"linear_cross_entropy: target must be int64; got {target.dtype}")
+    return _LinearCrossEntropy.apply(x, weight, target, ignore_index)

@@ -645,6 +645,40 @@ int amk_bnact_bwd_bwd(const float* ggx, const float* gg_gamma, const float* gg_b
                       int N, int C, int64_t HW, float slope, float* g_gz, float* g_x, float* g_gamma, float* ws,
                       void* stream);
 
+/* --------------------------------------------------------------------------
+ * Masked-token loss head (csrc/ce_head.hip): logits + cross-entropy on the rows that count, f32 on
+ * v_mfma_f32_32x32x2_f32.  Replaces decoder.linear(...) followed by F.cross_entropy(logits.transpose(1, 2), tgt,
+ * ignore_index=-1) of the reference's train steps (models/muse.py:176, models/maskgit.py:187):
+ *   z[m, v] = sum_k x[m, k] w[v, k]                     x (M, K) at row stride ldx, w (V, K) at ldw, no bias
+ *   loss    = mean over the rows with target[m] != ignore_index of  logsumexp_v z[m, v] - z[m, target[m]]
+ * The logits are never written in the forward and rows with target == ignore_index cost no matrix work: `rows`
+ * (int32, M) receives the valid row indices in ascending order (entries past count: -1) and `count` (int32, 1) their
+ * number, both on the device and never read on the host, so the call is safe under graph capture.  lse[i], i < count,
+ * is the log-sum-exp of row rows[i] (entries past count are not written).  The forward is free of atomics: bitwise
+ * reproducible.
+ * count == 0: loss is NaN (0 / 0, as torch), dx and dw are zeros, nothing faults.
+ * A target that is neither ignore_index nor in [0, V) is never used as an index.  Its row counts as valid (count
+ * includes it), makes the loss NaN, and neither receives nor gives a gradient: its dx row is zero and it adds nothing
+ * to dw, while d_loss / count still divides by the count that includes it.
+ * Backward: d_loss is a DEVICE scalar.  g[i, v] = (exp(z - lse[i]) - [v == target]) d_loss / count is recomputed into
+ * ws (compacted rows at stride V rounded up to 128, transient); dx[rows] = g w at row stride lddx, rows that are
+ * ignored or out of range written as exact zeros; dw = g^T x[rows] (V, K) at lddw, fully overwritten.  Fixed
+ * accumulation orders: bitwise reproducible.  Only the K floats of a row are written in dx / dw (padding untouched).
+ * ws: amk_ce_head_fwd_ws_bytes / _bwd_ws_bytes bytes (0 for sizes outside the limits), contents undefined on return.
+ * AMK_EINVAL: null pointer, non-positive size, a leading dimension below K, misaligned pointer (x, w, dx, dw, ws: 16
+ * bytes; target: 8; the others: 4), workspace too small.  AMK_EUNSUPPORTED: K or a leading dimension not a multiple
+ * of 4; M > 2^24, V > 2^22, K > 2^16, or a grid of 2^31 workgroups.  All refusals precede any device work.
+ * -------------------------------------------------------------------------- */
+int64_t amk_ce_head_fwd_ws_bytes(int64_t M, int V, int K);
+int64_t amk_ce_head_bwd_ws_bytes(int64_t M, int V, int K);
+int amk_ce_head_fwd(const float* x, int64_t ldx, const float* w, int64_t ldw, const int64_t* target,
+                    int64_t ignore_index, int64_t M, int V, int K, float* loss, float* lse, int32_t* rows,
+                    int32_t* count, void* ws, int64_t ws_bytes, void* stream);
+int amk_ce_head_bwd(const float* x, int64_t ldx, const float* w, int64_t ldw, const int64_t* target,
+                    int64_t ignore_index, int64_t M, int V, int K, const float* d_loss, const float* lse,
+                    const int32_t* rows, const int32_t* count, float* dx, int64_t lddx, float* dw, int64_t lddw,
+                    void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1761,15 +1761,33 @@ def bn_leaky_relu(x, bn, slope):
 CE_HEAD = os.environ.get("AMK_CE_HEAD", "1") != "0"
 
 
+# AMK_CE_HEAD_BF16: the same head under bf16 autocast (csrc/ce_head_bf16.hip: bf16 operands on v_mfma_f32_32x32x16_bf16,
+# the logits and every softmax quantity in f32) in place of the library's three GEMMs over all rows, the bf16 logits,
+# their f32 copy, the log-softmax and the logits' gradient.  Measured at the Muse head (tools/kbench_ce_head.py --autocast
+# bf16, profiles/kbench_ce_head_bf16.log): 0.75 ms against 18.70 ms forward + backward, 201 MB against 688 MB of peak memory
+# above the inputs; bench.py --model muse --autocast bf16 63.3 against 81.7 ms per step on the parent commit
+# (profiles/bench_muse_ce_head_bf16.log).  So the switch ships on.  AMK_CE_HEAD=0 disables both heads.  Read once per process.
+CE_HEAD_BF16 = os.environ.get("AMK_CE_HEAD_BF16", "1") != "0"
+
+
+def _bf16_autocast():
+    return torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16
+
+
 def ce_head_ok(x, weight):
-    """The models' gate: the switch is on, f32 HIP tensors, no autocast (a bf16-MFMA variant is the follow-up)."""
-    return (CE_HEAD and x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32
-            and not torch.is_autocast_enabled() and x.shape[-1] % 4 == 0 and x.numel() > 0)
+    """The models' gate.  Without autocast: the switch is on, f32 HIP tensors, K a multiple of 4.  Under bf16 autocast:
+    both switches are on, HIP tensors, an f32 master weight, K a multiple of 8 (the bf16 head)."""
+    if not (CE_HEAD and x.is_cuda and weight.dtype == torch.float32 and x.numel() > 0):
+        return False
+    if torch.is_autocast_enabled():
+        return (CE_HEAD_BF16 and _bf16_autocast() and x.dtype in (torch.float32, torch.bfloat16)
+                and x.shape[-1] % 8 == 0)
+    return x.dtype == torch.float32 and x.shape[-1] % 4 == 0
 
 
-def _row_major_view(t2):
-    """t2 (rows, cols) as the kernels take it: unit column stride, row stride a multiple of 4, 16-byte aligned."""
-    if t2.stride(1) != 1 or t2.stride(0) % 4 or t2.stride(0) < t2.shape[1] or t2.data_ptr() % 16:
+def _row_major_view(t2, mult=4):
+    """t2 (rows, cols) as the kernels take it: unit column stride, row stride a multiple of mult, 16-byte aligned."""
+    if t2.stride(1) != 1 or t2.stride(0) % mult or t2.stride(0) < t2.shape[1] or t2.data_ptr() % 16:
         t2 = t2.contiguous()
         if t2.data_ptr() % 16:
             t2 = t2.clone()
@@ -1835,12 +1853,77 @@ class _LinearCrossEntropy(torch.autograd.Function):
         return dx.view(ctx.x_shape), dw, None, None
 
 
+class _LinearCrossEntropyBF16(torch.autograd.Function):
+    """_LinearCrossEntropy under bf16 autocast (csrc/ce_head_bf16.hip): x cast to bf16 if it arrives in f32, the weight
+    through _w16 (the optimizer's bf16 shadow when it is current); loss and lse in f32, dx in x's dtype, dw in f32 --
+    into the reducer's bucket when it can be claimed.  Saves x16, w16, target, lse, rows and count only."""
+
+    @staticmethod
+    def forward(ctx, x, weight, target, ignore_index):
+        K = x.shape[-1]
+        x16 = _row_major_view(x.reshape(-1, K).to(torch.bfloat16), 8)
+        w16 = _row_major_view(_w16(weight), 8)
+        t = target.reshape(-1).contiguous()
+        M, V = x16.shape[0], w16.shape[0]
+        if t.shape[0] != M or w16.shape[1] != K:
+            raise RuntimeError(f"linear_cross_entropy: x {tuple(x.shape)}, weight {tuple(weight.shape)}, target "
+                               f"{tuple(target.shape)} do not fit")
+        L = _lib.load()
+        dev = x16.device
+        nbytes = L.amk_ce_head_bf16_fwd_ws_bytes(M, V, K)
+        ws = torch.empty(max(nbytes // 4, 4), device=dev, dtype=torch.float32)
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        lse = torch.empty(M, device=dev, dtype=torch.float32)
+        rows = torch.empty(M, device=dev, dtype=torch.int32)
+        count = torch.empty(1, device=dev, dtype=torch.int32)
+        with _timed(f"bf16_ce_head_fwd M{M} V{V} K{K}"):
+            _lib.check(L.amk_ce_head_bf16_fwd(_ptr(x16), x16.stride(0), _ptr(w16), w16.stride(0), _ptr(t), int(ignore_index),
+                                              M, V, K, _ptr(loss), _ptr(lse), _ptr(rows), _ptr(count), _ptr(ws), nbytes,
+                                              _stream()), "amk_ce_head_bf16_fwd")
+        ctx.save_for_backward(x16, w16, t, lse, rows, count)
+        ctx.ignore_index = int(ignore_index)
+        ctx.x_shape, ctx.x_dtype = x.shape, x.dtype
+        ctx.weight = weight
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_loss):
+        x16, w16, t, lse, rows, count = ctx.saved_tensors
+        M, K = x16.shape
+        V = w16.shape[0]
+        L = _lib.load()
+        dev = x16.device
+        d = d_loss.reshape(1).to(torch.float32).contiguous()   # stays on the device
+        dx = torch.empty(M, K, device=dev, dtype=torch.bfloat16)
+        wr, wv = _claim(ctx.weight) if ctx.needs_input_grad[1] else (None, None)
+        if wv is not None and (wv.stride(-1) != 1 or wv.data_ptr() % 16 or wv.shape != w16.shape or wv.stride(0) % 8
+                               or wv.dtype != torch.float32):
+            wr, wv = None, None   # (not reached with the reducer's views: ALIGN-ed, contiguous)
+        dw = wv if wv is not None else torch.empty(V, K, device=dev, dtype=torch.float32)
+        nbytes = L.amk_ce_head_bf16_bwd_ws_bytes(M, V, K)
+        ws = torch.empty(max(nbytes // 2, 8), device=dev, dtype=torch.bfloat16)
+        with _timed(f"bf16_ce_head_bwd M{M} V{V} K{K}"):
+            _lib.check(L.amk_ce_head_bf16_bwd(_ptr(x16), x16.stride(0), _ptr(w16), w16.stride(0), _ptr(t), ctx.ignore_index,
+                                              M, V, K, _ptr(d), _ptr(lse), _ptr(rows), _ptr(count), _ptr(dx), dx.stride(0),
+                                              _ptr(dw), dw.stride(0), _ptr(ws), nbytes, _stream()), "amk_ce_head_bf16_bwd")
+        if wv is not None:
+            wr.wrote(ctx.weight)
+            dw = None
+        return dx.view(ctx.x_shape).to(ctx.x_dtype), dw, None, None
+
+
 def linear_cross_entropy(x, weight, target, ignore_index=-100):
     """F.cross_entropy(F.linear(x, weight).flatten(0, -2), target.flatten(), ignore_index=ignore_index) as one op that
     never writes the logits: x (..., K) f32, weight (V, K), target (...) int64 -> scalar f32 (mean over the rows whose
-    target is not ignore_index; NaN when there is none).  A target outside [0, V) that is not ignore_index poisons the
+    target is not ignore_index; NaN when there is none).  Inside bf16 autocast: x f32 or bf16, weight the f32 master, the
+    products on bf16 operands with the logits and the softmax in f32 (csrc/ce_head_bf16.hip).  A target outside [0, V) that is not ignore_index poisons the
     loss (NaN) instead of raising: raising would need the host to read device data.  Once differentiable."""
-    _require_device(x, weight, target)
+    bf16 = _bf16_autocast()
+    _require_device(*((weight, target) if bf16 and x.is_cuda and x.dtype == torch.bfloat16 else (x, weight, target)))
     if target.dtype != torch.int64:
         raise RuntimeError(f"linear_cross_entropy: target must be int64; got {target.dtype}")
+    if bf16:   # bf16 operands (x cast, the weight's bf16 shadow), f32 loss, dx in x's dtype, dw in f32
+        with torch.autocast("cuda", enabled=False):
+            return _LinearCrossEntropyBF16.apply(x, weight, target, ignore_index)
     return _LinearCrossEntropy.apply(x, weight, target, ignore_index)

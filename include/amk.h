@@ -679,6 +679,40 @@ int amk_ce_head_bwd(const float* x, int64_t ldx, const float* w, int64_t ldw, co
                     const int32_t* rows, const int32_t* count, float* dx, int64_t lddx, float* dw, int64_t lddw,
                     void* ws, int64_t ws_bytes, void* stream);
 
+/* --------------------------------------------------------------------------
+ * The masked-token loss head under bf16 autocast (csrc/ce_head_bf16.hip): the head above with bf16 operands on
+ * v_mfma_f32_32x32x16_bf16.  x (M, K) and w (V, K) are bf16, row-major with unit column stride; products accumulate in
+ * f32 and every softmax quantity stays in f32 (running maximum, sum of exp, lse, the target logit, the loss,
+ * d_loss / count): the logits are never rounded to bf16 and never written in the forward.  loss and lse are f32.
+ * Semantics as above, restated:
+ *   - a row is valid when target[m] != ignore_index; `rows` (int32, M: the valid indices ascending, then -1) and
+ *     `count` (int32, 1) are built on the device and never read on the host; every grid is sized from M and a row tile
+ *     that starts at or past count exits before any load (rows with an ignored target are never read);
+ *   - count == 0: loss is NaN, dx and dw are zeros;
+ *   - a target outside [0, V) that is not ignore_index makes the loss NaN, takes and gives no gradient, and is still
+ *     counted in the divisor of the mean and of d_loss / count;
+ *   - the dx rows of ignored and out-of-range targets are written as exact zeros;
+ *   - no atomics: forward and backward are bitwise reproducible from run to run.
+ * Backward: d_loss is a DEVICE scalar (f32).  g = (exp(z - lse) - [v == target]) d_loss / count is recomputed in f32 and
+ * rounded once to bf16 into ws (compacted rows at stride V rounded up to 128, transient: M x that stride bf16);
+ * dx[rows] = g w (bf16 at row stride lddx, f32 accumulation over ascending v, one rounding); dw = g^T x[rows] (V, K) F32
+ * at lddw (f32 accumulation over ascending compacted row), fully overwritten.  Only the K elements of a row are written
+ * in dx / dw (padding untouched).
+ * ws: amk_ce_head_bf16_fwd_ws_bytes / _bwd_ws_bytes bytes (0 for sizes outside the limits), contents undefined on return.
+ * AMK_EINVAL: null pointer, non-positive size, a leading dimension below K, misaligned pointer (x, w, dx, dw, ws: 16
+ * bytes; target: 8; the others: 4), workspace too small.  AMK_EUNSUPPORTED: K or a leading dimension not a multiple
+ * of 8; M > 2^24, V > 2^22, K > 2^16, or a grid of 2^31 workgroups.  All refusals precede any device work.
+ * -------------------------------------------------------------------------- */
+int64_t amk_ce_head_bf16_fwd_ws_bytes(int64_t M, int V, int K);
+int64_t amk_ce_head_bf16_bwd_ws_bytes(int64_t M, int V, int K);
+int amk_ce_head_bf16_fwd(const void* x, int64_t ldx, const void* w, int64_t ldw, const int64_t* target,
+                         int64_t ignore_index, int64_t M, int V, int K, float* loss, float* lse, int32_t* rows,
+                         int32_t* count, void* ws, int64_t ws_bytes, void* stream);
+int amk_ce_head_bf16_bwd(const void* x, int64_t ldx, const void* w, int64_t ldw, const int64_t* target,
+                         int64_t ignore_index, int64_t M, int V, int K, const float* d_loss, const float* lse,
+                         const int32_t* rows, const int32_t* count, void* dx, int64_t lddx, float* dw, int64_t lddw,
+                         void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

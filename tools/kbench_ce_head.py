@@ -8,8 +8,14 @@ rows, the work the fused op replaces -- against the f32 MFMA peak.
 Cases: the Muse head of bench.py --model muse (8192 rows, 8192 words, dim 1024) with targets drawn by fill_mask's cosine
 schedule; a MaskGit-sized head (8 x 256 tokens, dim 768, 8192 words, same schedule); the Muse head with every row valid.
 The default rule of AMK_CE_HEAD (README): on only if the fused op is not slower than the parent path at the Muse size by
-more than the spread."""
+more than the spread.
+
+--autocast bf16: the same three cases inside torch.autocast("cuda", bfloat16) with bf16 inputs and an f32 master weight,
+as the autocast train step has them: the fused op is then csrc/ce_head_bf16.hip, the parent path F.linear +
+F.cross_entropy as autocast runs them (bf16 GEMMs over all rows, bf16 logits, their f32 copy for the softmax), and the
+credited TFLOP/s are set against the dense bf16 MFMA peak.  The same rule decides the default of AMK_CE_HEAD_BF16."""
 import argparse
+import contextlib
 import math
 import os
 import statistics
@@ -24,6 +30,7 @@ import torch.nn.functional as F  # noqa: E402
 from amk import ops  # noqa: E402
 
 PEAK = 157.3   # TFLOP/s, f32 MFMA
+PEAK_BF16 = 2500.0   # TFLOP/s, dense bf16 MFMA (the figure DESIGN.md uses)
 CASES = [("muse 8x1024 d1024 V8192", 8, 1024, 1024, 8192, "schedule"),
          ("maskgit 8x256 d768 V8192", 8, 256, 768, 8192, "schedule"),
          ("muse, every row valid", 8, 1024, 1024, 8192, "all")]
@@ -40,17 +47,22 @@ def schedule_targets(B, T, V, dev, mode):
     return tokens.masked_fill(~(order < n_masked.unsqueeze(-1)), -1)
 
 
-def make(B, T, K, V, mode, dev):
-    x = torch.randn(B, T, K, device=dev).requires_grad_()
+def make(B, T, K, V, mode, dev, autocast=None):
+    x = torch.randn(B, T, K, device=dev, dtype=torch.bfloat16 if autocast else torch.float32).requires_grad_()
     w = (torch.randn(V, K, device=dev) * 0.02).requires_grad_()
     tgt = schedule_targets(B, T, V, dev, mode)
 
+    def amp():
+        return torch.autocast("cuda", dtype=autocast) if autocast else contextlib.nullcontext()
+
     def fused():
-        loss = ops.linear_cross_entropy(x, w, tgt, -1)
+        with amp():
+            loss = ops.linear_cross_entropy(x, w, tgt, -1)
         return torch.autograd.grad(loss, (x, w))
 
     def parent():
-        loss = F.cross_entropy(F.linear(x, w).transpose(1, 2), tgt, ignore_index=-1)
+        with amp():
+            loss = F.cross_entropy(F.linear(x, w).transpose(1, 2), tgt, ignore_index=-1)
         return torch.autograd.grad(loss, (x, w))
 
     return {"fused": fused, "parent": parent}, float((tgt != -1).float().mean())
@@ -82,14 +94,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--autocast", choices=["none", "bf16"], default="none")
     args = ap.parse_args()
+    autocast = torch.bfloat16 if args.autocast == "bf16" else None
+    peak = PEAK_BF16 if autocast else PEAK
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
+    print(f"autocast {args.autocast}: fused = {'csrc/ce_head_bf16.hip' if autocast else 'csrc/ce_head.hip'}, credited TFLOP/s "
+          f"against {peak:g}")
     print(f"forward + backward, median of {args.rounds} alternating rounds x {args.iters} calls; spread = max - min of the rounds")
     print(f"{'case':>26} {'valid':>6} {'parent ms':>10} {'spread':>7} {'fused ms':>9} {'spread':>7} {'fused/parent':>12} "
           f"{'parent MB':>10} {'fused MB':>9} {'credited TF':>11} {'of peak':>8}")
     for name, B, T, K, V, mode in CASES:
-        fns, frac = make(B, T, K, V, mode, dev)
+        fns, frac = make(B, T, K, V, mode, dev, autocast)
         res = {k: [] for k in fns}
         for r in range(args.rounds + 1):
             for k in ("parent", "fused"):
@@ -101,7 +118,7 @@ def main():
         sp, sf = max(res["parent"]) - min(res["parent"]), max(res["fused"]) - min(res["fused"])
         tf = 3 * 2.0 * B * T * V * K / (f * 1e-3) / 1e12
         print(f"{name:>26} {frac:6.2f} {p:10.3f} {sp:7.3f} {f:9.3f} {sf:7.3f} {f / p:12.2f} {mem['parent']:10.0f} "
-              f"{mem['fused']:9.0f} {tf:11.1f} {tf / PEAK:8.3f}", flush=True)
+              f"{mem['fused']:9.0f} {tf:11.1f} {tf / peak:8.3f}", flush=True)
         del fns
 
 

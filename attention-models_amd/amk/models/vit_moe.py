@@ -4,6 +4,7 @@ SwitchHead experts and the MoE FFN, as in the reference (models/vit_moe.py:26-27
 import torch
 import torch.nn as nn
 
+from .. import ops
 from .layers import LayerNorm
 from .attention import SwitchHeadAttention
 from .moe import MoELayer
@@ -39,7 +40,9 @@ class Encoder(nn.Module):
         n = layers[0].norm1(x)
         for i, layer in enumerate(layers):
             a = layer.self_attn(x=n, context_mask=context_mask)
-            x, n = layer.norm2(a, residual=x)
+            # norm2's output feeds only the MoE gate (a Linear) and the experts: with the bf16 expert kernels on it is produced
+            # in bf16 directly under bf16 autocast (no cast pass in front of the experts; 11.69 -> 11.53 ms per step at configs[3])
+            x, n = layer.norm2(a, residual=x, branch=ops.MOE_BF16)
             m = layer.moe(n)
             if i + 1 < len(layers):
                 x, n = layers[i + 1].norm1(m, residual=x)

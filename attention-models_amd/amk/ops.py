@@ -743,7 +743,101 @@ class _RoutedLinear(torch.autograd.Function):
         return dx, dlogits, dW, db, None, None, None, None
 
 
+# AMK_MOE_BF16: MoELayer's routed expert products under bf16 autocast on bf16 operands (csrc/moe_bf16.hip,
+# v_mfma_f32_32x32x16_bf16, f32 accumulation and f32 outputs) instead of upcasting the activations and running the f32
+# kernels of csrc/moe.hip.  0: the path before (inputs upcast, f32 kernels).  Measurements: README, "Switches".  Read once
+# per process.
+MOE_BF16 = os.environ.get("AMK_MOE_BF16", "1") != "0"
+
+
+class _RoutedLinearBF16(torch.autograd.Function):
+    """_RoutedLinear in MoELayer's form (weighted, outer 1) under bf16 autocast: the routing on the f32 logits as ever, x
+    cast to bf16 if it arrives in f32, the weight through _w16 (the optimizer's bf16 shadow when it is current), the
+    three expert products by csrc/moe_bf16.hip with f32 Y / dW / db, combine and gate gradient by the f32 kernels.  out is
+    f32; dx and dlogits come back in the dtypes of x and logits."""
+
+    @staticmethod
+    def forward(ctx, x2, logits2, W, bias, k, x_div):
+        _require_device(W, bias)
+        U, E = logits2.shape
+        N, Kd = W.shape[1], W.shape[2]
+        P = U * k
+        if x2.shape != (P // x_div, Kd):
+            raise RuntimeError(f"routed linear shapes disagree: x {tuple(x2.shape)} U {U} k {k} x_div {x_div} W {tuple(W.shape)}")
+        if not (x2.is_cuda and logits2.is_cuda):
+            raise RuntimeError("amk ops run only on MI355X (HIP) tensors; got a CPU tensor. There is no CPU fallback.")
+        dev = x2.device
+        x16 = _row_major_view(x2.to(torch.bfloat16), 8)
+        w16 = _w16(W).contiguous()
+        with _timed(f"moe_route U{U} E{E} k{k}"):
+            r = moe_route(logits2.detach().float(), k)
+        L = _lib.load()
+        b32 = bias.detach().contiguous() if bias is not None else None
+        Y = torch.empty((P, N), device=dev, dtype=torch.float32)
+        with _timed(f"bf16_grouped_nt P{P} N{N} K{Kd}"):
+            rc = L.amk_grouped_gemm_nt_bf16(_ptr(x16), x16.stride(0), x_div, _ptr(w16), _ptr(b32), _ptr(r["offsets"]), _ptr(r["perm"]),
+                                            P, E, N, Kd, _ptr(Y), _stream())
+        _lib.check(rc, "amk_grouped_gemm_nt_bf16")
+        out = torch.empty((U, N), device=dev, dtype=torch.float32)
+        with _timed(f"moe_combine G{U} N{N} x{k}"):
+            rc = L.amk_moe_combine(_ptr(Y), _ptr(r["ids"]), _ptr(r["gate"]), U, 1, k, N, _ptr(out), _stream())
+        _lib.check(rc, "amk_moe_combine")
+        ctx.save_for_backward(x16, w16, Y, r["ids"], r["gate"], r["offsets"], r["perm"])
+        ctx.cfg = (k, x_div, E, bias is not None, x2.dtype, logits2.dtype)
+        ctx.mark_non_differentiable(r["ids"])
+        ctx.set_materialize_grads(False)
+        return out, r["ids"]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_out, _d_ids):
+        if d_out is None:
+            return (None,) * 6
+        x16, w16, Y, ids, gate, offsets, perm = ctx.saved_tensors
+        k, x_div, E, has_bias, x_dtype, l_dtype = ctx.cfg
+        N, Kd = w16.shape[1], w16.shape[2]
+        P = ids.numel()
+        U = P // k
+        dev = x16.device
+        d_out = d_out.to(torch.float32).contiguous()
+        d16 = d_out.to(torch.bfloat16)   # once, for both products
+        L = _lib.load()
+        dlogits = torch.empty((U, E), device=dev, dtype=torch.float32)
+        rc = L.amk_moe_gate_grad(_ptr(d_out), _ptr(Y), _ptr(ids), _ptr(gate), P, k, E, N, k, _ptr(dlogits), _stream())
+        _lib.check(rc, "amk_moe_gate_grad")
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dxp = torch.empty((P, Kd), device=dev, dtype=torch.float32)
+            with _timed(f"bf16_grouped_nn P{P} N{N} K{Kd}"):
+                rc = L.amk_grouped_gemm_nn_bf16(_ptr(d16), N, k, _ptr(w16), _ptr(gate), _ptr(offsets), _ptr(perm), P, E, N, Kd,
+                                                _ptr(dxp), _stream())
+            _lib.check(rc, "amk_grouped_gemm_nn_bf16")
+            dx = torch.empty(x16.shape, device=dev, dtype=torch.float32)
+            rc = L.amk_moe_combine(_ptr(dxp), _ptr(ids), _NULL, x16.shape[0], x_div // k, k, Kd, _ptr(dx), _stream())
+            _lib.check(rc, "amk_moe_combine")
+            dx = dx.to(x_dtype)
+        dW = torch.empty((E, N, Kd), device=dev, dtype=torch.float32)
+        db = torch.empty((E, N), device=dev, dtype=torch.float32) if has_bias else None
+        with _timed(f"bf16_grouped_wgrad P{P} N{N} K{Kd}"):
+            rc = L.amk_grouped_gemm_wgrad_bf16(_ptr(d16), N, k, _ptr(x16), x16.stride(0), x_div, _ptr(gate), _ptr(offsets), _ptr(perm),
+                                               P, E, N, Kd, _ptr(dW), _ptr(db), _stream())
+        _lib.check(rc, "amk_grouped_gemm_wgrad_bf16")
+        return dx, dlogits.to(l_dtype), dW, db, None, None
+
+
+def _moe_bf16_ok(x2, logits2, W, bias, weighted, outer):
+    """MoELayer's form under bf16 autocast on HIP tensors, an f32 master weight, N and Kd multiples of 8."""
+    return (MOE_BF16 and weighted and outer == 1 and torch.is_autocast_enabled()
+            and torch.get_autocast_dtype("cuda") == torch.bfloat16 and x2.is_cuda and logits2.is_cuda and W.is_cuda
+            and W.dtype == torch.float32 and W.dim() == 3 and W.shape[1] % 8 == 0 and W.shape[2] % 8 == 0
+            and x2.dtype in (torch.float32, torch.bfloat16) and logits2.dtype in (torch.float32, torch.bfloat16)
+            and (bias is None or bias.dtype == torch.float32))
+
+
 def routed_linear(x2, logits2, W, bias, k, x_div, weighted=True, outer=1):
+    if _moe_bf16_ok(x2, logits2, W, bias, weighted, outer):
+        with torch.autocast("cuda", enabled=False):
+            return _RoutedLinearBF16.apply(x2, logits2, W, bias, k, x_div)
     return _RoutedLinear.apply(x2, logits2, W, bias, k, x_div, weighted, outer)
 
 

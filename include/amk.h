@@ -713,6 +713,35 @@ int amk_ce_head_bf16_bwd(const void* x, int64_t ldx, const void* w, int64_t ldw,
                          const int32_t* rows, const int32_t* count, void* dx, int64_t lddx, float* dw, int64_t lddw,
                          void* ws, int64_t ws_bytes, void* stream);
 
+/* --------------------------------------------------------------------------
+ * The routed expert products of MoELayer under bf16 autocast (csrc/moe_bf16.hip): the per-expert nn.Linear layers of
+ * models/moe.py:23-38 inside accelerator.autocast() (trainers/vit.py:67), forward, input gradient and weight / bias
+ * gradient, on v_mfma_f32_32x32x16_bf16.  They take the offsets (E+1) / perm lists of amk_moe_route and the a_div /
+ * g_div / x_div addressing of amk_grouped_gemm_nt / _nn / _wgrad; rows the lists do not name are left untouched, an
+ * expert without pairs gets exactly zero dW and dbias.  Operands are bf16, accumulation is f32 and every OUTPUT IS
+ * F32 (Y feeds amk_moe_combine / amk_moe_gate_grad unchanged; dW and dbias are parameter gradients).  No atomics, no
+ * workspace, nothing allocated or synchronised: bitwise reproducible from run to run and capturable.
+ *   nt:    Y[p,:] = A[p / a_div,:] W[e(p)]^T + bias[e(p)]; A bf16 rows of Kd at stride lda, W bf16 (E,N,Kd), bias f32
+ *          (E,N) or NULL, Y f32 (P,N).
+ *   nn:    Y[p,:] = scale[p] (G[p / a_div,:] W[e(p)]); G bf16 rows of N at stride ldg, scale f32 (P) or NULL (applied
+ *          in f32 after the chain), Y f32 (P,Kd).
+ *   wgrad: dW[e] = sum_{p in e} scale[p] G[p / g_div,:]^T (x) X[p / x_div,:], dbias[e] = sum scale[p] G[..]; G, X bf16,
+ *          scale[p] G rounded once to bf16 where it is staged; dW f32 (E,N,Kd) and dbias f32 (E,N) or NULL, both fully
+ *          overwritten.
+ * AMK_EINVAL: null pointer, non-positive size, a pointer not 16-byte aligned, a row stride that is not a multiple of 8
+ * or is shorter than the row.  AMK_EUNSUPPORTED: N or Kd not a multiple of 8, E > 1024, a buffer of 2 GiB or more, a
+ * grid of 2^31 workgroups.  All refusals precede any device work.
+ * -------------------------------------------------------------------------- */
+int amk_grouped_gemm_nt_bf16(const void* A, int64_t lda, int a_div, const void* W, const float* bias,
+                             const int32_t* offsets, const int32_t* perm, int64_t P, int E, int N, int Kd,
+                             float* Y, void* stream);
+int amk_grouped_gemm_nn_bf16(const void* G, int64_t ldg, int a_div, const void* W, const float* scale,
+                             const int32_t* offsets, const int32_t* perm, int64_t P, int E, int N, int Kd,
+                             float* Y, void* stream);
+int amk_grouped_gemm_wgrad_bf16(const void* G, int64_t ldg, int g_div, const void* X, int64_t ldx, int x_div,
+                                const float* scale, const int32_t* offsets, const int32_t* perm,
+                                int64_t P, int E, int N, int Kd, float* dW, float* dbias, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

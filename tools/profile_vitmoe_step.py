@@ -1,6 +1,6 @@
 """ViTMoE (BASELINE.json configs[3]) forward + cross-entropy + backward at batch 64, a few steps: the workload
 `rocprofv3 --kernel-trace --stats` is pointed at to see where a step's time goes.
-    python tools/profile_vitmoe_step.py [--steps 5] [--graph]
+    python tools/profile_vitmoe_step.py [--steps 5] [--autocast bf16] [--events]
 """
 import argparse
 import os
@@ -19,6 +19,7 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--events", action="store_true", help="HIP events around the routed-expert launches: per-launch table")
+    ap.add_argument("--autocast", choices=["none", "bf16"], default="none", help="bf16: the forward inside torch.autocast, as the autocast train step runs it")
     ap.add_argument("--no-tune", action="store_true", help="library GEMMs without TunableOp (keeps its trial kernels out of a profile)")
     a = ap.parse_args()
     from amk import tuning
@@ -35,7 +36,9 @@ def main():
 
     def step():
         vm.zero_grad(set_to_none=True)
-        torch.nn.functional.cross_entropy(vm(imgs), labels).backward()
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=a.autocast == "bf16"):
+            out = vm(imgs)
+        torch.nn.functional.cross_entropy(out.float(), labels).backward()
 
     for _ in range(3):
         step()

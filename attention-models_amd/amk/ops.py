@@ -109,10 +109,26 @@ def _mask_u8(mask, shape, what):
     return m.to(torch.uint8).contiguous()
 
 
-# Forward path of the attention core: "f32" = exact-f32 MFMA (v_mfma_f32_32x32x2_f32); "bf16x6" = the same
-# kernel with every product formed from three-way bf16 splits of its f32 operands (six exact partial
-# products, f32 accumulation): f32-level error, 2.6x the matrix rate.  See csrc/attn_fwd_x6.hip.
-ATTENTION_FORWARD = os.environ.get("AMK_ATTENTION_FORWARD", "f32")
+# Forward path of the attention core (head dim 64, f32): "f32" = exact-f32 MFMA (v_mfma_f32_32x32x2_f32); "bf16x6" = the
+# same algorithm with every product formed from three-way bf16 splits of its f32 operands (six exact partial products,
+# f32 accumulation, csrc/attn_fwd_x6.hip): f32-level error at 2.6x the matrix rate, for a pre-pass that splits K and V
+# once per call.  Both keep the scores for the fused backward under the same conditions.  "auto" (the default): the
+# autograd entry points (attention, attention_fused_kv and the modules on top of them) take the split-bf16 forward when
+# the call is large enough (ATTENTION_X6_MIN_KEYS, ATTENTION_X6_MIN_SCORES), the f32 one below; a direct _attn_forward call stays on the f32
+# kernel (bench.py times that call against the f32 MFMA peak).  AMK_ATTENTION_FORWARD=f32 restores the f32 launches
+# everywhere.
+ATTENTION_FORWARD = os.environ.get("AMK_ATTENTION_FORWARD", "auto")
+if ATTENTION_FORWARD not in ("auto", "f32", "bf16x6"):
+    raise RuntimeError(f"AMK_ATTENTION_FORWARD must be auto, f32 or bf16x6 (got {ATTENTION_FORWARD!r})")
+# "auto": the pre-pass is a fixed cost per call (one more launch, 48 KiB written per (batch, head, 64-key tile)) that a
+# small call does not earn back.  Measured at batch 32, 8 heads, scores kept, f32 against split-bf16 (pre-pass included,
+# profiles/kbench_attn_fwd_x6.log): (I, J) = (1024, 1024) 0.584 / 0.530 ms, (1024, 77) 0.094 / 0.076 ms, (65, 65)
+# 0.025 / 0.030 ms.  Back to back the split-bf16 forward wins at 77 keys, but the Muse decoder step, whose
+# cross-attention has that shape, ran 0.25 % slower with it under graph replay (194.55 against 194.06 ms, three
+# alternating runs each, profiles/attn_fwd_x6_keep_step_breakdown.log).  So "auto" asks for at least two 64-key tiles and
+# for at least 2^22 scores in the call ((65, 65) at batch 32 has 2^20).
+ATTENTION_X6_MIN_KEYS = 128
+ATTENTION_X6_MIN_SCORES = 1 << 22
 
 # Training: the forward leaves the raw scores S (4 bytes per (b, h, i, j), 32x32 tiles) in HBM and the fused
 # backward reads them back instead of recomputing S = QK^T -- four matrix products instead of five, bit for
@@ -139,8 +155,9 @@ def _release_kept(nbytes):
 ATTENTION_BACKWARD_KEYS = int(os.environ.get("AMK_ATTN_BWD_KEYS", "0"))
 
 
-def _attn_forward(q, k, v, key_mask, causal_mask, scale, keep_scores=False):
-    """Returns (q, k, v, o, stats, scores); scores is None unless keep_scores and the f32 kernel ran."""
+def _attn_forward(q, k, v, key_mask, causal_mask, scale, keep_scores=False, auto_x6=False):
+    """Returns (q, k, v, o, stats, scores); scores is None unless keep_scores and the scores fit the budgets.
+    auto_x6: what ATTENTION_FORWARD == "auto" resolves to for this caller (the autograd entry points pass True)."""
     B, H, I, D = q.shape
     J = k.shape[2]
     _require_device(q, k, v, key_mask, causal_mask)
@@ -150,7 +167,11 @@ def _attn_forward(q, k, v, key_mask, causal_mask, scale, keep_scores=False):
     o = _new_bthd(B, H, I, D, q)
     stats = torch.empty((B, H, I, 2), device=q.device, dtype=torch.float32)
     L = _lib.load()
-    x6 = ATTENTION_FORWARD == "bf16x6" and D == 64  # every other head dim runs the plain f32 kernels
+    if ATTENTION_FORWARD not in ("auto", "f32", "bf16x6"):
+        raise RuntimeError(f"ops.ATTENTION_FORWARD must be auto, f32 or bf16x6 (got {ATTENTION_FORWARD!r})")
+    x6 = D == 64 and (ATTENTION_FORWARD == "bf16x6"   # every other head dim runs the plain f32 kernels
+                      or (ATTENTION_FORWARD == "auto" and auto_x6 and J >= ATTENTION_X6_MIN_KEYS
+                          and B * H * I * J >= ATTENTION_X6_MIN_SCORES))
     ws = torch.empty((L.amk_attn_fwd_x6_ws_bytes(B, H, J),), device=q.device, dtype=torch.uint8) if x6 else None
     scores = None
     # (head dim 128: the score-keeping forward exists without masks, and its one-pass backward takes atomics only.  Head dim
@@ -159,15 +180,21 @@ def _attn_forward(q, k, v, key_mask, causal_mask, scale, keep_scores=False):
     # The other head dims, 96 to 256, have no score-keeping forward nor one-pass backward: they always recompute)
     det = DETERMINISTIC_ATTENTION_BACKWARD or torch.are_deterministic_algorithms_enabled()
     keepable = D == 64 or (D == 128 and key_mask is None and causal_mask is None and not det)
-    if (keep_scores and keepable and not x6 and ATTENTION_KEEP_SCORES
-            and not ATTENTION_BACKWARD_TWO_KERNEL):
+    if keep_scores and keepable and ATTENTION_KEEP_SCORES and not ATTENTION_BACKWARD_TWO_KERNEL:
         nbytes = L.amk_attn_scores_bytes(B, H, I, J)
         if nbytes <= ATTENTION_KEEP_SCORES_MAX_BYTES and _kept_scores_bytes[0] + nbytes <= _keep_budget(q.device):
             scores = torch.empty((nbytes // 4,), device=q.device, dtype=torch.float32)
             _kept_scores_bytes[0] += nbytes
             weakref.finalize(scores.untyped_storage(), _release_kept, nbytes)
-    with _timed("attn_fwd_keep_kernel" if scores is not None else "attn_fwd_kernel"):
-        if scores is not None:
+    # (the split-bf16 launches under names of their own: bench.py sets the attn_fwd_* names against the f32 MFMA peak)
+    with _timed(("attn_fwd_x6" if x6 else "attn_fwd") + ("_keep_kernel" if scores is not None else "_kernel")):
+        if x6 and scores is not None:
+            rc = L.amk_attn_fwd_x6_keep(
+                _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(stats), _ptr(ws), _ptr(scores), _ptr(key_mask), _ptr(causal_mask),
+                B, H, I, J, D, *_strides4(q), *_strides4(k), *_strides4(v), *_strides4(o),
+                float(scale), _stream(),
+            )
+        elif scores is not None:
             rc = L.amk_attn_fwd_keep(
                 _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(stats), _ptr(scores), _ptr(key_mask), _ptr(causal_mask),
                 B, H, I, J, D, *_strides4(q), *_strides4(k), *_strides4(v), *_strides4(o),
@@ -269,7 +296,7 @@ class _AttnCore(torch.autograd.Function):
     @_amp_fwd
     def forward(ctx, q, k, v, key_mask, causal_mask, scale):
         need = any(ctx.needs_input_grad[:3])
-        q, k, v, o, stats, scores = _attn_forward(q, k, v, key_mask, causal_mask, scale, keep_scores=need)
+        q, k, v, o, stats, scores = _attn_forward(q, k, v, key_mask, causal_mask, scale, keep_scores=need, auto_x6=True)
         ctx.save_for_backward(q, k, v, o, stats, key_mask, causal_mask, scores)
         ctx.scale = scale
         return o
@@ -305,7 +332,7 @@ class _AttnFusedKV(torch.autograd.Function):
         k = kv[:, :, 0].permute(0, 2, 1, 3)
         v = kv[:, :, 1].permute(0, 2, 1, 3)
         need = any(ctx.needs_input_grad[:2])
-        q, k, v, o, stats, scores = _attn_forward(q, k, v, key_mask, causal_mask, scale, keep_scores=need)
+        q, k, v, o, stats, scores = _attn_forward(q, k, v, key_mask, causal_mask, scale, keep_scores=need, auto_x6=True)
         ctx.save_for_backward(q, k, v, o, stats, key_mask, causal_mask, scores)
         ctx.scale = scale
         return o.permute(0, 2, 1, 3).reshape(B, I, H * D)

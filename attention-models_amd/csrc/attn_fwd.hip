@@ -520,7 +520,7 @@ __global__ __launch_bounds__(WG, 2) void attn_fwd_plain_kernel(FwdParams p) {
 
 using namespace amk_attn;
 
-// AMK_ATTN_FWD_PLAIN=0: unmasked calls go through the mask-capable kernel as well (A/B measurements)
+// AMK_ATTN_FWD_PLAIN=0: unmasked calls go through the mask-capable kernels as well, f32 and split-bf16 (A/B measurements)
 static bool getenv_plain() {   // (read per call: tools/ab_attn_fwd.py flips it inside one process)
   const char* e = getenv("AMK_ATTN_FWD_PLAIN");
   return !(e && e[0] == '0');
@@ -565,7 +565,7 @@ static int attn_fwd_impl(void* x6_ws, bool x6, float* scores, const float* q, co
   if (Dh != D)
     launch_attn_fwd_gen(p, Dh, nwg, st);
   else if (x6)
-    launch_attn_fwd_x6(p, nwg, st);
+    launch_attn_fwd_x6(p, nwg, st, getenv_plain());
   else if (!causal_mask && !key_mask && getenv_plain() && scores)
     hipLaunchKernelGGL((attn_fwd_plain_kernel<true>), dim3((unsigned)nwg), dim3(WG), 0, st, p);
   else if (!causal_mask && !key_mask && getenv_plain())
@@ -627,4 +627,17 @@ extern "C" int amk_attn_fwd_x6(const float* q, const float* k, const float* v, f
                                float scale, void* stream) {
   return attn_fwd_impl(ws, true, nullptr, q, k, v, o, stats, key_mask, causal_mask, B, H, I, J, Dh, q_sb, q_st, q_sh, k_sb, k_st, k_sh,
                        v_sb, v_st, v_sh, o_sb, o_st, o_sh, scale, stream);
+}
+
+extern "C" int amk_attn_fwd_x6_keep(const float* q, const float* k, const float* v, float* o, float* stats, void* ws, float* scores,
+                                    const uint8_t* key_mask, const uint8_t* causal_mask,
+                                    int B, int H, int I, int J, int Dh,
+                                    int64_t q_sb, int64_t q_st, int64_t q_sh,
+                                    int64_t k_sb, int64_t k_st, int64_t k_sh,
+                                    int64_t v_sb, int64_t v_st, int64_t v_sh,
+                                    int64_t o_sb, int64_t o_st, int64_t o_sh,
+                                    float scale, void* stream) {
+  AMK_CHECK_ARG(scores, "amk_attn_fwd_x6_keep: null scores buffer");
+  return attn_fwd_impl(ws, true, scores, q, k, v, o, stats, key_mask, causal_mask, B, H, I, J, Dh, q_sb, q_st, q_sh, k_sb, k_st,
+                       k_sh, v_sb, v_st, v_sh, o_sb, o_st, o_sh, scale, stream);
 }

@@ -101,7 +101,8 @@ int amk_attn_fwd_keep(const float* q, const float* k, const float* v, float* o, 
  * (24 mantissa bits) and each product is the sum of six exact partial products accumulated in f32
  * (v_mfma_f32_32x32x16_bf16).  Same arguments, outputs, statistics and masks; the error against a
  * double-precision result is that of the f32 MFMA path (1.5e-6 vs 2.6e-6 on K = 64 dot products,
- * tools/ubench_bf16x6.hip), not that of a bf16 computation.  The backward is amk_attn_bwd either way.
+ * tools/ubench_bf16x6.hip), not that of a bf16 computation.  The backward is amk_attn_bwd, or amk_attn_bwd_kept
+ * after amk_attn_fwd_x6_keep.
  * ws: amk_attn_fwd_x6_ws_bytes(B, H, J) bytes (48 KiB per (batch, head, 64-key tile): K and V split into
  * bf16 planes once per call by a pre-pass); contents undefined on return. */
 int64_t amk_attn_fwd_x6_ws_bytes(int B, int H, int J);
@@ -113,6 +114,18 @@ int amk_attn_fwd_x6(const float* q, const float* k, const float* v, float* o, fl
                     int64_t v_sb, int64_t v_st, int64_t v_sh,
                     int64_t o_sb, int64_t o_st, int64_t o_sh,
                     float scale, void* stream);
+/* amk_attn_fwd_x6 that also leaves its raw scores (the split-bf16 products, before any fill) for amk_attn_bwd_kept:
+ * `scores` as for amk_attn_fwd_keep (non-null, 16-byte aligned, amk_attn_scores_bytes(B, H, I, J) bytes, same layout),
+ * head dim 64 only.  The backward then forms P from the very scores the forward's statistics were taken from.
+ * (Added within 0.4.0: an addition only, no signature changed.) */
+int amk_attn_fwd_x6_keep(const float* q, const float* k, const float* v, float* o, float* stats, void* ws, float* scores,
+                         const uint8_t* key_mask, const uint8_t* causal_mask,
+                         int B, int H, int I, int J, int D,
+                         int64_t q_sb, int64_t q_st, int64_t q_sh,
+                         int64_t k_sb, int64_t k_st, int64_t k_sh,
+                         int64_t v_sb, int64_t v_st, int64_t v_sh,
+                         int64_t o_sb, int64_t o_st, int64_t o_sh,
+                         float scale, void* stream);
 
 /* Backward of amk_attn_fwd (autograd of the same reference lines).
  * Inputs: q,k,v,o,stats as in the forward, d_o (gradient of o, same addressing

@@ -88,6 +88,9 @@ SIGNATURES = {
     "amk_swiglu_bf16_bwd": (_I, [_P, _P, _L, _I, _P, _P]),
     "amk_add_layernorm_mixed_fwd": (_I, [_P, _I, _P, _P, _P, _L, _I, _F, _P, _P, _P, _P, _P]),
     "amk_add_layernorm_mixed_bwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _L, _I, _P, _P, _P, _P]),
+    "amk_geglu_ln_bf16_num_partials": (_I, [_L, _I]),
+    "amk_geglu_ln_bf16_fwd": (_I, [_P, _L, _L, _I, _P, _P, _F, _P, _P, _P, _P]),
+    "amk_geglu_ln_bf16_bwd": (_I, [_P, _L, _P, _P, _P, _P, _L, _I, _P, _P, _P]),
     "amk_gemm_bf16": (_I, [_I, _I, _P, _L, _P, _L, _P, _P, _L, _P, _L, _L, _I, _I, _P]),
     "amk_gemm_bf16_swiglu_bwd": (_I, [_P, _L, _P, _L, _P, _L, _P, _L, _L, _I, _I, _P]),
     "amk_gemm_tn_bf16_ws_bytes": (_L, [_L, _I, _I]),

@@ -50,6 +50,10 @@ class FeedForward(nn.Module):
                                 nn.Linear(inner, dim, bias=False))
 
     def forward(self, x):
+        lin1, _, norm, lin2 = self.ff
+        if ops.geglu_ffn_ok(x, lin1.weight, norm.gamma, norm.beta, lin2.weight):
+            # bf16 autocast: gate + LayerNorm as one kernel each way, f32 weight gradients (ops._GEGLUFFNMixed)
+            return ops.geglu_ffn(x, lin1.weight, norm.gamma, norm.beta, lin2.weight)
         return self.ff(x)
 
 

@@ -1759,6 +1759,108 @@ def swiglu_ffn(x, w12, b12, w3, b3):
     return linear(torch.nn.functional.silu(a) * b, w3, b3)
 
 
+# ---------------------------------------------------------------------------- GEGLU + LayerNorm FFN (bf16 autocast)
+# AMK_GEGLU_FFN_BF16: the transformer FFN (models/transformer.py:22-43) under bf16 autocast as one Function: both Linear
+# layers on the bf16 shadow weights with f32 weight gradients by amk_gemm_tn_bf16, and the gate + LayerNorm between them as
+# one row-wise kernel each way (csrc/geglu_ln_bf16.hip) in place of an upcast copy, the f32 gate, the f32 LayerNorm and a
+# downcast copy.  Measured at the Muse decoder's FFN (8192 rows, dim 1024, inner 4096; tools/kbench_geglu_ffn.py,
+# profiles/kbench_geglu_ffn.log): 0.79 ms against 1.28 ms forward + backward (spread 0.01 ms), 612 MB against 923 MB of peak
+# memory above the inputs; bench.py --model muse --autocast bf16 52.1 against 63.9 ms per step on the parent commit
+# (profiles/bench_muse_geglu_ffn_bf16.log).  So the switch ships on.  Read once per process.
+GEGLU_FFN_BF16 = os.environ.get("AMK_GEGLU_FFN_BF16", "1") != "0"
+
+
+def geglu_ln_bf16_fwd(ab2, gamma, beta, eps=1e-5):
+    """(y bf16 (M, H), mean, rstd f32 (M)) of LayerNorm(gate * gelu(val)) for ab2 = (val | gate), an (M, 2H) bf16 matrix
+    with unit column stride (any row stride the kernel takes)."""
+    M, H = ab2.shape[0], ab2.shape[1] // 2
+    y = torch.empty((M, H), device=ab2.device, dtype=torch.bfloat16)
+    mean = torch.empty((M,), device=ab2.device, dtype=torch.float32)
+    rstd = torch.empty_like(mean)
+    with _timed(f"geglu_ln_bf16_fwd M{M} H{H}"):
+        _lib.check(_lib.load().amk_geglu_ln_bf16_fwd(_ptr(ab2), ab2.stride(0), M, H, _ptr(gamma), _ptr(beta), float(eps),
+                                                     _ptr(y), _ptr(mean), _ptr(rstd), _stream()), "amk_geglu_ln_bf16_fwd")
+    return y, mean, rstd
+
+
+def geglu_ln_bf16_bwd(ab2, dy, gamma, mean, rstd):
+    """(d_ab bf16 (M, 2H), partial sums (parts, 2, H) f32 of dgamma / dbeta) -- the backward of geglu_ln_bf16_fwd."""
+    M, H = ab2.shape[0], ab2.shape[1] // 2
+    L = _lib.load()
+    d_ab = torch.empty((M, 2 * H), device=ab2.device, dtype=torch.bfloat16)
+    part = torch.empty((L.amk_geglu_ln_bf16_num_partials(M, H), 2, H), device=ab2.device, dtype=torch.float32)
+    with _timed(f"geglu_ln_bf16_bwd M{M} H{H}"):
+        _lib.check(L.amk_geglu_ln_bf16_bwd(_ptr(ab2), ab2.stride(0), _ptr(dy), _ptr(gamma), _ptr(mean), _ptr(rstd), M, H,
+                                           _ptr(d_ab), _ptr(part), _stream()), "amk_geglu_ln_bf16_bwd")
+    return d_ab, part
+
+
+class _GEGLUFFNMixed(torch.autograd.Function):
+    """w2(LN(gate * gelu(val))), (val | gate) = w1(x), under bf16 autocast: w1 and w2 forward and the two input gradients
+    on the library's bf16 GEMMs, gate + LayerNorm by amk_geglu_ln_bf16_fwd / _bwd, both weight gradients in f32 by
+    amk_gemm_tn_bf16.  Kept for the backward: x, (val | gate) and the LayerNorm's output in bf16, mean and rstd."""
+
+    @staticmethod
+    def forward(ctx, x, w1, gamma, beta, w2, eps):
+        x16 = x.to(torch.bfloat16).reshape(-1, x.shape[-1])
+        w1h, w2h = _w16(w1), _w16(w2)
+        gm, bt = gamma.contiguous(), beta.contiguous()
+        ab = torch.nn.functional.linear(x16, w1h)
+        y, mean, rstd = geglu_ln_bf16_fwd(ab, gm, bt, eps)
+        out = torch.nn.functional.linear(y, w2h)
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(x16, ab, y, mean, rstd, w1h, w2h, gm)
+        ctx.x_shape, ctx.x_dtype = x.shape, x.dtype
+        ctx.params = (w1, gamma, beta, w2)
+        return out.view(*x.shape[:-1], w2.shape[0])
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        from . import dense
+
+        x16, ab, y, mean, rstd, w1h, w2h, gm = ctx.saved_tensors
+        w1, gamma, beta, w2 = ctx.params
+        dy2 = dy.to(torch.bfloat16).reshape(-1, dy.shape[-1])
+        dw2, _ = _tn_into(dense.gemm_tn_bf16, dy2, y, w2, None)
+        dyn = dy2.mm(w2h)
+        d_ab, part = geglu_ln_bf16_bwd(ab, dyn, gm, mean, rstd)
+        dgamma, dbeta = _ln_param_grads(part, (gamma, beta if ctx.needs_input_grad[3] else None))
+        dw1, _ = _tn_into(dense.gemm_tn_bf16, d_ab, x16, w1, None)
+        dx = d_ab.mm(w1h).view(ctx.x_shape).to(ctx.x_dtype) if ctx.needs_input_grad[0] else None
+        return dx, dw1, dgamma, (dbeta if ctx.needs_input_grad[3] else None), dw2, None
+
+
+def geglu_ffn_ok(x, w1, gamma, beta, w2):
+    """The gate of the fused FFN: the switch and bf16 autocast are on, HIP tensors, f32 master weights that both take a
+    gradient (or nothing does), x f32 or bf16, dim and inner multiples of 8, 8 <= inner <= 4096, x not empty."""
+    if not (GEGLU_FFN_BF16 and x.is_cuda and w1.is_cuda and w2.is_cuda and _bf16_autocast()):
+        return False
+    inner, dim = w2.shape[1], w2.shape[0]
+    if not (w1.dtype == torch.float32 and w2.dtype == torch.float32 and gamma.dtype == torch.float32 and beta.dtype == torch.float32
+            and x.dtype in (torch.float32, torch.bfloat16) and tuple(w1.shape) == (2 * inner, dim) and x.shape[-1] == dim
+            and dim % 8 == 0 and inner % 8 == 0 and 8 <= inner <= 4096 and x.numel() > 0):
+        return False
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (x, w1, gamma, beta, w2)):
+        return w1.requires_grad and w2.requires_grad
+    return True
+
+
+def geglu_ffn(x, w1, gamma, beta, w2, eps=1e-5):
+    """w2(LayerNorm(gate * gelu(val)) * gamma + beta) with (val | gate) = w1(x), no biases: the transformer FFN.  Fused
+    (see _GEGLUFFNMixed) when geglu_ffn_ok, else the separate ops; on CPU tensors plain PyTorch."""
+    if geglu_ffn_ok(x, w1, gamma, beta, w2):
+        with torch.autocast("cuda", enabled=False):
+            return _GEGLUFFNMixed.apply(x, w1, gamma, beta, w2, eps)
+    ab = torch.nn.functional.linear(x, w1)
+    if ab.is_cuda and ab.shape[-1] % 8 == 0 and ab.numel() > 0:
+        g = geglu(ab)
+    else:
+        val, gate = ab.chunk(2, dim=-1)
+        g = gate * torch.nn.functional.gelu(val)
+    return torch.nn.functional.linear(layer_norm(g, gamma, beta, eps), w2)
+
+
 # ---------------------------------------------------------------------------- discriminator BatchNorm + LeakyReLU
 # AMK_DISCR_NORM: "amk" (default) = the training-mode BatchNorm2d + LeakyReLU pairs of NLayerDiscriminator run on
 # csrc/discr_norm.hip (forward, backward and the gradient penalty's double backward); "aten" = the modules as they are

@@ -604,6 +604,27 @@ int amk_add_layernorm_mixed_bwd(const void* dy, int dy_is_bf16, const float* h, 
                                 const float* mean, const float* rstd, int64_t M, int D, float* dh, void* dh_bf16,
                                 float* dgb_part, void* stream);
 
+/* ----------------------------------------------------------------------------
+ * The gate and the LayerNorm of the transformer FFN under bf16 autocast as one row-wise pass each way
+ * (models/transformer.py:22-43: Linear(dim, 2 inner) -> gate * gelu(val) -> LayerNorm(inner) -> Linear(inner, dim)).
+ *   forward : ab (M, 2H) bf16 = (val | gate) as chunk(2, -1) gives them, row stride ab_stride elements;
+ *             g = gelu(val) * gate (exact erf, f32, never rounded to bf16 and never written), two-pass mean / variance
+ *             of g, y (M, H) = (g - mean) rstd gamma + beta rounded to bf16 once; mean, rstd (M) f32; gamma, beta (H) f32.
+ *   backward: recomputes g and xhat from ab, mean, rstd; dy (M, H) bf16;
+ *             dg = rstd (dy gamma - mean_j(dy gamma) - xhat mean_j(dy gamma xhat)),
+ *             d_ab (M, 2H) contiguous = (dg gate gelu'(val) | dg gelu(val)) rounded to bf16 once;
+ *             dgb_part (amk_geglu_ln_bf16_num_partials(M, H), 2, H) f32: per-workgroup partial sums of dgamma (row 0)
+ *             and dbeta (row 1), at most 512 of them; the caller sums axis 0.  No atomics: bitwise reproducible.
+ * H a multiple of 8 with 8 <= H <= 4096, else AMK_EUNSUPPORTED.  AMK_EINVAL: a null pointer, M <= 0 or H <= 0,
+ * ab_stride not a multiple of 8 or below 2H, ab / dy / y / d_ab / gamma / beta / dgb_part off 16-byte alignment.
+ * A refused call launches nothing and writes nothing.
+ * -------------------------------------------------------------------------- */
+int amk_geglu_ln_bf16_num_partials(int64_t M, int H);
+int amk_geglu_ln_bf16_fwd(const void* ab, int64_t ab_stride, int64_t M, int H, const float* gamma, const float* beta,
+                          float eps, void* y, float* mean, float* rstd, void* stream);
+int amk_geglu_ln_bf16_bwd(const void* ab, int64_t ab_stride, const void* dy, const float* gamma, const float* mean,
+                          const float* rstd, int64_t M, int H, void* d_ab, float* dgb_part, void* stream);
+
 /* Weight and bias gradient of nn.Linear in the mixed-precision mode (csrc/gemm_bf16.hip): c[n, k] = sum_m y[m, n] x[m, k]
  * with y (M, N) and x (M, K) in bf16 as the autocast GEMMs leave them, c (N, K) and dbias (N, optional: column sums of y)
  * in f32 as the parameters' gradients are kept.  Replaces the autograd backward of nn.Linear under torch.autocast

@@ -17,7 +17,7 @@
 //   V tile [64 keys][64 d] bf16 in LDS AS STORED, row stride 192 B: the A fragments of V^T (8 keys of one head
 //   dim, in the key order of a packed accumulator) come from ds_read_b64_tr_b16, the hardware transposing read
 //   (4 rows x 16 columns per 16 lanes; 4 rows x 64 B per half-wave land on 64 distinct banks at this stride).
-// Backward: one pass with the key on the lane (as attn_bwd_fused.hip): a workgroup = 8 waves x 32 keys; K and V
+// Backward: one pass with the key on the lane (as attn_bwd_fused.hip at head dim 64): a workgroup = 8 waves x 32 keys; K and V
 // fragments of the wave's keys in registers, dK^T / dV^T in accumulators; per 32-query tile S = Q K^T and
 // dP = dO V^T (A = rows of Q / dO from LDS), P and dS in registers, dV^T += dO^T P and dK^T += Q^T dS with the
 // packed accumulators as B operands and transposing reads of the dO / Q tiles as A operands; dS crosses LDS once

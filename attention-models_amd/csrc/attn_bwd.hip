@@ -13,7 +13,7 @@
 //     attn_bwd_dkdv  : KEY ON THE LANE (a wave owns 32 keys, k / v live in registers)
 //          S  = Q K^T,  dP = dO V^T         (A = q / dO rows from LDS, B = k / v registers)
 //          dV^T += dO^T P,  dK^T += Q^T dS  (A = dO / q columns from LDS, B = accumulators)
-//   the one-pass kernels of attn_bwd_fused.hip (head dim 64) and attn_bwd_fused_gen.hip (32 / 128), after delta
+//   the one-pass kernel of attn_bwd_fused.hip (head dims 32, 64, 128), after delta
 //
 // Gradients do not flow through positions the forward filled with -1e9 (masked_fill).
 #include "attn_generic.h"
@@ -75,10 +75,10 @@ static int attn_bwd_impl(const float* scores, const float* q, const float* k, co
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (stages & AMK_ATTN_BWD_DELTA) launch_attn_bwd_gen(p, Dh, AMK_ATTN_BWD_DELTA, st);
   if (stages & AMK_ATTN_BWD_FUSED) {
-    // the one-pass kernel of this head dim (64: attn_bwd_fused.hip; 32 / 128: attn_bwd_fused_gen.hip; the others have
-    // none) when the layout allows it, else the two recompute kernels
+    // the one-pass kernel of this head dim (attn_bwd_fused.hip: 32, 64, 128; the others have none) when the layout
+    // allows it, else the two recompute kernels
     const int keys = (stages & AMK_ATTN_BWD_KEYS256) ? 256 : ((stages & AMK_ATTN_BWD_KEYS128) ? 128 : 0);
-    const bool ran = Dh == D ? launch_attn_bwd_fused(p, keys, st) : launch_attn_bwd_fused_gen(p, Dh, st);
+    const bool ran = launch_attn_bwd_fused(p, Dh, keys, st);
     AMK_CHECK_SUPPORTED(ran || Dh == D || !scores,
                         "amk_attn_bwd_kept: the one-pass kernel could not run (dq layout) and the recompute kernels do not read kept scores");
     stages = ran ? 0 : (AMK_ATTN_BWD_DKDV | AMK_ATTN_BWD_DQ);

@@ -1,4 +1,4 @@
-// Fused softmax-attention backward for gfx950: ONE pass, dQ by f32 atomics.
+// Fused softmax-attention backward for gfx950 (head dims 32, 64, 128): ONE pass, dQ by f32 atomics.
 //
 // The two-kernel backward of attn_bwd.hip recomputes S twice and dP twice (7 products, bitwise
 // reproducible, no atomics).  This kernel computes each product once (cdna guide, Appendix B
@@ -13,16 +13,27 @@
 //   P, dS                       key on the lane: fills are per-lane constants, row stats from LDS
 //   dV^T += dO^T P, dK^T += Q^T dS   A = dO / q columns from LDS, B = the accumulators as they stand
 //   dS -> LDS ([query][key], all keys of the workgroup), one barrier, then
-//   dQ tile (32 x 64) = dS (32 x 32NW) K (32NW x 64) with v_mfma_f32_16x16x4_f32: every wave owns 8/NW
+//   dQ tile (32 x DH) = dS (32 x 32NW) K (32NW x DH) with v_mfma_f32_16x16x4_f32: every wave owns its share of the
 //        16x16 output blocks over ALL keys of the workgroup, so no cross-wave reduction; the result is added
-//        to dq with global_atomic_add_f32 (dq is zeroed by the launcher).  Atomic volume is
+//        to dq with global_atomic_add_f32 (dq is zeroed by the launcher).  Atomic volume at head dim 64 is
 //        8 KiB per (32 query x 32NW key) tile: every dq element receives J / (32 NW) adds.
 // Two workgroup barriers per query tile (the next q / dO tile is committed under the dQ product);
 // workgroups start at rotated query tiles so that co-resident ones are not in the same phase.
 // Results differ from run to run in the last bits of dq only (f32 atomic arrival order); dk, dv are
 // reproducible.  The two-kernel path stays available (AMK_ATTN_BWD_DKDV | AMK_ATTN_BWD_DQ).
+//
+// One kernel template over the head dim; what a head dim has of its own is an FGeom constant:
+//   DH = 64 : NW = 4 (128 keys per workgroup, two workgroups per CU) or 8 (256 keys; half the dq adds), and the
+//             reproducible-dq form (DQ = 1);
+//   DH = 32 : NW = 8 and query tiles of 64 (QS = 2 sub-tiles of 32 per barrier pair): the 64 x 32 dQ tile is eight
+//             16 x 16 blocks, one per wave;
+//   DH = 128: NW = 4 at ONE wave per SIMD with the 512-register file: eight 32 x 32 accumulators for dK^T / dV^T alone
+//             are 128 registers; the 32 x 128 dQ tile is sixteen blocks, four per wave.
+// The other head dims run the two recompute kernels of attn_generic.h (7 matrix products for the 4 or 5 here), and so
+// do 32 / 128 under AMK_DETERMINISTIC: the reproducible-dq form exists for head dim 64 only.
 #include "attn_common.h"
 #include <stdlib.h>
+#include <type_traits>
 
 // diagnostic builds only (tools/ablate_attn_bwd.sh): AMK_BWD_ABL bits switch parts of the tile loop off -- WRONG results,
 // timing only: 1 no dq atomics / stores, 2 no dQ product, 4 no dS LDS writes, 8 no P / dS arithmetic, 16 no kept-score
@@ -33,17 +44,56 @@
 
 namespace amk_attn {
 
-constexpr int TQ = 32;             // queries per tile
+// RowStagerT's interface without its per-thread state: every offset is recomputed at the load (a 64-bit multiply and a
+// compare per 16 B).  Head dim 128 stages q / dO with it: its kernels sit at the register limit, and RowStagerT's eight
+// running offsets cost the recomputing causal variant 0.4 % (0.766 -> 0.769 ms at B*H = 64, T = 1024); at head dim 32 this
+// form costs the kept-scores causal variant 1.8 %, so 32 and 64 keep the running offsets.
+template <int ROWS, int NT, int DH>
+struct RowRestagerT {
+  static constexpr int F4R = DH / 4, RP = NT / F4R, NP = ROWS / RP;
+  __amdgpu_buffer_rsrc_t rsrc;
+  int64_t st;
+  int nrows, row0, tid;
+  __device__ __forceinline__ void init(const float* base, int64_t row_stride, int nrows_, int tid_) {
+    rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)(((int64_t)(nrows_ - 1) * row_stride + DH) * 4), 0x00020000);
+    st = row_stride; nrows = nrows_; row0 = 0; tid = tid_;
+  }
+  __device__ __forceinline__ void seek(int blk, int64_t, int) { row0 = blk * ROWS; }
+  __device__ __forceinline__ float4 piece(int ps) const {   // rows past the sequence: an offset past the range, zeros
+    const int r = row0 + tid / F4R + RP * ps;
+    const unsigned off = r < nrows ? (unsigned)(((int64_t)r * st + (tid % F4R) * 4) * 4) : 0x80000000u;
+    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)off, 0, 0));
+  }
+};
 
-template <int NW>
-struct FusedGeom {
+// QS: 32-query sub-tiles per query tile (one barrier pair and one q / dO staging pass per TILE).  Head dim 32 uses 2: its
+// sub-tile carries half the MFMA work of head dim 64 over the same softmax arithmetic, LDS round trip and barriers, its
+// staging pass covers 64 rows anyway (512 threads x 16 B), and with 64 queries the dQ tile is one 16 x 16 block per wave.
+template <int DH, int NW, int QS>
+struct FGeom {
+  static constexpr int TQ = 32 * QS;          // queries per tile
   static constexpr int NT = 64 * NW;          // threads
   static constexpr int KB = 32 * NW;          // keys per workgroup
+  static constexpr int HD = DH / 2;           // k-extent owned by one half-wave
+  static constexpr int LS = DH + 4;           // LDS row stride of the q / dO / K images (LDS_STRIDE at head dim 64)
+  static constexpr int NTILE = DH / 32;       // 32-wide dim tiles of dK^T / dV^T
   static constexpr int DS_STRIDE = KB + 4;    // dS tile row stride (floats): 16-B aligned rows, b128 row reads
-  static constexpr int LDS_FLOATS = 2 * TQ * LDS_STRIDE + KB * LDS_STRIDE + TQ * DS_STRIDE + 4 * TQ;
-  static constexpr int NBLK = 8 / NW;         // 16x16 dQ blocks per wave
+  static constexpr int LDS_FLOATS = 2 * TQ * LS + KB * LS + TQ * DS_STRIDE + 4 * TQ;
   static constexpr int KPG = KB / 4;          // keys per k-group of the 16x16x4 product
+  static constexpr int NQB = 2 * QS;          // 16-query row blocks of the dQ tile
+  static constexpr int CBW = (DH / 16) * NQB / NW;   // 16-wide column blocks of the dQ tile per wave
+  static_assert(CBW * NW == (DH / 16) * NQB, "every wave owns whole dQ blocks over all keys of the workgroup");
+  // independent accumulator chains per dQ block: head dim 64 at 8 waves splits its one block into even / odd k-steps
+  static constexpr int DQ_CHAINS = (DH == 64 && CBW == 1) ? 2 : 1;
+  static constexpr int MIN_WG = DH >= 128 ? 1 : 2;    // workgroups per CU the register budget is set for
+  // MFMA issue order within a query column: all of dV then all of dK (head dim 64), or dV / dK alternating per 32-wide
+  // dim tile (head dim 128: 0.4 % of the kernel, measured; head dim 32 has one tile)
+  static constexpr bool DV_FIRST = DH == 64;
+  using QStager = std::conditional_t<DH >= 128, RowRestagerT<TQ, NT, DH>, RowStagerT<TQ, NT, DH>>;   // a q / dO tile
+  using KStager = RowStagerT<KB / 2, NT, DH>;         // the K block, in two halves
 };
+static_assert(FGeom<64, 4, 1>::LS == LDS_STRIDE && FGeom<64, 4, 1>::LDS_FLOATS == 2 * 32 * 68 + 128 * 68 + 32 * 132 + 4 * 32 &&
+              FGeom<64, 8, 1>::LDS_FLOATS == 2 * 32 * 68 + 256 * 68 + 32 * 260 + 4 * 32, "head dim 64 keeps its LDS images");
 
 __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
   // D(16x16) += A(16x4) B(4x16): lane l supplies A[l & 15][l >> 4], B[l >> 4][l & 15];
@@ -54,18 +104,18 @@ __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
 // DQ: 0 = f32 atomic adds into a zeroed dq (fastest; dq differs in the last bits from run to run);
 //     1 = plain stores -- of dq itself when the workgroup holds every key of its (batch, head) (J <= 32 NW: no
 //         atomics, no memset), else of this key block's partial into p.dq_part[kb], summed in key-block order
-//         by attn_bwd_dq_reduce_kernel: bitwise reproducible.
+//         by attn_bwd_dq_reduce_kernel: bitwise reproducible.  Instantiated for head dim 64 only.
 // CAUSAL: p.causal_mask, an (I, J) byte mask shared by batch and heads (models/softmax_attention.py:62-66): a non-zero
 // byte puts the fill value in place of the score (its dS is 0, its P still feeds dV), as the forward does
-template <int NW, bool KEPT, int DQ, bool CAUSAL>
-__global__ __launch_bounds__(64 * NW, 2) void attn_bwd_fused_kernel(BwdParams p) {
-  using G = FusedGeom<NW>;
-  constexpr int NT = G::NT, KB = G::KB, DS_STRIDE = G::DS_STRIDE, KPG = G::KPG;
+template <int DH, int NW, int QS, bool KEPT, int DQ, bool CAUSAL>
+__global__ __launch_bounds__(64 * NW, (FGeom<DH, NW, QS>::MIN_WG)) void attn_bwd_fused_kernel(BwdParams p) {
+  using G = FGeom<DH, NW, QS>;
+  constexpr int TQ = G::TQ, KB = G::KB, HD = G::HD, LS = G::LS, NTILE = G::NTILE, DS_STRIDE = G::DS_STRIDE, KPG = G::KPG;
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* Qs = smem;                           // [TQ][LDS_STRIDE]  (q * scale * log2 e)
-  float* Gs = Qs + TQ * LDS_STRIDE;           // [TQ][LDS_STRIDE]  dO
-  float* Kc = Gs + TQ * LDS_STRIDE;           // [KB][LDS_STRIDE]  this workgroup's K rows
-  float* dSl = Kc + KB * LDS_STRIDE;          // [TQ][DS_STRIDE]   dS of the current tile
+  float* Qs = smem;                           // [TQ][LS]  (q * scale * log2 e)
+  float* Gs = Qs + TQ * LS;                   // [TQ][LS]  dO
+  float* Kc = Gs + TQ * LS;                   // [KB][LS]  this workgroup's K rows
+  float* dSl = Kc + KB * LS;                  // [TQ][DS_STRIDE]   dS of the current tile
   float* Ms = dSl + TQ * DS_STRIDE;
   float* Ls = Ms + TQ;
   float* Ds = Ls + TQ;    // MINUS delta: the initial accumulator of the dP chain (dP - delta leaves the matrix pipe)
@@ -88,11 +138,11 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_bwd_fused_kernel(BwdParams p)
   const float* vbase = p.v + (int64_t)b * p.vs.sb + (int64_t)h * p.vs.sh;
 
   // B operand held for the whole kernel: v of this lane's key (k comes from the K block in LDS).
-  float vreg[32];
+  float vreg[HD];
   {
-    const float* vp = vbase + (int64_t)kj * p.vs.st + 32 * hf;
+    const float* vp = vbase + (int64_t)kj * p.vs.st + HD * hf;
 #pragma unroll
-    for (int s4 = 0; s4 < 8; ++s4) {
+    for (int s4 = 0; s4 < HD / 4; ++s4) {
       const float4 c = kvalid ? ld4(vp + 4 * s4) : make_float4(0.f, 0.f, 0.f, 0.f);
       vreg[4 * s4 + 0] = c.x; vreg[4 * s4 + 1] = c.y; vreg[4 * s4 + 2] = c.z; vreg[4 * s4 + 3] = c.w;
     }
@@ -101,26 +151,31 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_bwd_fused_kernel(BwdParams p)
   if (!kvalid) kfill = -INFINITY;
   else if (p.key_mask && p.key_mask[(int64_t)b * p.J + kj] == 0) kfill = AMK_FILL_MASKED;
   const bool plain = !CAUSAL && __all(kfill == 0.f);  // wave-uniform: none of this wave's scores is filled
-  // CAUSAL: this lane's key column of the mask, one byte per query row of its 16 registers; the bytes of the coming
+  // CAUSAL: this lane's key column of the mask, one byte per query row of its 16 registers per sub-tile; the bytes of the coming
   // tile are requested a tile ahead (unconditional loads at clamped rows: no branch around memory instructions)
   const uint8_t* cm_col = CAUSAL ? p.causal_mask + min(kj, p.J - 1) : nullptr;
-  unsigned cm_raw[16];
+  unsigned cm_raw[QS][16];
   auto load_cmask = [&](int i0) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) cm_raw[r] = cm_col[(int64_t)min(i0 + acc_row(r, hf), p.I - 1) * p.J];
+    for (int u = 0; u < QS; ++u)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) cm_raw[u][r] = cm_col[(int64_t)min(i0 + 32 * u + acc_row(r, hf), p.I - 1) * p.J];
   };
 
   // K rows of the whole workgroup -> LDS once (B operand of the dQ product, and of S when it is recomputed)
+  using KStager = typename G::KStager;
+  using QStager = typename G::QStager;
+  const int srow = (unsigned)tid / QStager::F4R, scol = ((unsigned)tid % QStager::F4R) * 4;   // this thread's 16 B of a staging pass
   {
-    RowStagerT<KB / 2, NT> kl;  // two passes of KB/2 rows, 4 x 16 B per thread each
+    KStager kl;  // two halves of KB/2 rows, KStager::NP x 16 B per thread each
     const float* kblk = kbase + (int64_t)kb * KB * p.ks.st;
     kl.init(kblk, p.ks.st, min(KB, p.J - kb * KB), tid);
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
-      float4 t[4];
+      float4 t[KStager::NP];
       kl.load(t);
 #pragma unroll
-      for (int ps = 0; ps < 4; ++ps) st4(&Kc[((KB / 2) * half + (tid >> 4) + (NT / 16) * ps) * LDS_STRIDE + (tid & 15) * 4], t[ps]);
+      for (int ps = 0; ps < KStager::NP; ++ps) st4(&Kc[((KB / 2) * half + srow + KStager::RP * ps) * LS + scol], t[ps]);
     }
   }
 
@@ -128,12 +183,12 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_bwd_fused_kernel(BwdParams p)
   const float* gbase = p.d_o + (int64_t)b * p.dos.sb + (int64_t)h * p.dos.sh;
   const float* stbase = p.stats + ((int64_t)b * p.H + h) * p.I * 2;
   const float* dlbase = p.delta + ((int64_t)b * p.H + h) * p.I;
-  float* dqbase = (DQ == 1 && p.nkblk > 1 ? p.dq_part + (int64_t)kb * p.B * p.I * p.H * D : p.dq) +
+  float* dqbase = (DQ == 1 && p.nkblk > 1 ? p.dq_part + (int64_t)kb * p.B * p.I * p.H * DH : p.dq) +
                   (int64_t)b * p.dqs.sb + (int64_t)h * p.dqs.sh;
   // dq rows of this (batch, head) through a buffer descriptor: adds to rows beyond the sequence are
   // dropped by the hardware range check, so the atomics need no branch either
   const __amdgpu_buffer_rsrc_t dq_rsrc =
-      __builtin_amdgcn_make_buffer_rsrc((void*)dqbase, 0, (int)(((int64_t)(p.I - 1) * p.dqs.st + 64) * 4), 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc((void*)dqbase, 0, (int)(((int64_t)(p.I - 1) * p.dqs.st + DH) * 4), 0x00020000);
 
   // kept scores: this wave's 32 keys x all query tiles are nqt consecutive 4-KiB tiles; a buffer
   // descriptor of zero records (key block beyond the forward's tiles) reads zeros
@@ -146,17 +201,18 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_bwd_fused_kernel(BwdParams p)
     sc_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)tiles, 0, kb32 < stl.nkb ? stl.nqt * 4096 : 0, 0x00020000);
     sc_voff = ln * 128 + hf * 16;  // row = this lane's key, 4 queries of register group g at +32 g bytes
   }
-  float4 sk[4];  // KEPT: the score registers of the coming tile (16 queries of this lane's key)
-  auto load_scores = [&](int qt) {
+  float4 sk[QS][4];  // KEPT: the score registers of the coming tile (16 queries of this lane's key per sub-tile)
+  auto load_scores = [&](int qt) {   // qt: query TILE; its sub-tiles are consecutive 4-KiB score tiles
 #pragma unroll
-    for (int g = 0; g < 4; ++g)
-      sk[g] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(sc_rsrc, sc_voff + qt * 4096 + 32 * g, 0, 2));
+    for (int u = 0; u < QS; ++u)
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+        sk[u][g] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(sc_rsrc, sc_voff + (qt * QS + u) * 4096 + 32 * g, 0, 2));
   };
 
-  constexpr int QNP = RowStagerT<TQ, NT>::NP;  // 16-B pieces per thread of a 32-row tile (2 or 1)
-  const int srow = tid >> 4, scol = (tid & 15) * 4;
+  constexpr int QNP = QStager::NP;  // 16-B pieces per thread of a query tile
   float4 qst[QNP], gst[QNP];
-  RowStagerT<TQ, NT> qload, gload;
+  QStager qload, gload;
   qload.init(qbase, p.qs.st, p.I, tid);
   gload.init(gbase, p.dos.st, p.I, tid);
   // No branch around any vector-memory instruction of the tile loop: the compiler can then count, at
@@ -165,10 +221,17 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_bwd_fused_kernel(BwdParams p)
   float2 ml_raw = make_float2(0.f, 1.f);
   float dl_raw = 0.f;
   bool row_ok = false;
-  auto prefetch = [&](int i0) {  // loads only: whatever consumes them waits in commit(), a tile later
-    qload.load(qst);
-    gload.load(gst);
-    const int i = i0 + (tid & (TQ - 1));
+  auto prefetch = [&](int qt) {  // query tile qt; loads only: whatever consumes them waits in commit(), a tile later
+    qload.seek(qt, p.qs.st, tid);
+    gload.seek(qt, p.dos.st, tid);
+    if constexpr (DH >= 128) {
+#pragma unroll
+      for (int ps = 0; ps < QNP; ++ps) { qst[ps] = qload.piece(ps); gst[ps] = gload.piece(ps); }
+    } else {
+      qload.load(qst);
+      gload.load(gst);
+    }
+    const int i = qt * TQ + (tid & (TQ - 1));
     const int ic = min(i, p.I - 1);
     ml_raw = *reinterpret_cast<const float2*>(stbase + 2 * ic);
     dl_raw = dlbase[ic];
@@ -181,9 +244,9 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_bwd_fused_kernel(BwdParams p)
     const float sc = p.scale * AMK_LOG2E;  // S comes out in the log2 domain; dK is scaled back by ln 2
 #pragma unroll
     for (int ps = 0; ps < QNP; ++ps) {
-      const int r = srow + (NT / 16) * ps;
-      st4(&Qs[r * LDS_STRIDE + scol], make_float4(qst[ps].x * sc, qst[ps].y * sc, qst[ps].z * sc, qst[ps].w * sc));
-      st4(&Gs[r * LDS_STRIDE + scol], gst[ps]);
+      const int r = srow + QStager::RP * ps;
+      st4(&Qs[r * LS + scol], make_float4(qst[ps].x * sc, qst[ps].y * sc, qst[ps].z * sc, qst[ps].w * sc));
+      st4(&Gs[r * LS + scol], gst[ps]);
     }
     // rows beyond the sequence: P = exp2(x - inf) * 0 = 0
     if (tid < TQ) {  // LDS stores only
@@ -195,14 +258,16 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_bwd_fused_kernel(BwdParams p)
     __builtin_amdgcn_sched_barrier(0);
   };
 
-  f32x16 dk0 = zero16(), dk1 = zero16(), dv0 = zero16(), dv1 = zero16();
+  f32x16 dk[NTILE], dv[NTILE];
+#pragma unroll
+  for (int n = 0; n < NTILE; ++n) { dk[n] = zero16(); dv[n] = zero16(); }
 
   // dQ product geometry: 16x16x4 MFMA, lane = (column c = l & 15, k-group kg = l >> 4)
   const int c16 = lane & 15, kg = lane >> 4;
-  const int qhalf = wave & 1;                          // which 16 of the tile's 32 queries
-  const int dcol0 = (16 * G::NBLK) * (wave >> 1);      // this wave's output columns (NBLK 16-wide blocks)
+  const int qhalf = (unsigned)wave % G::NQB;                     // which 16 of the tile's queries
+  const int dcol0 = (16 * G::CBW) * ((unsigned)wave / G::NQB);   // this wave's output columns (CBW 16-wide blocks)
   const float* ds_row = &dSl[(16 * qhalf + c16) * DS_STRIDE + KPG * kg];  // A: dS[query][KPG*kg + s]
-  const float* kc_col = &Kc[(KPG * kg) * LDS_STRIDE + dcol0 + c16];       // B: K[KPG*kg + s][dcol]
+  const float* kc_col = &Kc[(KPG * kg) * LS + dcol0 + c16];               // B: K[KPG*kg + s][dcol]
 
   const int ntile = (p.I + TQ - 1) / TQ;
   // Two barriers per query tile.  After the dS barrier every wave is past the phases that read the
@@ -216,153 +281,151 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_bwd_fused_kernel(BwdParams p)
   // against a start tile per workgroup.
   const int rot = (int)(((unsigned)bh * 5u) % (unsigned)ntile);
   auto tile_of = [&](int t) { const int x = t + rot; return x >= ntile ? x - ntile : x; };
-  qload.seek(rot, p.qs.st, tid);
-  gload.seek(rot, p.dos.st, tid);
-  prefetch(rot * TQ);
+  prefetch(rot);
   if (KEPT) load_scores(rot);
   if (CAUSAL) load_cmask(rot * TQ);
   __syncthreads();  // the K block is in LDS
   commit();
   __syncthreads();
-  {
-    const int nx = tile_of(min(1, ntile - 1));
-    qload.seek(nx, p.qs.st, tid);
-    gload.seek(nx, p.dos.st, tid);
-    prefetch(nx * TQ);
-  }
+  prefetch(tile_of(min(1, ntile - 1)));
   // Enter the loop with nothing in flight: the waits inside are then the back edge's counted ones
   // (one memory latency per workgroup here; vmcnt(0) with expcnt / lgkmcnt left alone).
   __builtin_amdgcn_s_waitcnt(0x0F70);
   for (int t = 0; t < ntile; ++t) {
     const int i0 = tile_of(t) * TQ;
 
-    // ---- S and dP for the tile's 32 queries x this wave's 32 keys
+    // ---- per 32-query sub-tile u: S and dP for its queries x this wave's 32 keys
+    // (a do-while: behind the entry test of a `for`, even one that folds away, the causal variants of head dim 64
+    // come out 4 to 15 VGPRs larger and spill)
     // dP's chain starts from -delta of the register's query row: the subtraction of softmax's backward costs no VALU
-    f32x16 s = zero16(), dp;
+    int u = 0;
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const float4 d4 = ld4(&Ds[8 * g + 4 * hf]);
-      dp[4 * g + 0] = d4.x; dp[4 * g + 1] = d4.y; dp[4 * g + 2] = d4.z; dp[4 * g + 3] = d4.w;
-    }
-    {
-      const float* qr = &Qs[ln * LDS_STRIDE + 32 * hf];
-      const float* gr = &Gs[ln * LDS_STRIDE + 32 * hf];
-      const float* kr = &Kc[(32 * wave + ln) * LDS_STRIDE + 32 * hf];  // this lane's key row
+    do {
+      f32x16 s = zero16(), dp;
 #pragma unroll
-      for (int s4 = 0; s4 < 8; ++s4) {
-        const float4 c = ld4(gr + 4 * s4);
-        if (!KEPT) {
-          const float4 a = ld4(qr + 4 * s4);
-          const float4 kk = ld4(kr + 4 * s4);
+      for (int g = 0; g < 4; ++g) {
+        const float4 d4 = ld4(&Ds[32 * u + 8 * g + 4 * hf]);
+        dp[4 * g + 0] = d4.x; dp[4 * g + 1] = d4.y; dp[4 * g + 2] = d4.z; dp[4 * g + 3] = d4.w;
+      }
+      {
+        const float* qr = &Qs[(32 * u + ln) * LS + HD * hf];
+        const float* gr = &Gs[(32 * u + ln) * LS + HD * hf];
+        const float* kr = &Kc[(32 * wave + ln) * LS + HD * hf];  // this lane's key row
+#pragma unroll
+        for (int s4 = 0; s4 < HD / 4; ++s4) {
+          const float4 c = ld4(gr + 4 * s4);
+          if (!KEPT) {
+            const float4 a = ld4(qr + 4 * s4);
+            const float4 kk = ld4(kr + 4 * s4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              s = mfma32(f4(a, e), f4(kk, e), s);
+              dp = mfma32(f4(c, e), vreg[4 * s4 + e], dp);
+            }
+          } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) dp = mfma32(f4(c, e), vreg[4 * s4 + e], dp);
+          }
+        }
+      }
+      if (KEPT && !(AMK_BWD_ABL & 16)) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          s[4 * g + 0] = sk[u][g].x; s[4 * g + 1] = sk[u][g].y; s[4 * g + 2] = sk[u][g].z; s[4 * g + 3] = sk[u][g].w;
+        }
+      }
+      // ---- P and dS (register r of this lane is query 32 u + acc_row(r, hf))
+      if (AMK_BWD_ABL & 8) {
+      } else if (plain) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          // (no fill in this wave's columns, so every row has a live key here and m is a genuine score maximum: the
+          // normaliser folds into the exponent, P = exp2(S - (m + log2 l)); the two-constant form below is for rows whose
+          // m may be the fill value, where m + log2 l would swallow l)
+          const float4 ml4 = ld4(&MLs[32 * u + 8 * g + 4 * hf]);
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            s = mfma32(f4(a, e), f4(kk, e), s);
-            dp = mfma32(f4(c, e), vreg[4 * s4 + e], dp);
+            const int r = 4 * g + e;
+            const float pr = __builtin_amdgcn_exp2f(s[r] - f4(ml4, e));
+            s[r] = pr;
+            dp[r] = pr * dp[r];
           }
-        } else {
+        }
+      } else {
+        unsigned cbits = 0xffffu;   // bit r: the score of register r is kept
+        if (CAUSAL) {
+          cbits = 0;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) dp = mfma32(f4(c, e), vreg[4 * s4 + e], dp);
+          for (int r = 0; r < 16; ++r) cbits |= (cm_raw[u][r] == 0 ? 1u : 0u) << r;   // (a non-zero byte masks)
+        }
+        const float fillv = kfill != 0.f ? kfill : AMK_FILL_MASKED;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const float4 m4 = ld4(&Ms[32 * u + 8 * g + 4 * hf]);
+          const float4 l4 = ld4(&Ls[32 * u + 8 * g + 4 * hf]);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int r = 4 * g + e;
+            const bool filled = kfill != 0.f || !((cbits >> r) & 1u);
+            const float tt = filled ? fillv : s[r];
+            const float pr = __builtin_amdgcn_exp2f(tt - f4(m4, e)) * f4(l4, e);
+            s[r] = pr;
+            dp[r] = filled ? 0.f : pr * dp[r];
+          }
         }
       }
-    }
-    if (KEPT && !(AMK_BWD_ABL & 16)) {
+      // ---- dS -> LDS as [query][key] for the workgroup-wide dQ product
+      if (!(AMK_BWD_ABL & 4)) {
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        s[4 * g + 0] = sk[g].x; s[4 * g + 1] = sk[g].y; s[4 * g + 2] = sk[g].z; s[4 * g + 3] = sk[g].w;
+        for (int r = 0; r < 16; ++r) dSl[(32 * u + acc_row(r, hf)) * DS_STRIDE + 32 * wave + ln] = dp[r];
       }
-    }
-    // ---- P and dS (register r of this lane is query acc_row(r, hf))
-    if (AMK_BWD_ABL & 8) {
-    } else if (plain) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        // (no fill in this wave's columns, so every row has a live key here and m is a genuine score maximum: the
-        // normaliser folds into the exponent, P = exp2(S - (m + log2 l)); the two-constant form below is for rows whose
-        // m may be the fill value, where m + log2 l would swallow l)
-        const float4 ml4 = ld4(&MLs[8 * g + 4 * hf]);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int r = 4 * g + e;
-          const float pr = __builtin_amdgcn_exp2f(s[r] - f4(ml4, e));
-          s[r] = pr;
-          dp[r] = pr * dp[r];
-        }
-      }
-    } else {
-      unsigned cbits = 0xffffu;   // bit r: the score of register r is kept
-      if (CAUSAL) {
-        cbits = 0;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) cbits |= (cm_raw[r] == 0 ? 1u : 0u) << r;   // (a non-zero byte masks)
-      }
-      const float fillv = kfill != 0.f ? kfill : AMK_FILL_MASKED;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const float4 m4 = ld4(&Ms[8 * g + 4 * hf]);
-        const float4 l4 = ld4(&Ls[8 * g + 4 * hf]);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int r = 4 * g + e;
-          const bool filled = kfill != 0.f || !((cbits >> r) & 1u);
-          const float tt = filled ? fillv : s[r];
-          const float pr = __builtin_amdgcn_exp2f(tt - f4(m4, e)) * f4(l4, e);
-          s[r] = pr;
-          dp[r] = filled ? 0.f : pr * dp[r];
-        }
-      }
-    }
-    // ---- dS -> LDS as [query][key] for the workgroup-wide dQ product
-    if (!(AMK_BWD_ABL & 4)) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dSl[acc_row(r, hf) * DS_STRIDE + 32 * wave + ln] = dp[r];
-    }
 
-    // the next tile's scores (consumed after the next tile's dP product: three MFMA phases from here;
-    // the last iteration re-reads its own tile, unused)
-    if (KEPT && !(AMK_BWD_ABL & 16)) {
-      load_scores(tile_of(min(t + 1, ntile - 1)));
-      __builtin_amdgcn_sched_barrier(0);  // issued HERE: the compiler otherwise sinks them below the MFMAs
-    }
-    if (CAUSAL) load_cmask(tile_of(min(t + 1, ntile - 1)) * TQ);
+      // the next tile's scores / mask bytes, ahead of the last sub-tile's dV / dK products (consumed after the next
+      // tile's dP product: three MFMA phases from here; the last iteration re-reads its own tile, unused)
+      if (u == QS - 1) {
+        if (KEPT && !(AMK_BWD_ABL & 16)) {
+          load_scores(tile_of(min(t + 1, ntile - 1)));
+          __builtin_amdgcn_sched_barrier(0);  // issued HERE: the compiler otherwise sinks them below the MFMAs
+        }
+        if (CAUSAL) load_cmask(tile_of(min(t + 1, ntile - 1)) * TQ);
+      }
 
-    // ---- dV^T += dO^T P ; dK^T += (q*scale*log2e)^T dS   (2 x 32 MFMAs)
+      // ---- dV^T += dO^T P ; dK^T += (q*scale*log2e)^T dS   (2 x 16 NTILE MFMAs)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float* gc = &Gs[acc_row((AMK_BWD_ABL & 32) ? 0 : r, hf) * LDS_STRIDE + ln];
-      const float* qc = &Qs[acc_row((AMK_BWD_ABL & 32) ? 0 : r, hf) * LDS_STRIDE + ln];
-      dv0 = mfma32(gc[0], s[r], dv0);
-      dv1 = mfma32(gc[32], s[r], dv1);
-      dk0 = mfma32(qc[0], dp[r], dk0);
-      dk1 = mfma32(qc[32], dp[r], dk1);
-    }
+      for (int r = 0; r < 16; ++r) {
+        const float* gc = &Gs[(32 * u + acc_row((AMK_BWD_ABL & 32) ? 0 : r, hf)) * LS + ln];
+        const float* qc = &Qs[(32 * u + acc_row((AMK_BWD_ABL & 32) ? 0 : r, hf)) * LS + ln];
+#pragma unroll
+        for (int n = 0; n < NTILE; ++n) {
+          dv[n] = mfma32(gc[32 * n], s[r], dv[n]);
+          if (!G::DV_FIRST) dk[n] = mfma32(qc[32 * n], dp[r], dk[n]);
+        }
+#pragma unroll
+        for (int n = 0; n < (G::DV_FIRST ? NTILE : 0); ++n) dk[n] = mfma32(qc[32 * n], dp[r], dk[n]);
+      }
+    } while (++u < QS);
     __syncthreads();  // every wave's dS columns are in LDS; the q / dO / stats tiles are dead
     if (!(AMK_BWD_ABL & 64)) {
-    commit();         // (the last iteration commits a tile nobody reads)
-    {
-      const int nx = tile_of(min(t + 2, ntile - 1));
-      qload.seek(nx, p.qs.st, tid);
-      gload.seek(nx, p.dos.st, tid);
-      prefetch(nx * TQ);
-    }
+      commit();         // (the last iteration commits a tile nobody reads)
+      prefetch(tile_of(min(t + 2, ntile - 1)));
     }
 
-    // ---- dQ (16 queries x 16*NBLK columns per wave) = dS (16 x KB) K (KB x 16*NBLK): 64 MFMAs 16x16x4,
-    //      two independent accumulator chains either way (two blocks, or even / odd k-steps of one)
-    f32x4 q0 = {0.f, 0.f, 0.f, 0.f}, q1 = {0.f, 0.f, 0.f, 0.f};
+    // ---- dQ (16 queries x 16*CBW columns per wave) = dS (16 x KB) K (KB x 16*CBW): 16x16x4 MFMAs, one accumulator
+    //      chain per block, or DQ_CHAINS = 2: even / odd k-steps of the one block
+    f32x4 qa[G::CBW][G::DQ_CHAINS];
+#pragma unroll
+    for (int cbk = 0; cbk < G::CBW; ++cbk)
+#pragma unroll
+      for (int ch = 0; ch < G::DQ_CHAINS; ++ch) qa[cbk][ch] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int s4 = 0; s4 < ((AMK_BWD_ABL & 2) ? 0 : KPG / 4); ++s4) {
       const float4 a = ld4(ds_row + 4 * s4);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float* kc = kc_col + (4 * s4 + e) * LDS_STRIDE;
-        if (G::NBLK == 2) {
-          q0 = mfma16(f4(a, e), kc[0], q0);
-          q1 = mfma16(f4(a, e), kc[16], q1);
-        } else if (e & 1) {
-          q1 = mfma16(f4(a, e), kc[0], q1);
-        } else {
-          q0 = mfma16(f4(a, e), kc[0], q0);
-        }
+        const float* kc = kc_col + (4 * s4 + e) * LS;
+#pragma unroll
+        for (int cbk = 0; cbk < G::CBW; ++cbk)
+          qa[cbk][e % G::DQ_CHAINS] = mfma16(f4(a, e), kc[16 * cbk], qa[cbk][e % G::DQ_CHAINS]);
       }
     }
     {
@@ -371,23 +434,16 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_bwd_fused_kernel(BwdParams p)
       const int off = (int)(((int64_t)qi0 * p.dqs.st + dcol0 + c16) * 4);
       const int rstep = (int)(p.dqs.st * 4);
 #pragma unroll
-      for (int r = 0; r < ((AMK_BWD_ABL & 1) ? 0 : 4); ++r) {
-        if (DQ == 0) {
-          if (G::NBLK == 2) {
-            __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(q0[r] * sc, dq_rsrc, off + r * rstep, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(q1[r] * sc, dq_rsrc, off + r * rstep + 64, 0, 0);
-          } else {
-            __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32((q0[r] + q1[r]) * sc, dq_rsrc, off + r * rstep, 0, 0);
-          }
-        } else {  // plain stores through the same range-checked descriptor
-          if (G::NBLK == 2) {
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, q0[r] * sc), dq_rsrc, off + r * rstep, 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, q1[r] * sc), dq_rsrc, off + r * rstep + 64, 0, 0);
-          } else {
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (q0[r] + q1[r]) * sc), dq_rsrc, off + r * rstep, 0, 0);
-          }
+      for (int r = 0; r < ((AMK_BWD_ABL & 1) ? 0 : 4); ++r)
+#pragma unroll
+        for (int cbk = 0; cbk < G::CBW; ++cbk) {
+          float x = qa[cbk][0][r];
+          if constexpr (G::DQ_CHAINS == 2) x += qa[cbk][1][r];
+          x *= sc;
+          if (DQ == 0) __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(x, dq_rsrc, off + r * rstep + 64 * cbk, 0, 0);
+          else  // plain stores through the same range-checked descriptor
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, x), dq_rsrc, off + r * rstep + 64 * cbk, 0, 0);
         }
-      }
     }
     __syncthreads();  // dS consumed, the next q / dO tiles visible
   }
@@ -396,12 +452,12 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_bwd_fused_kernel(BwdParams p)
     float* dkp = p.dk + (int64_t)b * p.dks.sb + (int64_t)kj * p.dks.st + (int64_t)h * p.dks.sh + 4 * hf;
     float* dvp = p.dv + (int64_t)b * p.dvs.sb + (int64_t)kj * p.dvs.st + (int64_t)h * p.dvs.sh + 4 * hf;
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      st4(dkp + 8 * g, make_float4(dk0[4 * g] * AMK_LN2, dk0[4 * g + 1] * AMK_LN2, dk0[4 * g + 2] * AMK_LN2, dk0[4 * g + 3] * AMK_LN2));
-      st4(dkp + 32 + 8 * g, make_float4(dk1[4 * g] * AMK_LN2, dk1[4 * g + 1] * AMK_LN2, dk1[4 * g + 2] * AMK_LN2, dk1[4 * g + 3] * AMK_LN2));
-      st4(dvp + 8 * g, make_float4(dv0[4 * g], dv0[4 * g + 1], dv0[4 * g + 2], dv0[4 * g + 3]));
-      st4(dvp + 32 + 8 * g, make_float4(dv1[4 * g], dv1[4 * g + 1], dv1[4 * g + 2], dv1[4 * g + 3]));
-    }
+    for (int n = 0; n < NTILE; ++n)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        st4(dkp + 32 * n + 8 * g, make_float4(dk[n][4 * g] * AMK_LN2, dk[n][4 * g + 1] * AMK_LN2, dk[n][4 * g + 2] * AMK_LN2, dk[n][4 * g + 3] * AMK_LN2));
+        st4(dvp + 32 * n + 8 * g, make_float4(dv[n][4 * g], dv[n][4 * g + 1], dv[n][4 * g + 2], dv[n][4 * g + 3]));
+      }
   }
 }
 
@@ -418,18 +474,18 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_reduce_kernel(const float* __
   }
 }
 
-template <int NW, bool KEPT, int DQ, bool CAUSAL>
-static bool launch_variant_c(BwdParams p, hipStream_t st) {
-  using G = FusedGeom<NW>;
-  static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_fused_kernel<NW, KEPT, DQ, CAUSAL>),
+template <int DH, int NW, int QS, bool KEPT, int DQ, bool CAUSAL>
+static bool launch_one(BwdParams p, hipStream_t st) {
+  using G = FGeom<DH, NW, QS>;
+  static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_fused_kernel<DH, NW, QS, KEPT, DQ, CAUSAL>),
                                                   hipFuncAttributeMaxDynamicSharedMemorySize,
                                                   G::LDS_FLOATS * (int)sizeof(float)) == hipSuccess;
   if (!attr_ok) return false;
   p.nkblk = (p.J + G::KB - 1) / G::KB;
-  const int64_t ndq = (int64_t)p.B * p.I * p.H * D;
+  const int64_t ndq = (int64_t)p.B * p.I * p.H * DH;
   if (DQ == 0 && hipMemsetAsync(p.dq, 0, (size_t)ndq * sizeof(float), st) != hipSuccess) return false;
   const int64_t nk = (int64_t)p.B * p.H * p.nkblk;
-  hipLaunchKernelGGL((attn_bwd_fused_kernel<NW, KEPT, DQ, CAUSAL>), dim3((unsigned)nk), dim3(G::NT), G::LDS_FLOATS * sizeof(float), st, p);
+  hipLaunchKernelGGL((attn_bwd_fused_kernel<DH, NW, QS, KEPT, DQ, CAUSAL>), dim3((unsigned)nk), dim3(G::NT), G::LDS_FLOATS * sizeof(float), st, p);
   if (DQ == 1 && p.nkblk > 1) {
     const int64_t n4 = ndq / 4;
     const unsigned grid = (unsigned)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
@@ -438,27 +494,27 @@ static bool launch_variant_c(BwdParams p, hipStream_t st) {
   return true;
 }
 
-template <int NW, bool KEPT, int DQ>
-static bool launch_variant(const BwdParams& p, hipStream_t st) {
-  return p.causal_mask ? launch_variant_c<NW, KEPT, DQ, true>(p, st) : launch_variant_c<NW, KEPT, DQ, false>(p, st);
+template <int DH, int NW, int QS, int DQ>
+static bool launch_geom(const BwdParams& p, hipStream_t st) {
+  if (p.scores) return p.causal_mask ? launch_one<DH, NW, QS, true, DQ, true>(p, st) : launch_one<DH, NW, QS, true, DQ, false>(p, st);
+  return p.causal_mask ? launch_one<DH, NW, QS, false, DQ, true>(p, st) : launch_one<DH, NW, QS, false, DQ, false>(p, st);
 }
 
 int fused_keys_per_wg(int J, int keys_per_wg) { return keys_per_wg ? keys_per_wg : (J >= 256 ? 256 : 128); }
 
-// Launch the fused kernel.  dq must be the dense (B, I, H, 64) layout (one memset / one reduce pass);
-// returns false (nothing launched) when the layout or the masks rule it out.
-// keys_per_wg: 128 (4 waves, two workgroups per CU) or 256 (8 waves, one per CU; half the dq adds);
-// 0 = pick (256 when the sequence has at least 256 keys).  p.dq_part != null: reproducible dq (DQ = 1).
-bool launch_attn_bwd_fused(const BwdParams& p, int keys_per_wg, hipStream_t st) {
-  if (!(p.dqs.sh == D && p.dqs.st == (int64_t)p.H * D && p.dqs.sb == (int64_t)p.I * p.H * D)) return false;
-  keys_per_wg = fused_keys_per_wg(p.J, keys_per_wg);
+// Launch the one-pass kernel of head dim Dh (32, 64, 128).  dq must be the dense (B, I, H, Dh) layout (one memset / one
+// reduce pass); returns false (nothing launched) when the head dim, the layout or the reproducible-dq request rules it out.
+// keys_per_wg, head dim 64 only: 128 (4 waves, two workgroups per CU) or 256 (8 waves, one per CU; half the dq adds);
+// 0 = pick (256 when the sequence has at least 256 keys).  32 / 128 have one geometry each.
+// p.dq_part != null: reproducible dq (DQ = 1), head dim 64 only.
+bool launch_attn_bwd_fused(const BwdParams& p, int Dh, int keys_per_wg, hipStream_t st) {
+  if (!(p.dqs.sh == Dh && p.dqs.st == (int64_t)p.H * Dh && p.dqs.sb == (int64_t)p.I * p.H * Dh)) return false;
   const bool det = p.dq_part != nullptr;
-  if (keys_per_wg == 256) {
-    if (det) return p.scores ? launch_variant<8, true, 1>(p, st) : launch_variant<8, false, 1>(p, st);
-    return p.scores ? launch_variant<8, true, 0>(p, st) : launch_variant<8, false, 0>(p, st);
-  }
-  if (det) return p.scores ? launch_variant<4, true, 1>(p, st) : launch_variant<4, false, 1>(p, st);
-  return p.scores ? launch_variant<4, true, 0>(p, st) : launch_variant<4, false, 0>(p, st);
+  if (Dh == 32) return !det && launch_geom<32, 8, 2, 0>(p, st);
+  if (Dh == 128) return !det && launch_geom<128, 4, 1, 0>(p, st);
+  if (Dh != 64) return false;
+  if (fused_keys_per_wg(p.J, keys_per_wg) == 256) return det ? launch_geom<64, 8, 1, 1>(p, st) : launch_geom<64, 8, 1, 0>(p, st);
+  return det ? launch_geom<64, 4, 1, 1>(p, st) : launch_geom<64, 4, 1, 0>(p, st);
 }
 
 }  // namespace amk_attn

@@ -75,25 +75,25 @@ __device__ __forceinline__ f32x16 zero16() {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-// Streams ROWS rows x 64 floats of one (batch, head) operand, global -> registers, 16 B per thread
-// and pass (row = tid/16 + (NT/16)*pass, 16 B at column 4*(tid%16)), through a raw buffer descriptor:
-// the hardware range check returns zeros for rows beyond the sequence, so a tile costs four
+// Streams ROWS rows x DH floats of one (batch, head) operand, global -> registers, 16 B per thread
+// and pass (F4R = DH/4 threads per row: row = tid/F4R + RP*pass, 16 B at column 4*(tid%F4R)), through a raw
+// buffer descriptor: the hardware range check returns zeros for rows beyond the sequence, so a tile costs four
 // address adds and no compares / selects / 64-bit multiplies (every VALU instruction is paid
 // at ~4 cycles against the f32 MFMA pipe: tools/ubench_mfma_valu.hip).
-template <int ROWS, int NT = 256>
+template <int ROWS, int NT = 256, int DH = 64>
 struct RowStagerT {
-  static constexpr int RP = NT / 16;    // rows covered by one pass of the workgroup's NT threads
+  static constexpr int F4R = DH / 4;    // threads per row
+  static constexpr int RP = NT / F4R;   // rows covered by one pass of the workgroup's NT threads
   static constexpr int NP = ROWS / RP;
+  static_assert(NP * RP == ROWS, "the passes of the workgroup cover the row block exactly");
   __amdgpu_buffer_rsrc_t rsrc;
   int voff[NP];
   int step;
   __device__ __forceinline__ void init(const float* base, int64_t row_stride, int nrows, int tid) {
-    // bytes up to the end of the last row's 64-float slice; base / size are wave-uniform
-    rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)(((int64_t)(nrows - 1) * row_stride + 64) * 4), 0x00020000);
-    const int srow = tid >> 4, scol = (tid & 15) * 4;
-#pragma unroll
-    for (int ps = 0; ps < NP; ++ps) voff[ps] = (int)(((int64_t)(srow + RP * ps) * row_stride + scol) * 4);
+    // bytes up to the end of the last row's DH-float slice; base / size are wave-uniform
+    rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)(((int64_t)(nrows - 1) * row_stride + DH) * 4), 0x00020000);
     step = (int)(ROWS * row_stride * 4);
+    seek(0, row_stride, tid);
   }
   __device__ __forceinline__ void load(float4 (&dst)[NP]) {
 #pragma unroll
@@ -106,7 +106,7 @@ struct RowStagerT {
   }
   // jump so that the next load() fetches row block `blk` (blocks of ROWS rows)
   __device__ __forceinline__ void seek(int blk, int64_t row_stride, int tid) {
-    const int srow = tid >> 4, scol = (tid & 15) * 4;
+    const int srow = (unsigned)tid / F4R, scol = ((unsigned)tid % F4R) * 4;
 #pragma unroll
     for (int ps = 0; ps < NP; ++ps) voff[ps] = (int)(((int64_t)(srow + RP * ps) * row_stride + scol) * 4) + blk * step;
   }
@@ -127,8 +127,8 @@ __device__ __forceinline__ float f4(const float4& v, int e) {
 // plain: unmasked calls may take the unmasked specialisation
 void launch_attn_fwd_x6(const FwdParams& p, int64_t nwg, hipStream_t st, bool plain);
 
-// attn_bwd_fused.hip: one-pass backward (dQ by atomics); false = not applicable, nothing launched.
-bool launch_attn_bwd_fused(const BwdParams& p, int keys_per_wg, hipStream_t st);
+// attn_bwd_fused.hip: one-pass backward for head dims 32, 64, 128 (dQ by atomics); false = not applicable, nothing launched.
+bool launch_attn_bwd_fused(const BwdParams& p, int Dh, int keys_per_wg, hipStream_t st);
 int fused_keys_per_wg(int J, int keys_per_wg);
 
 // attn_generic.hip / attn_generic.h: the forward for head dims 32, 96, 128, 160, 192, 224, 256 (attn_gen_supported),
@@ -136,7 +136,5 @@ int fused_keys_per_wg(int J, int keys_per_wg);
 bool attn_gen_supported(int Dh);
 void launch_attn_fwd_gen(const FwdParams& p, int Dh, int64_t nwg, hipStream_t st);
 void launch_attn_bwd_gen(const BwdParams& p, int Dh, int stages, hipStream_t st);
-// attn_bwd_fused_gen.hip: the one-pass backward for head dims 32 / 128 (dq by atomics); false = nothing launched
-bool launch_attn_bwd_fused_gen(const BwdParams& p, int Dh, hipStream_t st);
 
 }  // namespace amk_attn

@@ -4,8 +4,8 @@
 // lane, accumulators reused as the next product's B operand.
 // The backward kernels serve every head dim, 64 included (instantiated by attn_bwd.hip, next to the dispatch).  The
 // forward here serves the head dims other than 64: the D = 64 forward is the tuned one of attn_fwd.hip
-// (software-pipelined operand reads, kept scores), and the one-pass backwards are attn_bwd_fused.hip (64) and
-// attn_bwd_fused_gen.hip (32 / 128).
+// (software-pipelined operand reads, kept scores), and the one-pass backward of head dims 32, 64 and 128
+// is attn_bwd_fused.hip.
 // attn_generic.hip instantiates D = 32 and 128 and dispatches; attn_generic_dNNN.hip one further head dim each
 // (separate translation units, so the build compiles them in parallel).
 #pragma once

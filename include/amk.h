@@ -67,8 +67,8 @@ const char* amk_last_error(void);
  * key_mask: uint8 (B,J) contiguous or NULL; causal_mask: uint8 (I,J) contiguous
  * or NULL.  stats: (B,H,I,2) contiguous.  D is a multiple of 32 from 32 to 256; any other head dim is
  * AMK_EUNSUPPORTED before any device work.  64: the tuned kernels and the split-bf16 forward; 32 / 128:
- * csrc/attn_generic.h -- forward, with kept scores when there is no mask -- and csrc/attn_bwd_fused_gen.hip,
- * the one-pass backward with dq by atomics; the reproducible backward of those head dims is the two recompute
+ * csrc/attn_generic.h -- forward, with kept scores when there is no mask -- and the head dim 64 one-pass backward
+ * of csrc/attn_bwd_fused.hip at their own geometry, dq by atomics; their reproducible backward is the two recompute
  * kernels of csrc/attn_generic.h.  96, 160, 192, 224, 256 (same library version, 0.4.0): the forward and the
  * recompute backward of csrc/attn_generic.h only -- amk_attn_fwd_keep / amk_attn_bwd_kept return
  * AMK_EUNSUPPORTED for them, and a FUSED request to amk_attn_bwd runs the recompute kernels.

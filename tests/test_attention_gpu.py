@@ -301,7 +301,7 @@ def test_kept_scores_equal_recomputed_scores(device, backward_path, B, H, I, J):
 def test_core_other_head_dims(device, backward_path, D, B, H, I, J, masks):
     """dim_head 32 and 128 (the reference takes any dim_head, models/softmax_attention.py:23) against the oracle, every
     mask combination, ragged sizes, several key blocks per (batch, head).  Paths: "fused" = the one-pass backward of
-    csrc/attn_bwd_fused_gen.hip (round 4) -- reading the scores the unmasked forward kept, or recomputing them
+    csrc/attn_bwd_fused.hip (round 4) -- reading the scores the unmasked forward kept, or recomputing them
     ("fused-recompute-*", and every masked call) --; "deterministic" and "two-kernel" = the two reproducible recompute
     kernels of csrc/attn_generic.hip."""
     if backward_path not in ("fused", "fused-recompute-256", "deterministic", "two-kernel"):

@@ -22,14 +22,18 @@ from collections import defaultdict
 def short(name):
     """Kernel name without namespace / arguments; the template variants bench.py reports separately keep
     their bench.py names: attn_fwd_kernel<.., .., true> = attn_fwd_keep_kernel (writes the scores),
-    attn_bwd_fused_kernel<NW, true> = attn_bwd_fused_kernel(kept scores)."""
+    attn_bwd_fused_kernel<.., KEPT = true, ..> = attn_bwd_fused_kernel(kept scores); its head dims 32 / 128 keep the
+    head dim in the name, and so does attn_bwd_fused_gen_kernel, their kernel in CSVs from before the merge."""
     m = re.search(r"(\w+_kernel)(<[^>]*>)?", name)
     if not m:
         return name
     base, targs = m.group(1), (m.group(2) or "").replace(" ", "")
-    if base == "attn_bwd_fused_kernel":   # <NW, KEPT, DQ>
+    if base in ("attn_bwd_fused_kernel", "attn_bwd_fused_gen_kernel"):
+        # <DH, NW, QS, KEPT, DQ, CAUSAL>; older CSVs: <NW, KEPT, DQ[, CAUSAL]> (head dim 64), gen <DH, NW, QS, KEPT, CAUSAL>
         t = targs.strip("<>").split(",")
-        return base + ("(kept scores)" if len(t) > 1 and t[1] == "true" else "")
+        old64 = base == "attn_bwd_fused_kernel" and len(t) < 6
+        dh, kept = ("64", t[1:2]) if old64 else (t[0], t[3:4])
+        return "attn_bwd_fused_kernel" + ("" if dh == "64" else f"<{dh}>") + ("(kept scores)" if kept == ["true"] else "")
     if base == "attn_fwd_kernel" and targs.endswith(",true>"):
         return "attn_fwd_keep_kernel"
     if base == "attn_fwd_plain_kernel":   # the unmasked forward (round 4): <KEEP>

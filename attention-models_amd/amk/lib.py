@@ -125,6 +125,10 @@ SIGNATURES = {
     "amk_grouped_gemm_nt_bf16": (_I, [_P, _L, _I, _P, _P, _P, _P, _L, _I, _I, _I, _P, _P]),
     "amk_grouped_gemm_nn_bf16": (_I, [_P, _L, _I, _P, _P, _P, _P, _L, _I, _I, _I, _P, _P]),
     "amk_grouped_gemm_wgrad_bf16": (_I, [_P, _L, _I, _P, _L, _I, _P, _P, _P, _L, _I, _I, _I, _P, _P, _P]),
+    "amk_grouped_gemm_nt64_bf16": (_I, [_P, _L, _I, _P, _P, _P, _P, _L, _I, _I, _I, _P, _P]),
+    "amk_grouped_gemm_nn64_bf16": (_I, [_P, _L, _I, _P, _P, _P, _P, _L, _I, _I, _I, _P, _P]),
+    "amk_grouped_gemm_wgrad64_bf16": (_I, [_P, _L, _I, _P, _L, _I, _P, _P, _P, _L, _I, _I, _I, _P, _P]),
+    "amk_moe_expert_sums_bf16": (_I, [_P, _I, _L, _I, _P, _P, _L, _I, _I, _I, _P, _P]),
 }
 
 _lib = None

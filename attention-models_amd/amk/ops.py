@@ -1012,11 +1012,171 @@ class _SummedExperts(torch.autograd.Function):
         return da, None, dW, None, None
 
 
+# AMK_SWITCHHEAD_BF16: SwitchHeadAttention's experts under bf16 autocast on bf16 operands -- the narrow grouped kernels
+# and the bf16 per-expert sums of csrc/moe_bf16.hip, the dense Z products on the library's bf16 GEMM -- instead of
+# upcasting what autocast hands over and running the f32 kernels.  0: the path before.  Measurements: README,
+# "Switches".  Read once per process.
+SWITCHHEAD_BF16 = os.environ.get("AMK_SWITCHHEAD_BF16", "1") != "0"
+
+
+def _expert_sums_bf16(a2, a_div, ids, scale, G, fan, E, d):
+    """_expert_sums with Z (G, E*d) in bf16 (the same f32 sums, rounded once); a2 f32 or bf16."""
+    Z = torch.empty((G, E * d), device=a2.device, dtype=torch.bfloat16)
+    with _timed(f"bf16_moe_expert_sums G{G} fan{fan} E{E} d{d}"):
+        rc = _lib.load().amk_moe_expert_sums_bf16(_ptr(a2), int(a2.dtype == torch.bfloat16), a2.stride(0), a_div, _ptr(ids), scale,
+                                                  G, fan, E, d, _ptr(Z), _stream())
+    _lib.check(rc, "amk_moe_expert_sums_bf16")
+    return Z
+
+
+class _SharedRowExpertsBF16(torch.autograd.Function):
+    """_SharedRowExperts under bf16 autocast: the routing on the f32 logits as ever, x cast to bf16 once, the weight
+    through _w16 (the optimizer's bf16 shadow when it is current); V (G*E, d) f32 by amk_grouped_gemm_nt64_bf16, combine
+    and gate gradient by the f32 kernels (out is f32); backward: Z16 = the gated per-expert sums of d_out in bf16,
+    dx = Z16 @ W16 on the library's bf16 GEMM (handed back in x's dtype), dW f32 by amk_grouped_gemm_wgrad64_bf16."""
+
+    @staticmethod
+    def forward(ctx, x2, logits2, W, k, H):
+        _require_device(W)
+        U, E = logits2.shape
+        N, Kd = W.shape[1], W.shape[2]
+        G, fan = U // H, H * k
+        if x2.shape != (G, Kd) or U % H:
+            raise RuntimeError(f"shared-row experts: shapes disagree: x {tuple(x2.shape)} U {U} H {H} W {tuple(W.shape)}")
+        dev = x2.device
+        x16 = _row_major_view(x2.detach().to(torch.bfloat16), 8)
+        w16 = _w16(W).detach().contiguous()
+        L = _lib.load()
+        with _timed(f"moe_topk U{U} E{E} k{k} + distinct lists"):
+            ids, gate = _topk(logits2.detach().float(), k)
+            offsets, perm = _route_distinct(ids, G, fan, E)
+        V = torch.empty((G * E, N), device=dev, dtype=torch.float32)   # rows of chosen (token, expert) only
+        with _timed(f"bf16_grouped_nt P{U * k} N{N} K{Kd} (distinct rows)"):
+            _lib.check(L.amk_grouped_gemm_nt64_bf16(_ptr(x16), x16.stride(0), E, _ptr(w16), _NULL, _ptr(offsets), _ptr(perm),
+                                                    G * E, E, N, Kd, _ptr(V), _stream()), "amk_grouped_gemm_nt64_bf16")
+        out = torch.empty((U, N), device=dev, dtype=torch.float32)
+        _lib.check(L.amk_moe_combine_rows(_ptr(V), _ptr(ids), _ptr(gate), U, 1, k, N, fan, E, _ptr(out), _stream()),
+                   "amk_moe_combine_rows")
+        ctx.save_for_backward(x16, w16, V, ids, gate, offsets, perm)
+        ctx.cfg = (k, H, x2.dtype, logits2.dtype)
+        ctx.mark_non_differentiable(ids)
+        ctx.set_materialize_grads(False)
+        return out, ids
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_out, _d_ids):
+        if d_out is None:
+            return (None,) * 5
+        x16, w16, V, ids, gate, offsets, perm = ctx.saved_tensors
+        k, H, x_dtype, l_dtype = ctx.cfg
+        E, N, Kd = w16.shape
+        G, fan = x16.shape[0], H * k
+        U = G * H
+        dev = x16.device
+        L = _lib.load()
+        d32 = d_out.to(torch.float32).contiguous()   # the gate gradient reads f32 rows
+        dlogits = torch.empty((U, E), device=dev, dtype=torch.float32)
+        _lib.check(L.amk_moe_gate_grad_rows(_ptr(d32), _ptr(V), _ptr(ids), _ptr(gate), U * k, k, E, N, k, fan, _ptr(dlogits),
+                                            _stream()), "amk_moe_gate_grad_rows")
+        d_in = _row_major_view(d_out, 8) if d_out.dtype == torch.bfloat16 else d32
+        Z16 = _expert_sums_bf16(d_in, k, ids, _ptr(gate), G, fan, E, N)   # (G, E*N): gated output gradients per (token, expert)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            with _timed(f"bf16_dense_z_gemm M{G} N{Kd} K{E * N}"):
+                dx = (Z16 @ w16.view(E * N, Kd)).to(x_dtype)
+        dW = torch.empty((E, N, Kd), device=dev, dtype=torch.float32)
+        with _timed(f"bf16_grouped_wgrad P{U * k} N{N} K{Kd} (distinct rows)"):
+            _lib.check(L.amk_grouped_gemm_wgrad64_bf16(_ptr(Z16), N, 1, _ptr(x16), x16.stride(0), E, _NULL, _ptr(offsets), _ptr(perm),
+                                                       G * E, E, N, Kd, _ptr(dW), _stream()), "amk_grouped_gemm_wgrad64_bf16")
+        return dx, dlogits.to(l_dtype), dW, None, None
+
+
+class _SummedExpertsBF16(torch.autograd.Function):
+    """_SummedExperts under bf16 autocast: Z16 = the per-expert sums of the (f32) attention rows in bf16, out = Z16 @ W16
+    as (E*d, dim) on the library's bf16 GEMM -- out leaves in bf16, as an autocast nn.Linear's does; backward: d_out cast
+    to bf16 once, D (G*E, d) f32 by amk_grouped_gemm_nn64_bf16 fanned out by the f32 combine (da f32), dW f32 by
+    amk_grouped_gemm_wgrad64_bf16 on (d16, Z16).  The logits get no gradient."""
+
+    @staticmethod
+    def forward(ctx, a2, logits2, W, k, H):
+        _require_device(W)
+        U, E = logits2.shape
+        N, Kd = W.shape[1], W.shape[2]
+        G, fan = U // H, H * k
+        if a2.shape != (U, Kd) or U % H:
+            raise RuntimeError(f"summed experts: shapes disagree: a {tuple(a2.shape)} U {U} H {H} W {tuple(W.shape)}")
+        a2 = _row_major_view(a2.detach(), 8)
+        w16 = _w16(W).detach().contiguous()
+        with _timed(f"moe_topk U{U} E{E} k{k}"):
+            ids, _gate = _topk(logits2.detach().float(), k)
+        Z16 = _expert_sums_bf16(a2, k, ids, _NULL, G, fan, E, Kd)
+        with _timed(f"bf16_dense_z_gemm M{G} N{N} K{E * Kd}"):
+            out = Z16 @ w16.permute(0, 2, 1).reshape(E * Kd, N)
+        ctx.save_for_backward(w16, Z16, ids)
+        ctx.cfg = (k, H, a2.dtype)
+        ctx.mark_non_differentiable(ids)
+        ctx.set_materialize_grads(False)
+        return out, ids
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_out, _d_ids):
+        if d_out is None:
+            return (None,) * 5
+        w16, Z16, ids = ctx.saved_tensors
+        k, H, a_dtype = ctx.cfg
+        E, N, Kd = w16.shape
+        G, fan = Z16.shape[0], H * k
+        U = G * H
+        dev = w16.device
+        d16 = _row_major_view(d_out.to(torch.bfloat16), 8)   # once, for both products
+        L = _lib.load()
+        offsets, perm = _route_distinct(ids, G, fan, E)
+        da = None
+        if ctx.needs_input_grad[0]:
+            D = torch.empty((G * E, Kd), device=dev, dtype=torch.float32)
+            with _timed(f"bf16_grouped_nn P{U * k} N{N} K{Kd} (distinct rows)"):
+                _lib.check(L.amk_grouped_gemm_nn64_bf16(_ptr(d16), d16.stride(0), E, _ptr(w16), _NULL, _ptr(offsets), _ptr(perm),
+                                                        G * E, E, N, Kd, _ptr(D), _stream()), "amk_grouped_gemm_nn64_bf16")
+            da = torch.empty((U, Kd), device=dev, dtype=torch.float32)
+            _lib.check(L.amk_moe_combine_rows(_ptr(D), _ptr(ids), _NULL, U, 1, k, Kd, fan, E, _ptr(da), _stream()),
+                       "amk_moe_combine_rows")
+            da = da.to(a_dtype)
+        dW = torch.empty((E, N, Kd), device=dev, dtype=torch.float32)
+        with _timed(f"bf16_grouped_wgrad P{U * k} N{N} K{Kd} (distinct rows)"):
+            _lib.check(L.amk_grouped_gemm_wgrad64_bf16(_ptr(d16), d16.stride(0), E, _ptr(Z16), Kd, 1, _NULL, _ptr(offsets), _ptr(perm),
+                                                       G * E, E, N, Kd, _ptr(dW), _stream()), "amk_grouped_gemm_wgrad64_bf16")
+        return da, None, dW, None, None
+
+
+def _switchhead_bf16_ok(a2, logits2, W, d):
+    """bf16 autocast on HIP tensors, an f32 master weight with d <= 64 and both sides multiples of 8, and either the
+    weight trains or nothing does (a frozen weight under a trainable input keeps the f32 Functions)."""
+    return (SWITCHHEAD_BF16 and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16
+            and a2.is_cuda and logits2.is_cuda and W.is_cuda and W.dtype == torch.float32 and W.dim() == 3
+            and d <= 64 and W.shape[1] % 8 == 0 and W.shape[2] % 8 == 0
+            and a2.dtype in (torch.float32, torch.bfloat16) and logits2.dtype in (torch.float32, torch.bfloat16)
+            and (W.requires_grad or not (torch.is_grad_enabled() and (a2.requires_grad or logits2.requires_grad))))
+
+
+def switchhead_bf16_shapes(dim, d, fan, E):
+    """A SwitchHeadAttention of these sizes takes the bf16 Functions under bf16 autocast (with f32 master weights on the
+    GPU): the switch, the distinct form (distinct_experts_ok) and d <= 64 with d and dim multiples of 8."""
+    return SWITCHHEAD_BF16 and distinct_experts_ok(dim, d, fan, E) and d <= 64 and d % 8 == 0 and dim % 8 == 0
+
+
 def shared_row_experts(x2, logits2, W, k, H):
+    if _switchhead_bf16_ok(x2, logits2, W, W.shape[1] if W.dim() == 3 else 0):
+        with torch.autocast("cuda", enabled=False):
+            return _SharedRowExpertsBF16.apply(x2, logits2, W, k, H)
     return _SharedRowExperts.apply(x2, logits2, W, k, H)
 
 
 def summed_experts(a2, logits2, W, k, H):
+    if _switchhead_bf16_ok(a2, logits2, W, W.shape[2] if W.dim() == 3 else 0):
+        with torch.autocast("cuda", enabled=False):
+            return _SummedExpertsBF16.apply(a2, logits2, W, k, H)
     return _SummedExperts.apply(a2, logits2, W, k, H)
 
 

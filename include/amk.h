@@ -776,6 +776,39 @@ int amk_grouped_gemm_wgrad_bf16(const void* G, int64_t ldg, int g_div, const voi
                                 const float* scale, const int32_t* offsets, const int32_t* perm,
                                 int64_t P, int E, int N, int Kd, float* dW, float* dbias, void* stream);
 
+/* --------------------------------------------------------------------------
+ * SwitchHeadAttention's experts under bf16 autocast (csrc/moe_bf16.hip): the nn.Linear experts of
+ * models/switchhead_attention.py:46,53 inside accelerator.autocast() (trainers/vit.py:67) -- V experts (E, d, dim),
+ * output experts (E, dim, d), d <= 64 -- as ops._SharedRowExpertsBF16 / _SummedExpertsBF16 form them (:58-88,115): the
+ * three grouped products above in a tile form for a side of at most 64, and the per-expert sums with a bf16 result.
+ * The contract is that of the block above: bf16 operands, f32 accumulation, f32 Y / dW, the same offsets / perm lists
+ * (amk_moe_route's, or amk_moe_route_distinct's virtual pairs with P = G E and a_div = E) and a_div / g_div / x_div
+ * addressing, rows the lists do not name untouched, exactly zero dW for an expert without pairs; no atomics, no
+ * workspace, nothing allocated or synchronised, bitwise reproducible and capturable.
+ *   nt64:    amk_grouped_gemm_nt_bf16 for N <= 64 (unit: 256 pairs x all outputs, the waves over the pairs).
+ *   nn64:    amk_grouped_gemm_nn_bf16 for Kd <= 64.
+ *   wgrad64: amk_grouped_gemm_wgrad_bf16 for min(N, Kd) <= 64, without dbias (the experts have none).
+ *   amk_moe_expert_sums_bf16: amk_moe_expert_sums with Z (G, E d) in bf16, fully overwritten:
+ *            Z[g,e,:] = bf16(sum over the fan pairs p = g fan + j of row g with ids[p] == e of scale[p] A[p / a_div,:]),
+ *            the sum in f32 in ascending j exactly as the f32 kernel forms it, rounded once.  A: f32 rows
+ *            (a_is_bf16 == 0) or bf16 rows (!= 0) of d at stride lda ELEMENTS; scale f32 (G fan) or NULL.
+ * AMK_EINVAL: null pointer, non-positive size, a pointer not 16-byte aligned, a row stride that is not a multiple of 8
+ * or is shorter than the row.  AMK_EUNSUPPORTED: the narrow side above 64 (nt64: N, nn64: Kd, wgrad64: both N and
+ * Kd), N, Kd or d not a multiple of 8, E > 1024, fan > 4096, a buffer of 2 GiB or more, a grid of 2^31 workgroups.
+ * All refusals precede any device work.
+ * -------------------------------------------------------------------------- */
+int amk_grouped_gemm_nt64_bf16(const void* A, int64_t lda, int a_div, const void* W, const float* bias,
+                               const int32_t* offsets, const int32_t* perm, int64_t P, int E, int N, int Kd,
+                               float* Y, void* stream);
+int amk_grouped_gemm_nn64_bf16(const void* G, int64_t ldg, int a_div, const void* W, const float* scale,
+                               const int32_t* offsets, const int32_t* perm, int64_t P, int E, int N, int Kd,
+                               float* Y, void* stream);
+int amk_grouped_gemm_wgrad64_bf16(const void* G, int64_t ldg, int g_div, const void* X, int64_t ldx, int x_div,
+                                  const float* scale, const int32_t* offsets, const int32_t* perm,
+                                  int64_t P, int E, int N, int Kd, float* dW, void* stream);
+int amk_moe_expert_sums_bf16(const void* A, int a_is_bf16, int64_t lda, int a_div, const int64_t* ids, const float* scale,
+                             int64_t G, int fan, int E, int d, void* Z, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,8 @@ from .muse import MUSE, BidirectionalDecoder
 from .vit import ViT
 from .vit_moe import ViTMoE
 from .vitvqgan import Codebook, ViTVQGAN
-from . import vqgan  # conv-VQGAN codebook (models/vqgan.py:138-182): vqgan.Codebook
+from . import vqgan  # the conv VQGAN's own codebook stays vqgan.Codebook (models/vqgan.py:138-182)
+from .vqgan import VQGAN
 
-__all__ = ["SoftmaxAttention", "AgentAttention", "SwitchHeadAttention", "MoELayer", "Codebook", "ViTVQGAN",
+__all__ = ["SoftmaxAttention", "AgentAttention", "SwitchHeadAttention", "MoELayer", "Codebook", "ViTVQGAN", "VQGAN",
            "ViT", "ViTMoE", "MUSE", "BidirectionalDecoder", "MaskGitTransformer", "BiDirectionalTransformer", "build_model"]

@@ -2135,6 +2135,72 @@ def bn_leaky_relu(x, bn, slope):
                         float(slope))
 
 
+# ---------------------------------------------------------------------------- conv VQGAN GroupNorm + Swish
+# AMK_GN_ACT: "1" (default) = the GroupNorm (+ Swish) of amk.models.vqgan runs on csrc/gn_act.hip (x, mean and rstd saved; y
+# and sigma recomputed in the backward); "0" = nn.GroupNorm and x * sigmoid(x) as they are.  Measured on VQGAN(256, 8192),
+# batch 8 at 256 px, forward + backward, the switch alternated in one process (tools/kbench_vqgan.py,
+# profiles/kbench_vqgan.log): 79.8 ms with the modules, 73.7 ms fused, the arms' spreads 0.13 / 0.45 ms, peak memory 10.9 -> 7.5 GiB.  So the switch ships on.  Read once per process.
+GN_ACT = os.environ.get("AMK_GN_ACT", "1") != "0"
+
+
+def _gn_ws(x, G):
+    N, C, HW = _bn_dims(x)
+    return torch.empty(int(_lib.load().amk_gnact_ws_floats(N, C, HW, G)), device=x.device, dtype=torch.float32)
+
+
+class _GNAct(torch.autograd.Function):
+    """z = act(group_norm(x)), act 0 identity, 1 swish.  Saves x, mean and rstd (N, G); y and sigma are recomputed."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, G, eps, act):
+        N, C, HW = _bn_dims(x)
+        z = torch.empty_like(x)
+        mean = torch.empty((N, G), device=x.device, dtype=torch.float32)
+        rstd = torch.empty((N, G), device=x.device, dtype=torch.float32)
+        with _timed("gnact_fwd"):
+            _lib.check(_lib.load().amk_gnact_fwd(_ptr(x), _ptr(weight), _ptr(bias), N, C, HW, G, float(eps), act, _ptr(z),
+                                                 _ptr(mean), _ptr(rstd), _ptr(_gn_ws(x, G)), _stream()), "amk_gnact_fwd")
+        ctx.save_for_backward(x, weight, bias, mean, rstd)
+        ctx.G, ctx.act = G, act
+        return z
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gz):
+        x, weight, bias, mean, rstd = ctx.saved_tensors
+        gz = _bn_aligned(gz)
+        N, C, HW = _bn_dims(x)
+        gx = torch.empty_like(x)
+        dw = torch.empty_like(weight)
+        db = torch.empty_like(bias)
+        with _timed("gnact_bwd"):
+            _lib.check(_lib.load().amk_gnact_bwd(_ptr(gz), _ptr(x), _ptr(weight), _ptr(bias), _ptr(mean), _ptr(rstd), N, C,
+                                                 HW, ctx.G, ctx.act, _ptr(gx), _ptr(dw), _ptr(db), _ptr(_gn_ws(x, ctx.G)),
+                                                 _stream()), "amk_gnact_bwd")
+        return (gx if ctx.needs_input_grad[0] else None, dw if ctx.needs_input_grad[1] else None,
+                db if ctx.needs_input_grad[2] else None, None, None, None)
+
+
+def group_norm_act_ok(gn, x):
+    """True when (gn, act) can run on amk_gnact_*: an nn.GroupNorm with f32 affine parameters and a contiguous 4-D f32 HIP
+    tensor with at least one element, outside autocast and with the switch on.  Everything else (CPU, autocast,
+    non-contiguous input, AMK_GN_ACT=0) keeps the modules."""
+    return (GN_ACT and isinstance(gn, torch.nn.GroupNorm) and gn.affine and gn.weight.dtype == torch.float32
+            and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous() and x.numel() > 0
+            and gn.weight.is_cuda and not torch.is_autocast_enabled())
+
+
+def group_norm_act(x, gn, act):
+    """act(gn(x)) for an nn.GroupNorm; act 0 = identity, 1 = swish x * sigmoid(x)."""
+    if act not in (0, 1):
+        raise ValueError(f"group_norm_act: act must be 0 (identity) or 1 (swish), got {act}")
+    if not group_norm_act_ok(gn, x):
+        y = gn(x)
+        return y * torch.sigmoid(y) if act == 1 else y
+    x = x if x.data_ptr() % 16 == 0 else x.clone()
+    return _GNAct.apply(x, gn.weight, gn.bias, gn.num_groups, gn.eps, act)
+
+
 # ---------------------------------------------------------------------------- masked-token loss head
 # Logits + cross-entropy on the valid rows only (csrc/ce_head.hip) in place of F.linear + F.cross_entropy at the end of
 # the Muse / MaskGit train step: the (rows, vocabulary) logits, their log-softmax and their gradient are never written.

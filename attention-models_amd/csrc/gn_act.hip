@@ -1,0 +1,418 @@
+// GroupNorm(G, C, eps) + optional Swish of the conv VQGAN, f32 NCHW, for gfx950: forward and backward.
+//
+// ATen runs the pair as a normalisation kernel plus two element-wise passes and keeps the normalised tensor for the
+// backward.  Here the forward is two launches (per-segment statistics, then fold + apply) and the backward three
+// (per-plane partial sums, fold + apply, and a small fold of the parameter gradients over the batch); y and sigma are
+// recomputed from x, mean and rstd.  No float atomics: every output is bitwise reproducible, and a sample's result
+// does not depend on the batch it sits in.
+//
+// Notation, per run (n, g) of m = cpg HW contiguous floats (cpg = C / G channels): mu, var biased statistics,
+// r = (var + eps)^-1/2, xh = (x - mu) r, y = gamma_c xh + beta_c, z = act(y); act 0 = identity, act 1 = y sigma(y).
+//
+// Work split: a run is cpg planes (channels) of HW floats.  It is cut into S segments -- PP whole planes each, or for
+// planes larger than SEG, Q pieces of one plane -- and workgroup run * S + s owns segment s of its run in every
+// kernel.  A plane starts at element (n C + c) HW, 16-byte aligned only when that is a multiple of 4: each plane is
+// walked as a scalar head, an aligned float4 body and a scalar tail.
+#include "amk_common.h"
+
+namespace amk_gn {
+
+constexpr int BLOCK = 256;
+constexpr int WAVES = BLOCK / 64;
+constexpr int64_t SEG = 4096;  // target elements per workgroup segment
+
+struct Geo {
+  int N, C, G, cpg;
+  int64_t HW;
+  int PP;     // whole planes per segment (Q == 1)
+  int Q;      // pieces per plane (PP == 1)
+  int64_t L;  // elements per piece (Q > 1)
+  int S;      // segments per run
+};
+
+static Geo make_geo(int N, int C, int64_t HW, int G) {
+  Geo g;
+  g.N = N; g.C = C; g.G = G; g.cpg = C / G; g.HW = HW;
+  if (HW <= SEG) {
+    g.PP = (int)(SEG / HW);
+    if (g.PP > g.cpg) g.PP = g.cpg;
+    g.Q = 1; g.L = HW;
+    g.S = (g.cpg + g.PP - 1) / g.PP;
+  } else {
+    g.PP = 1;
+    g.Q = (int)((HW + SEG - 1) / SEG);
+    g.L = (((HW + g.Q - 1) / g.Q) + 3) & ~(int64_t)3;
+    g.S = g.cpg * g.Q;
+  }
+  return g;
+}
+
+struct Seg {
+  int p0, p1;       // planes of the run
+  int q;            // piece of the plane (0 when Q == 1)
+  int64_t e0, e1;   // elements of each plane
+};
+
+__device__ __forceinline__ Seg seg_of(const Geo& g, int s) {
+  Seg r;
+  if (g.Q == 1) {
+    r.p0 = s * g.PP; r.p1 = min(g.cpg, r.p0 + g.PP);
+    r.q = 0; r.e0 = 0; r.e1 = g.HW;
+  } else {
+    r.p0 = s / g.Q; r.p1 = r.p0 + 1;
+    r.q = s % g.Q;
+    r.e0 = min(g.HW, (int64_t)r.q * g.L);
+    r.e1 = min(g.HW, r.e0 + g.L);
+  }
+  return r;
+}
+
+__device__ __forceinline__ float seg_count(const Geo& g, int s) {
+  const Seg r = seg_of(g, s);
+  return (float)((int64_t)(r.p1 - r.p0) * (r.e1 - r.e0));
+}
+
+template <int W> struct Width { static constexpr int value = W; };
+
+template <int W>
+__device__ __forceinline__ void ld(const float* p, float (&v)[W]) {
+  if constexpr (W == 4) {
+    const float4 t = *reinterpret_cast<const float4*>(p);
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+  } else {
+    v[0] = *p;
+  }
+}
+
+template <int W>
+__device__ __forceinline__ void st(float* p, const float (&v)[W]) {
+  if constexpr (W == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  else *p = v[0];
+}
+
+// For every plane p of segment s of `run`: pre(p), then f(Width<4>, off) for every aligned 4-element run and
+// f(Width<1>, off) for every edge element, then post(p, piece); `off` indexes the (N, C, HW) tensor, whose base is
+// 16-byte aligned.  The loops' bounds are uniform over the workgroup, so pre and post may synchronise.
+template <class Pre, class F, class Post>
+__device__ __forceinline__ void seg_walk(const Geo& g, int run, int s, Pre&& pre, F&& f, Post&& post) {
+  const Seg r = seg_of(g, s);
+  const int64_t len = r.e1 - r.e0;
+  const int t = threadIdx.x;
+  for (int p = r.p0; p < r.p1; ++p) {
+    pre(p);
+    const int64_t base = ((int64_t)run * g.cpg + p) * g.HW + r.e0;
+    const int head = (int)min((int64_t)((4 - (base & 3)) & 3), len);
+    const int64_t nv = (len - head) >> 2;
+    const int tail = (int)(len - head - 4 * nv);
+    for (int64_t i = t; i < nv; i += BLOCK) f(Width<4>{}, base + head + 4 * i);
+    if (t < head) f(Width<1>{}, base + t);
+    else if (t < head + tail) f(Width<1>{}, base + 4 * nv + t);
+    post(p, r.q);
+  }
+}
+
+struct Nop {
+  __device__ __forceinline__ void operator()(int) const {}
+  __device__ __forceinline__ void operator()(int, int) const {}
+};
+
+struct Sum {
+  template <int K>
+  __device__ __forceinline__ void operator()(float (&a)[K], const float (&b)[K]) const {
+#pragma unroll
+    for (int k = 0; k < K; ++k) a[k] += b[k];
+  }
+};
+
+// Chan's merge of (count, mean, M2) triples
+struct Chan {
+  __device__ __forceinline__ void operator()(float (&a)[3], const float (&b)[3]) const {
+    const float n = a[0] + b[0];
+    if (b[0] == 0.f) return;
+    if (a[0] == 0.f) { a[0] = b[0]; a[1] = b[1]; a[2] = b[2]; return; }
+    const float d = b[1] - a[1], f = b[0] / n;
+    a[1] += d * f;
+    a[2] += b[2] + d * d * a[0] * f;
+    a[0] = n;
+  }
+};
+
+// Fixed-order block reduction: a butterfly inside each wave (lane 0's result is used), then every thread folds the
+// WAVES wave results in order, so all threads return the same value.
+template <int K, class Op>
+__device__ __forceinline__ void block_reduce(float (&v)[K], Op op, float* lds) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    float w[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) w[k] = __shfl_xor(v[k], o, 64);
+    op(v, w);
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) lds[wave * K + k] = v[k];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < K; ++k) v[k] = lds[k];
+#pragma unroll
+  for (int w = 1; w < WAVES; ++w) {
+    float u[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) u[k] = lds[w * K + k];
+    op(v, u);
+  }
+  __syncthreads();
+}
+
+// sigma(y) = 1 / (1 + e^-y) on v_exp_f32 and v_rcp_f32 (1 ulp each).  y -> -inf: e = +inf, rcp(inf) = 0;
+// y -> +inf: e = 0, sigma = 1.  e is used nowhere else, so no inf * 0 can arise.
+__device__ __forceinline__ float sigmoid(float y) {
+  const float e = __builtin_amdgcn_exp2f(-y * AMK_LOG2E);
+  return __builtin_amdgcn_rcpf(1.f + e);
+}
+
+template <int ACT>
+__device__ __forceinline__ float act_fwd(float y) {
+  if constexpr (ACT == 1) return y * sigmoid(y);
+  else return y;
+}
+
+// d act / d y; swish' = sigma (1 + y (1 - sigma)): at y = -200 it is 0 * -199, at y = 200 it is 1 * (1 + 200 * 0).
+template <int ACT>
+__device__ __forceinline__ float act_grad(float y) {
+  if constexpr (ACT == 1) {
+    const float sg = sigmoid(y);
+    return sg * (1.f + y * (1.f - sg));
+  } else {
+    return 1.f;
+  }
+}
+
+// ---------------------------------------------------------------- forward
+// part (N G, S, 2): per-segment mean and M2, each from two passes over the segment (the second hits L2).
+__global__ __launch_bounds__(BLOCK) void stats_kernel(const float* __restrict__ x, Geo g, float* __restrict__ part) {
+  __shared__ float lds[WAVES * 3];
+  const int run = blockIdx.x / g.S, s = blockIdx.x % g.S;
+  float v[1] = {0.f};
+  seg_walk(g, run, s, Nop{}, [&](auto w, int64_t off) {
+    constexpr int W = decltype(w)::value;
+    float xv[W];
+    ld<W>(x + off, xv);
+#pragma unroll
+    for (int k = 0; k < W; ++k) v[0] += xv[k];
+  }, Nop{});
+  block_reduce<1>(v, Sum{}, lds);
+  const float cnt = seg_count(g, s);
+  const float mean = cnt > 0.f ? v[0] / cnt : 0.f;
+  float q[1] = {0.f};
+  seg_walk(g, run, s, Nop{}, [&](auto w, int64_t off) {
+    constexpr int W = decltype(w)::value;
+    float xv[W];
+    ld<W>(x + off, xv);
+#pragma unroll
+    for (int k = 0; k < W; ++k) { const float d = xv[k] - mean; q[0] += d * d; }
+  }, Nop{});
+  block_reduce<1>(q, Sum{}, lds);
+  if (threadIdx.x == 0) {
+    part[(int64_t)blockIdx.x * 2] = mean;
+    part[(int64_t)blockIdx.x * 2 + 1] = q[0];
+  }
+}
+
+template <int ACT>
+__global__ __launch_bounds__(BLOCK) void fwd_apply_kernel(
+    const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta, Geo g,
+    const float* __restrict__ part, float eps, float* __restrict__ z, float* __restrict__ mean_out,
+    float* __restrict__ rstd_out) {
+  __shared__ float lds[WAVES * 3];
+  const int run = blockIdx.x / g.S, s = blockIdx.x % g.S;
+  const int c0 = (run % g.G) * g.cpg;
+  float a[3] = {0.f, 0.f, 0.f};
+  for (int j = threadIdx.x; j < g.S; j += BLOCK) {
+    const int64_t i = ((int64_t)run * g.S + j) * 2;
+    const float b[3] = {seg_count(g, j), part[i], part[i + 1]};
+    Chan{}(a, b);
+  }
+  block_reduce<3>(a, Chan{}, lds);
+  const float mu = a[1], var = a[2] / a[0];
+  const float r = rsqrtf(var + eps);
+  if (s == 0 && threadIdx.x == 0) {
+    mean_out[run] = mu;
+    rstd_out[run] = r;
+  }
+  float scale = 0.f, shift = 0.f;
+  seg_walk(g, run, s, [&](int p) {
+    scale = gamma[c0 + p] * r;
+    shift = beta[c0 + p] - mu * scale;
+  }, [&](auto w, int64_t off) {
+    constexpr int W = decltype(w)::value;
+    float xv[W];
+    ld<W>(x + off, xv);
+#pragma unroll
+    for (int k = 0; k < W; ++k) xv[k] = act_fwd<ACT>(fmaf(xv[k], scale, shift));
+    st<W>(z + off, xv);
+  }, Nop{});
+}
+
+// ---------------------------------------------------------------- backward
+// part (N C, Q, 2): per-(n, channel, piece) sums of gy and gy * xh, gy = gz act'(y).
+template <int ACT>
+__global__ __launch_bounds__(BLOCK) void bwd_reduce_kernel(
+    const float* __restrict__ gz, const float* __restrict__ x, const float* __restrict__ gamma,
+    const float* __restrict__ beta, const float* __restrict__ mean, const float* __restrict__ rstd, Geo g,
+    float* __restrict__ part) {
+  __shared__ float lds[WAVES * 3];
+  const int run = blockIdx.x / g.S, s = blockIdx.x % g.S;
+  const int c0 = (run % g.G) * g.cpg;
+  const float mu = mean[run], r = rstd[run];
+  float scale = 0.f, shift = 0.f;
+  float v[2];
+  seg_walk(g, run, s, [&](int p) {
+    scale = gamma[c0 + p] * r;
+    shift = beta[c0 + p] - mu * scale;
+    v[0] = 0.f; v[1] = 0.f;
+  }, [&](auto w, int64_t off) {
+    constexpr int W = decltype(w)::value;
+    float xv[W], gv[W];
+    ld<W>(x + off, xv);
+    ld<W>(gz + off, gv);
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      const float gy = gv[k] * act_grad<ACT>(fmaf(xv[k], scale, shift));
+      v[0] += gy;
+      v[1] += gy * ((xv[k] - mu) * r);
+    }
+  }, [&](int p, int q) {
+    block_reduce<2>(v, Sum{}, lds);
+    if (threadIdx.x == 0) {
+      const int64_t i = (((int64_t)run * g.cpg + p) * g.Q + q) * 2;
+      part[i] = v[0];
+      part[i + 1] = v[1];
+    }
+  });
+}
+
+// gx = r (gamma_c gy - S1/m - xh S2/m), S1 = sum gamma_c gy and S2 = sum gamma_c gy xh over the run, folded from the
+// run's cpg Q partials in a fixed order.
+template <int ACT>
+__global__ __launch_bounds__(BLOCK) void bwd_apply_kernel(
+    const float* __restrict__ gz, const float* __restrict__ x, const float* __restrict__ gamma,
+    const float* __restrict__ beta, const float* __restrict__ mean, const float* __restrict__ rstd, Geo g,
+    const float* __restrict__ part, float* __restrict__ gx) {
+  __shared__ float lds[WAVES * 3];
+  const int run = blockIdx.x / g.S, s = blockIdx.x % g.S;
+  const int c0 = (run % g.G) * g.cpg;
+  const float mu = mean[run], r = rstd[run];
+  float v[2] = {0.f, 0.f};
+  for (int j = threadIdx.x; j < g.cpg * g.Q; j += BLOCK) {
+    const float gm = gamma[c0 + j / g.Q];
+    const int64_t i = ((int64_t)run * g.cpg * g.Q + j) * 2;
+    v[0] += gm * part[i];
+    v[1] += gm * part[i + 1];
+  }
+  block_reduce<2>(v, Sum{}, lds);
+  const float inv_m = 1.f / (float)((double)g.cpg * (double)g.HW);
+  const float A = v[0] * inv_m, B = v[1] * inv_m;
+  float gm = 0.f, scale = 0.f, shift = 0.f;
+  seg_walk(g, run, s, [&](int p) {
+    gm = gamma[c0 + p];
+    scale = gm * r;
+    shift = beta[c0 + p] - mu * scale;
+  }, [&](auto w, int64_t off) {
+    constexpr int W = decltype(w)::value;
+    float xv[W], gv[W];
+    ld<W>(x + off, xv);
+    ld<W>(gz + off, gv);
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      const float gy = gv[k] * act_grad<ACT>(fmaf(xv[k], scale, shift));
+      const float xh = (xv[k] - mu) * r;
+      xv[k] = r * (gm * gy - A - xh * B);
+    }
+    st<W>(gx + off, xv);
+  }, Nop{});
+}
+
+// dbeta_c = sum over (n, piece) of the gy partials, dgamma_c of the gy xh partials, in a fixed order; workgroup c.
+__global__ __launch_bounds__(BLOCK) void param_grad_kernel(const float* __restrict__ part, Geo g,
+                                                           float* __restrict__ dgamma, float* __restrict__ dbeta) {
+  __shared__ float lds[WAVES * 3];
+  const int c = blockIdx.x;
+  float v[2] = {0.f, 0.f};
+  for (int j = threadIdx.x; j < g.N * g.Q; j += BLOCK) {
+    const int64_t i = (((int64_t)(j / g.Q) * g.C + c) * g.Q + j % g.Q) * 2;
+    v[0] += part[i];
+    v[1] += part[i + 1];
+  }
+  block_reduce<2>(v, Sum{}, lds);
+  if (threadIdx.x == 0) {
+    dbeta[c] = v[0];
+    dgamma[c] = v[1];
+  }
+}
+
+}  // namespace amk_gn
+
+using namespace amk_gn;
+
+static bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// The launch grid is N G S workgroups, one dimension.
+static int64_t grid_of(int N, int C, int64_t HW, int G) {
+  const Geo g = make_geo(N, C, HW, G);
+  return (int64_t)N * G * g.S;
+}
+
+#define AMK_GN_SHAPE(what)                                                                          \
+  AMK_CHECK_ARG(N > 0 && C > 0 && HW > 0 && G > 0, what ": non-positive size");                     \
+  AMK_CHECK_ARG(act == 0 || act == 1, what ": act must be 0 (identity) or 1 (swish), got %d", act); \
+  AMK_CHECK_SUPPORTED(C % G == 0, what ": G %d does not divide C %d", G, C);                        \
+  AMK_CHECK_SUPPORTED(grid_of(N, C, HW, G) < ((int64_t)1 << 31),                                    \
+                      what ": shape N %d C %d HW %lld G %d needs a grid beyond 2^31", N, C, (long long)HW, G)
+
+extern "C" int64_t amk_gnact_ws_floats(int N, int C, int64_t HW, int G) {
+  if (N <= 0 || C <= 0 || HW <= 0 || G <= 0 || C % G != 0) return 0;
+  // forward: N G S pairs; backward: N C Q pairs, and S <= cpg Q
+  return (int64_t)N * C * make_geo(N, C, HW, G).Q * 2;
+}
+
+extern "C" int amk_gnact_fwd(const float* x, const float* gamma, const float* beta, int N, int C, int64_t HW, int G,
+                             float eps, int act, float* z, float* mean, float* rstd, float* ws, void* stream) {
+  AMK_CHECK_ARG(x && gamma && beta && z && mean && rstd && ws, "amk_gnact_fwd: null pointer");
+  AMK_GN_SHAPE("amk_gnact_fwd");
+  AMK_CHECK_ARG(a16(x) && a16(z), "amk_gnact_fwd: x and z must be 16-byte aligned");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const Geo g = make_geo(N, C, HW, G);
+  const dim3 grid((unsigned)grid_of(N, C, HW, G)), block(BLOCK);
+  hipLaunchKernelGGL(stats_kernel, grid, block, 0, st, x, g, ws);
+  if (act == 1)
+    hipLaunchKernelGGL(fwd_apply_kernel<1>, grid, block, 0, st, x, gamma, beta, g, ws, eps, z, mean, rstd);
+  else
+    hipLaunchKernelGGL(fwd_apply_kernel<0>, grid, block, 0, st, x, gamma, beta, g, ws, eps, z, mean, rstd);
+  AMK_CHECK_LAUNCH("amk_gnact_fwd");
+  return AMK_OK;
+}
+
+extern "C" int amk_gnact_bwd(const float* gz, const float* x, const float* gamma, const float* beta,
+                             const float* mean, const float* rstd, int N, int C, int64_t HW, int G, int act,
+                             float* gx, float* dgamma, float* dbeta, float* ws, void* stream) {
+  AMK_CHECK_ARG(gz && x && gamma && beta && mean && rstd && gx && dgamma && dbeta && ws,
+                "amk_gnact_bwd: null pointer");
+  AMK_GN_SHAPE("amk_gnact_bwd");
+  AMK_CHECK_ARG(a16(gz) && a16(x) && a16(gx), "amk_gnact_bwd: gz, x and gx must be 16-byte aligned");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const Geo g = make_geo(N, C, HW, G);
+  const dim3 grid((unsigned)grid_of(N, C, HW, G)), block(BLOCK);
+  if (act == 1) {
+    hipLaunchKernelGGL(bwd_reduce_kernel<1>, grid, block, 0, st, gz, x, gamma, beta, mean, rstd, g, ws);
+    hipLaunchKernelGGL(bwd_apply_kernel<1>, grid, block, 0, st, gz, x, gamma, beta, mean, rstd, g, ws, gx);
+  } else {
+    hipLaunchKernelGGL(bwd_reduce_kernel<0>, grid, block, 0, st, gz, x, gamma, beta, mean, rstd, g, ws);
+    hipLaunchKernelGGL(bwd_apply_kernel<0>, grid, block, 0, st, gz, x, gamma, beta, mean, rstd, g, ws, gx);
+  }
+  hipLaunchKernelGGL(param_grad_kernel, dim3(C), block, 0, st, ws, g, dgamma, dbeta);
+  AMK_CHECK_LAUNCH("amk_gnact_bwd");
+  return AMK_OK;
+}

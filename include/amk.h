@@ -680,6 +680,27 @@ int amk_bnact_bwd_bwd(const float* ggx, const float* gg_gamma, const float* gg_b
                       void* stream);
 
 /* --------------------------------------------------------------------------
+ * GroupNorm(G, C, eps) + optional Swish of the conv VQGAN (csrc/gn_act.hip), f32, contiguous NCHW x (N, C, HW);
+ * replaces the GroupNorm and Swish modules of the reference, models/vqgan.py:11-22.
+ * Per sample n and group g (cpg = C / G consecutive channels, one contiguous run of m = cpg HW floats): mu and var are
+ * the biased statistics of the run, r = (var + eps)^-1/2, xh = (x - mu) r, y = gamma_c xh + beta_c, z = act(y);
+ * act 0 = identity, act 1 = swish y sigma(y).  y and sigma are recomputed from x, never stored.
+ *   fwd : z; mean, rstd (N, G) for the backward.
+ *   bwd : gy = gz act'(y), swish' = sigma (1 + y (1 - sigma));  dbeta_c = sum_{n,hw} gy, dgamma_c = sum_{n,hw} gy xh (C);
+ *         S1 = sum_run gamma_c gy, S2 = sum_run gamma_c gy xh;  gx = r (gamma_c gy - S1/m - xh S2/m).
+ * Any HW; x, z, gz and gx 16-byte aligned; G must divide C (else AMK_EUNSUPPORTED, as is a grid beyond 2^31
+ * workgroups); act outside {0, 1} is AMK_EINVAL.  Reductions go through ordered per-workgroup partials in ws
+ * (amk_gnact_ws_floats(N, C, HW, G) floats), no atomics: bitwise reproducible, and a sample's outputs do not depend
+ * on the rest of the batch.  Two launches forward, three backward.
+ * -------------------------------------------------------------------------- */
+int64_t amk_gnact_ws_floats(int N, int C, int64_t HW, int G);
+int amk_gnact_fwd(const float* x, const float* gamma, const float* beta, int N, int C, int64_t HW, int G, float eps,
+                  int act, float* z, float* mean, float* rstd, float* ws, void* stream);
+int amk_gnact_bwd(const float* gz, const float* x, const float* gamma, const float* beta, const float* mean,
+                  const float* rstd, int N, int C, int64_t HW, int G, int act, float* gx, float* dgamma, float* dbeta,
+                  float* ws, void* stream);
+
+/* --------------------------------------------------------------------------
  * Masked-token loss head (csrc/ce_head.hip): logits + cross-entropy on the rows that count, f32 on
  * v_mfma_f32_32x32x2_f32.  Replaces decoder.linear(...) followed by F.cross_entropy(logits.transpose(1, 2), tgt,
  * ignore_index=-1) of the reference's train steps (models/muse.py:176, models/maskgit.py:187):

@@ -8,8 +8,14 @@ as one fused op, ``ops.group_norm_act(x, gn, 1)`` (csrc/gn_act.hip), which recom
 instead of storing it; the ``gn`` inside ``NonLocalBlock`` runs the same kernels without the activation.  Containers that
 hold a ``GroupNorm`` followed by a ``Swish`` (``ResidualBlock.block``, the tails of ``Encoder.model`` / ``Decoder.model``) are
 walked by ``_run``, which fuses each such pair and calls every other layer as it is; ``Swish`` therefore has no parameters and
-is skipped after a fused pair.  With ``AMK_GN_ACT=0``, on the CPU, under autocast or for a non-contiguous input the op keeps
-the modules (``nn.GroupNorm`` and ``x * sigmoid(x)``).
+is skipped after a fused pair.  With ``AMK_GN_ACT=0``, on the CPU or for a non-contiguous input the op keeps the modules
+(``nn.GroupNorm`` and ``x * sigmoid(x)``).
+
+Under ``torch.autocast("cuda", dtype=torch.bfloat16)`` every norm sits behind a convolution (or behind ``F.pad`` /
+``F.interpolate`` / a residual sum of convolution outputs), so its input is a contiguous bf16 tensor, and all 70 run on the
+bf16 form of the same kernels (``amk_gnact_bf16_*``, ``AMK_GN_ACT_BF16``): bf16 in, f32 arithmetic, bf16 out rounded once,
+where the modules would cast to f32, run three f32 passes and leave the rounding to the next convolution.  ``encode_imgs`` /
+``decode_indices`` under autocast and ``no_grad`` (a frozen tokenizer) take the forward kernel and save nothing.
 
 Codebook (models/vqgan.py:138-182): the same l2-normalised nearest-neighbour lookup as the ViT-VQGAN codebook with a
 channels-first ``(B, C, H, W)`` input, ``codebook_dim`` 256 by default (README.md:246-249), uniform init, ``beta`` on the

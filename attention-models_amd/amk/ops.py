@@ -2181,6 +2181,65 @@ class _GNAct(torch.autograd.Function):
                 db if ctx.needs_input_grad[2] else None, None, None, None)
 
 
+# AMK_GN_ACT_BF16: the same pair under bf16 autocast, where the modules cast the convolution's bf16 output to f32
+# (group_norm is on autocast's f32 list), normalise, run sigmoid and mul as two more f32 passes, keep three f32 tensors for
+# the backward and leave the cast back to bf16 to the next convolution.  "1" = amk_gnact_bf16_fwd / _bwd (csrc/gn_act.hip
+# on bf16 x, z, gz and gx: the f32 arithmetic of the f32 kernels, one rounding to bf16 on the store; bf16 x and f32 mean /
+# rstd saved); "0" = the modules.  Measured on VQGAN(256, 8192), batch 8 at 256 px under bf16 autocast, forward + backward, the
+# switch alternated in one process (tools/kbench_vqgan.py --autocast bf16, profiles/kbench_vqgan_bf16.log): 51.98 ms with the
+# modules, 39.59 ms fused, the arms' spreads 0.09 / 0.32 ms, peak memory 9.65 -> 3.97 GiB.  So the switch ships on.
+# AMK_GN_ACT=0 disables both.  Read once per process.
+GN_ACT_BF16 = os.environ.get("AMK_GN_ACT_BF16", "1") != "0"
+
+
+class _GNActBF16(torch.autograd.Function):
+    """_GNAct on bf16 x under bf16 autocast: z and gx bf16, rounded once; mean, rstd (N, G), dgamma and dbeta f32.  Saves the
+    bf16 x, mean and rstd."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, G, eps, act):
+        N, C, HW = _bn_dims(x)
+        L = _lib.load()
+        z = torch.empty_like(x)
+        mean = torch.empty((N, G), device=x.device, dtype=torch.float32)
+        rstd = torch.empty((N, G), device=x.device, dtype=torch.float32)
+        ws = torch.empty(int(L.amk_gnact_bf16_ws_floats(N, C, HW, G)), device=x.device, dtype=torch.float32)
+        with _timed("gnact_bf16_fwd"):
+            _lib.check(L.amk_gnact_bf16_fwd(_ptr(x), _ptr(weight), _ptr(bias), N, C, HW, G, float(eps), act, _ptr(z),
+                                            _ptr(mean), _ptr(rstd), _ptr(ws), _stream()), "amk_gnact_bf16_fwd")
+        ctx.save_for_backward(x, weight, bias, mean, rstd)
+        ctx.G, ctx.act = G, act
+        return z
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gz):
+        x, weight, bias, mean, rstd = ctx.saved_tensors
+        gz = _bn_aligned(gz.to(torch.bfloat16))
+        N, C, HW = _bn_dims(x)
+        L = _lib.load()
+        gx = torch.empty_like(x)
+        dw = torch.empty_like(weight)
+        db = torch.empty_like(bias)
+        ws = torch.empty(int(L.amk_gnact_bf16_ws_floats(N, C, HW, ctx.G)), device=x.device, dtype=torch.float32)
+        with _timed("gnact_bf16_bwd"):
+            _lib.check(L.amk_gnact_bf16_bwd(_ptr(gz), _ptr(x), _ptr(weight), _ptr(bias), _ptr(mean), _ptr(rstd), N, C, HW,
+                                            ctx.G, ctx.act, _ptr(gx), _ptr(dw), _ptr(db), _ptr(ws), _stream()),
+                       "amk_gnact_bf16_bwd")
+        return (gx if ctx.needs_input_grad[0] else None, dw if ctx.needs_input_grad[1] else None,
+                db if ctx.needs_input_grad[2] else None, None, None, None)
+
+
+def group_norm_act_bf16_ok(gn, x):
+    """True when (gn, act) can run on amk_gnact_bf16_*: both switches on, autocast enabled on the device with dtype bf16, an
+    nn.GroupNorm with f32 affine parameters on the device and a contiguous 4-D bf16 HIP tensor with at least one element.
+    An f32 x under autocast, autocast to f16 and everything group_norm_act_ok refuses keep the modules."""
+    return (GN_ACT and GN_ACT_BF16 and isinstance(gn, torch.nn.GroupNorm) and gn.affine
+            and gn.weight.dtype == torch.float32 and gn.weight.is_cuda and x.is_cuda and x.dtype == torch.bfloat16
+            and x.dim() == 4 and x.is_contiguous() and x.numel() > 0 and torch.is_autocast_enabled()
+            and torch.get_autocast_dtype("cuda") == torch.bfloat16)
+
+
 def group_norm_act_ok(gn, x):
     """True when (gn, act) can run on amk_gnact_*: an nn.GroupNorm with f32 affine parameters and a contiguous 4-D f32 HIP
     tensor with at least one element, outside autocast and with the switch on.  Everything else (CPU, autocast,
@@ -2191,9 +2250,16 @@ def group_norm_act_ok(gn, x):
 
 
 def group_norm_act(x, gn, act):
-    """act(gn(x)) for an nn.GroupNorm; act 0 = identity, 1 = swish x * sigmoid(x)."""
+    """act(gn(x)) for an nn.GroupNorm; act 0 = identity, 1 = swish x * sigmoid(x).
+
+    The result is f32, except for a bf16 x under bf16 autocast that group_norm_act_bf16_ok accepts: there it is bf16 (the
+    modules would return f32, which the convolution that consumes it casts to bf16: the same values, rounded in the same
+    place)."""
     if act not in (0, 1):
         raise ValueError(f"group_norm_act: act must be 0 (identity) or 1 (swish), got {act}")
+    if group_norm_act_bf16_ok(gn, x):
+        x = x if x.data_ptr() % 16 == 0 else x.clone()
+        return _GNActBF16.apply(x, gn.weight, gn.bias, gn.num_groups, gn.eps, act)
     if not group_norm_act_ok(gn, x):
         y = gn(x)
         return y * torch.sigmoid(y) if act == 1 else y

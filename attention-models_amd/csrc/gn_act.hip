@@ -1,4 +1,5 @@
-// GroupNorm(G, C, eps) + optional Swish of the conv VQGAN, f32 NCHW, for gfx950: forward and backward.
+// GroupNorm(G, C, eps) + optional Swish of the conv VQGAN, NCHW, for gfx950: forward and backward, for f32 tensors and,
+// under bf16 autocast, for bf16 x, z, gz and gx (amk_gnact_bf16_*).
 //
 // ATen runs the pair as a normalisation kernel plus two element-wise passes and keeps the normalised tensor for the
 // backward.  Here the forward is two launches (per-segment statistics, then fold + apply) and the backward three
@@ -13,6 +14,15 @@
 // planes larger than SEG, Q pieces of one plane -- and workgroup run * S + s owns segment s of its run in every
 // kernel.  A plane starts at element (n C + c) HW, 16-byte aligned only when that is a multiple of 4: each plane is
 // walked as a scalar head, an aligned float4 body and a scalar tail.
+//
+// bf16: every kernel is a template on the element type T of x, z, gz and gx.  T = __bf16 reads 8 elements per 16-byte
+// access (head and tail of up to 7 elements; a plane is aligned only when (n C + c) HW is a multiple of 8; pieces are
+// multiples of 8), widens them to f32 on the load and rounds z and gx to bf16 once, to nearest even, on the store.
+// Everything between is the f32 arithmetic of T = float: statistics, y, sigma, the partial sums, mean, rstd, dgamma and
+// dbeta are f32, as are gamma and beta.  SEG stays 4096 elements (8 KiB of bf16): the small layers of the model
+// (512 x 16^2, 256 x 32^2) are one or two segments per run, latency-bound at one workgroup per CU, and halving their
+// workgroups to keep 16 KiB per segment would halve what hides that latency; at the large layers either choice fills the
+// device many times over.
 #include "amk_common.h"
 
 namespace amk_gn {
@@ -30,7 +40,8 @@ struct Geo {
   int S;      // segments per run
 };
 
-static Geo make_geo(int N, int C, int64_t HW, int G) {
+// VW: elements per 16-byte access (4 for f32, 8 for bf16); pieces are multiples of it.
+static Geo make_geo(int N, int C, int64_t HW, int G, int VW = 4) {
   Geo g;
   g.N = N; g.C = C; g.G = G; g.cpg = C / G; g.HW = HW;
   if (HW <= SEG) {
@@ -41,7 +52,7 @@ static Geo make_geo(int N, int C, int64_t HW, int G) {
   } else {
     g.PP = 1;
     g.Q = (int)((HW + SEG - 1) / SEG);
-    g.L = (((HW + g.Q - 1) / g.Q) + 3) & ~(int64_t)3;
+    g.L = (((HW + g.Q - 1) / g.Q) + (VW - 1)) & ~(int64_t)(VW - 1);
     g.S = g.cpg * g.Q;
   }
   return g;
@@ -90,10 +101,40 @@ __device__ __forceinline__ void st(float* p, const float (&v)[W]) {
   else *p = v[0];
 }
 
-// For every plane p of segment s of `run`: pre(p), then f(Width<4>, off) for every aligned 4-element run and
-// f(Width<1>, off) for every edge element, then post(p, piece); `off` indexes the (N, C, HW) tensor, whose base is
-// 16-byte aligned.  The loops' bounds are uniform over the workgroup, so pre and post may synchronise.
-template <class Pre, class F, class Post>
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+template <int W>
+__device__ __forceinline__ void ld(const __bf16* p, float (&v)[W]) {
+  if constexpr (W == 8) {
+    const bf16x8 t = *reinterpret_cast<const bf16x8*>(p);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = (float)t[k];
+  } else {
+    v[0] = (float)*p;
+  }
+}
+
+// the one rounding of z and gx: f32 -> bf16, to nearest even
+template <int W>
+__device__ __forceinline__ void st(__bf16* p, const float (&v)[W]) {
+  if constexpr (W == 8) {
+    bf16x8 t;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) t[k] = (__bf16)v[k];
+    *reinterpret_cast<bf16x8*>(p) = t;
+  } else {
+    *p = (__bf16)v[0];
+  }
+}
+
+// elements per 16-byte access and its log2
+template <class T> struct Vec { static constexpr int W = 4, SH = 2; };
+template <> struct Vec<__bf16> { static constexpr int W = 8, SH = 3; };
+
+// For every plane p of segment s of `run`: pre(p), then f(Width<VW>, off) for every aligned VW-element run (VW = 4 for
+// f32, 8 for bf16) and f(Width<1>, off) for every edge element, then post(p, piece); `off` indexes the (N, C, HW) tensor
+// of T, whose base is 16-byte aligned.  The loops' bounds are uniform over the workgroup, so pre and post may synchronise.
+template <class T, class Pre, class F, class Post>
 __device__ __forceinline__ void seg_walk(const Geo& g, int run, int s, Pre&& pre, F&& f, Post&& post) {
   const Seg r = seg_of(g, s);
   const int64_t len = r.e1 - r.e0;
@@ -101,12 +142,13 @@ __device__ __forceinline__ void seg_walk(const Geo& g, int run, int s, Pre&& pre
   for (int p = r.p0; p < r.p1; ++p) {
     pre(p);
     const int64_t base = ((int64_t)run * g.cpg + p) * g.HW + r.e0;
-    const int head = (int)min((int64_t)((4 - (base & 3)) & 3), len);
-    const int64_t nv = (len - head) >> 2;
-    const int tail = (int)(len - head - 4 * nv);
-    for (int64_t i = t; i < nv; i += BLOCK) f(Width<4>{}, base + head + 4 * i);
+    constexpr int VW = Vec<T>::W;
+    const int head = (int)min((int64_t)((VW - (base & (VW - 1))) & (VW - 1)), len);
+    const int64_t nv = (len - head) >> Vec<T>::SH;
+    const int tail = (int)(len - head - VW * nv);
+    for (int64_t i = t; i < nv; i += BLOCK) f(Width<VW>{}, base + head + VW * i);
     if (t < head) f(Width<1>{}, base + t);
-    else if (t < head + tail) f(Width<1>{}, base + 4 * nv + t);
+    else if (t < head + tail) f(Width<1>{}, base + VW * nv + t);
     post(p, r.q);
   }
 }
@@ -192,11 +234,12 @@ __device__ __forceinline__ float act_grad(float y) {
 
 // ---------------------------------------------------------------- forward
 // part (N G, S, 2): per-segment mean and M2, each from two passes over the segment (the second hits L2).
-__global__ __launch_bounds__(BLOCK) void stats_kernel(const float* __restrict__ x, Geo g, float* __restrict__ part) {
+template <class T>
+__global__ __launch_bounds__(BLOCK) void stats_kernel(const T* __restrict__ x, Geo g, float* __restrict__ part) {
   __shared__ float lds[WAVES * 3];
   const int run = blockIdx.x / g.S, s = blockIdx.x % g.S;
   float v[1] = {0.f};
-  seg_walk(g, run, s, Nop{}, [&](auto w, int64_t off) {
+  seg_walk<T>(g, run, s, Nop{}, [&](auto w, int64_t off) {
     constexpr int W = decltype(w)::value;
     float xv[W];
     ld<W>(x + off, xv);
@@ -207,7 +250,7 @@ __global__ __launch_bounds__(BLOCK) void stats_kernel(const float* __restrict__ 
   const float cnt = seg_count(g, s);
   const float mean = cnt > 0.f ? v[0] / cnt : 0.f;
   float q[1] = {0.f};
-  seg_walk(g, run, s, Nop{}, [&](auto w, int64_t off) {
+  seg_walk<T>(g, run, s, Nop{}, [&](auto w, int64_t off) {
     constexpr int W = decltype(w)::value;
     float xv[W];
     ld<W>(x + off, xv);
@@ -221,10 +264,10 @@ __global__ __launch_bounds__(BLOCK) void stats_kernel(const float* __restrict__ 
   }
 }
 
-template <int ACT>
+template <class T, int ACT>
 __global__ __launch_bounds__(BLOCK) void fwd_apply_kernel(
-    const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta, Geo g,
-    const float* __restrict__ part, float eps, float* __restrict__ z, float* __restrict__ mean_out,
+    const T* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta, Geo g,
+    const float* __restrict__ part, float eps, T* __restrict__ z, float* __restrict__ mean_out,
     float* __restrict__ rstd_out) {
   __shared__ float lds[WAVES * 3];
   const int run = blockIdx.x / g.S, s = blockIdx.x % g.S;
@@ -243,7 +286,7 @@ __global__ __launch_bounds__(BLOCK) void fwd_apply_kernel(
     rstd_out[run] = r;
   }
   float scale = 0.f, shift = 0.f;
-  seg_walk(g, run, s, [&](int p) {
+  seg_walk<T>(g, run, s, [&](int p) {
     scale = gamma[c0 + p] * r;
     shift = beta[c0 + p] - mu * scale;
   }, [&](auto w, int64_t off) {
@@ -258,9 +301,9 @@ __global__ __launch_bounds__(BLOCK) void fwd_apply_kernel(
 
 // ---------------------------------------------------------------- backward
 // part (N C, Q, 2): per-(n, channel, piece) sums of gy and gy * xh, gy = gz act'(y).
-template <int ACT>
+template <class T, int ACT>
 __global__ __launch_bounds__(BLOCK) void bwd_reduce_kernel(
-    const float* __restrict__ gz, const float* __restrict__ x, const float* __restrict__ gamma,
+    const T* __restrict__ gz, const T* __restrict__ x, const float* __restrict__ gamma,
     const float* __restrict__ beta, const float* __restrict__ mean, const float* __restrict__ rstd, Geo g,
     float* __restrict__ part) {
   __shared__ float lds[WAVES * 3];
@@ -269,7 +312,7 @@ __global__ __launch_bounds__(BLOCK) void bwd_reduce_kernel(
   const float mu = mean[run], r = rstd[run];
   float scale = 0.f, shift = 0.f;
   float v[2];
-  seg_walk(g, run, s, [&](int p) {
+  seg_walk<T>(g, run, s, [&](int p) {
     scale = gamma[c0 + p] * r;
     shift = beta[c0 + p] - mu * scale;
     v[0] = 0.f; v[1] = 0.f;
@@ -296,11 +339,11 @@ __global__ __launch_bounds__(BLOCK) void bwd_reduce_kernel(
 
 // gx = r (gamma_c gy - S1/m - xh S2/m), S1 = sum gamma_c gy and S2 = sum gamma_c gy xh over the run, folded from the
 // run's cpg Q partials in a fixed order.
-template <int ACT>
+template <class T, int ACT>
 __global__ __launch_bounds__(BLOCK) void bwd_apply_kernel(
-    const float* __restrict__ gz, const float* __restrict__ x, const float* __restrict__ gamma,
+    const T* __restrict__ gz, const T* __restrict__ x, const float* __restrict__ gamma,
     const float* __restrict__ beta, const float* __restrict__ mean, const float* __restrict__ rstd, Geo g,
-    const float* __restrict__ part, float* __restrict__ gx) {
+    const float* __restrict__ part, T* __restrict__ gx) {
   __shared__ float lds[WAVES * 3];
   const int run = blockIdx.x / g.S, s = blockIdx.x % g.S;
   const int c0 = (run % g.G) * g.cpg;
@@ -316,7 +359,7 @@ __global__ __launch_bounds__(BLOCK) void bwd_apply_kernel(
   const float inv_m = 1.f / (float)((double)g.cpg * (double)g.HW);
   const float A = v[0] * inv_m, B = v[1] * inv_m;
   float gm = 0.f, scale = 0.f, shift = 0.f;
-  seg_walk(g, run, s, [&](int p) {
+  seg_walk<T>(g, run, s, [&](int p) {
     gm = gamma[c0 + p];
     scale = gm * r;
     shift = beta[c0 + p] - mu * scale;
@@ -360,17 +403,45 @@ using namespace amk_gn;
 static bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // The launch grid is N G S workgroups, one dimension.
-static int64_t grid_of(int N, int C, int64_t HW, int G) {
-  const Geo g = make_geo(N, C, HW, G);
+static int64_t grid_of(int N, int C, int64_t HW, int G, int VW = 4) {
+  const Geo g = make_geo(N, C, HW, G, VW);
   return (int64_t)N * G * g.S;
 }
 
-#define AMK_GN_SHAPE(what)                                                                          \
+#define AMK_GN_SHAPE(what, VW)                                                                      \
   AMK_CHECK_ARG(N > 0 && C > 0 && HW > 0 && G > 0, what ": non-positive size");                     \
   AMK_CHECK_ARG(act == 0 || act == 1, what ": act must be 0 (identity) or 1 (swish), got %d", act); \
   AMK_CHECK_SUPPORTED(C % G == 0, what ": G %d does not divide C %d", G, C);                        \
-  AMK_CHECK_SUPPORTED(grid_of(N, C, HW, G) < ((int64_t)1 << 31),                                    \
+  AMK_CHECK_SUPPORTED(grid_of(N, C, HW, G, VW) < ((int64_t)1 << 31),                                \
                       what ": shape N %d C %d HW %lld G %d needs a grid beyond 2^31", N, C, (long long)HW, G)
+
+template <class T>
+static void launch_fwd(const T* x, const float* gamma, const float* beta, int N, int C, int64_t HW, int G, float eps,
+                       int act, T* z, float* mean, float* rstd, float* ws, hipStream_t st) {
+  const Geo g = make_geo(N, C, HW, G, Vec<T>::W);
+  const dim3 grid((unsigned)grid_of(N, C, HW, G, Vec<T>::W)), block(BLOCK);
+  hipLaunchKernelGGL(stats_kernel<T>, grid, block, 0, st, x, g, ws);
+  if (act == 1)
+    hipLaunchKernelGGL((fwd_apply_kernel<T, 1>), grid, block, 0, st, x, gamma, beta, g, ws, eps, z, mean, rstd);
+  else
+    hipLaunchKernelGGL((fwd_apply_kernel<T, 0>), grid, block, 0, st, x, gamma, beta, g, ws, eps, z, mean, rstd);
+}
+
+template <class T>
+static void launch_bwd(const T* gz, const T* x, const float* gamma, const float* beta, const float* mean,
+                       const float* rstd, int N, int C, int64_t HW, int G, int act, T* gx, float* dgamma, float* dbeta,
+                       float* ws, hipStream_t st) {
+  const Geo g = make_geo(N, C, HW, G, Vec<T>::W);
+  const dim3 grid((unsigned)grid_of(N, C, HW, G, Vec<T>::W)), block(BLOCK);
+  if (act == 1) {
+    hipLaunchKernelGGL((bwd_reduce_kernel<T, 1>), grid, block, 0, st, gz, x, gamma, beta, mean, rstd, g, ws);
+    hipLaunchKernelGGL((bwd_apply_kernel<T, 1>), grid, block, 0, st, gz, x, gamma, beta, mean, rstd, g, ws, gx);
+  } else {
+    hipLaunchKernelGGL((bwd_reduce_kernel<T, 0>), grid, block, 0, st, gz, x, gamma, beta, mean, rstd, g, ws);
+    hipLaunchKernelGGL((bwd_apply_kernel<T, 0>), grid, block, 0, st, gz, x, gamma, beta, mean, rstd, g, ws, gx);
+  }
+  hipLaunchKernelGGL(param_grad_kernel, dim3(C), block, 0, st, ws, g, dgamma, dbeta);
+}
 
 extern "C" int64_t amk_gnact_ws_floats(int N, int C, int64_t HW, int G) {
   if (N <= 0 || C <= 0 || HW <= 0 || G <= 0 || C % G != 0) return 0;
@@ -381,16 +452,9 @@ extern "C" int64_t amk_gnact_ws_floats(int N, int C, int64_t HW, int G) {
 extern "C" int amk_gnact_fwd(const float* x, const float* gamma, const float* beta, int N, int C, int64_t HW, int G,
                              float eps, int act, float* z, float* mean, float* rstd, float* ws, void* stream) {
   AMK_CHECK_ARG(x && gamma && beta && z && mean && rstd && ws, "amk_gnact_fwd: null pointer");
-  AMK_GN_SHAPE("amk_gnact_fwd");
+  AMK_GN_SHAPE("amk_gnact_fwd", 4);
   AMK_CHECK_ARG(a16(x) && a16(z), "amk_gnact_fwd: x and z must be 16-byte aligned");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const Geo g = make_geo(N, C, HW, G);
-  const dim3 grid((unsigned)grid_of(N, C, HW, G)), block(BLOCK);
-  hipLaunchKernelGGL(stats_kernel, grid, block, 0, st, x, g, ws);
-  if (act == 1)
-    hipLaunchKernelGGL(fwd_apply_kernel<1>, grid, block, 0, st, x, gamma, beta, g, ws, eps, z, mean, rstd);
-  else
-    hipLaunchKernelGGL(fwd_apply_kernel<0>, grid, block, 0, st, x, gamma, beta, g, ws, eps, z, mean, rstd);
+  launch_fwd<float>(x, gamma, beta, N, C, HW, G, eps, act, z, mean, rstd, ws, static_cast<hipStream_t>(stream));
   AMK_CHECK_LAUNCH("amk_gnact_fwd");
   return AMK_OK;
 }
@@ -400,19 +464,40 @@ extern "C" int amk_gnact_bwd(const float* gz, const float* x, const float* gamma
                              float* gx, float* dgamma, float* dbeta, float* ws, void* stream) {
   AMK_CHECK_ARG(gz && x && gamma && beta && mean && rstd && gx && dgamma && dbeta && ws,
                 "amk_gnact_bwd: null pointer");
-  AMK_GN_SHAPE("amk_gnact_bwd");
+  AMK_GN_SHAPE("amk_gnact_bwd", 4);
   AMK_CHECK_ARG(a16(gz) && a16(x) && a16(gx), "amk_gnact_bwd: gz, x and gx must be 16-byte aligned");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const Geo g = make_geo(N, C, HW, G);
-  const dim3 grid((unsigned)grid_of(N, C, HW, G)), block(BLOCK);
-  if (act == 1) {
-    hipLaunchKernelGGL(bwd_reduce_kernel<1>, grid, block, 0, st, gz, x, gamma, beta, mean, rstd, g, ws);
-    hipLaunchKernelGGL(bwd_apply_kernel<1>, grid, block, 0, st, gz, x, gamma, beta, mean, rstd, g, ws, gx);
-  } else {
-    hipLaunchKernelGGL(bwd_reduce_kernel<0>, grid, block, 0, st, gz, x, gamma, beta, mean, rstd, g, ws);
-    hipLaunchKernelGGL(bwd_apply_kernel<0>, grid, block, 0, st, gz, x, gamma, beta, mean, rstd, g, ws, gx);
-  }
-  hipLaunchKernelGGL(param_grad_kernel, dim3(C), block, 0, st, ws, g, dgamma, dbeta);
+  launch_bwd<float>(gz, x, gamma, beta, mean, rstd, N, C, HW, G, act, gx, dgamma, dbeta, ws,
+                    static_cast<hipStream_t>(stream));
   AMK_CHECK_LAUNCH("amk_gnact_bwd");
+  return AMK_OK;
+}
+
+// ---------------------------------------------------------------- bf16 x, z, gz, gx
+extern "C" int64_t amk_gnact_bf16_ws_floats(int N, int C, int64_t HW, int G) {
+  if (N <= 0 || C <= 0 || HW <= 0 || G <= 0 || C % G != 0) return 0;
+  return (int64_t)N * C * make_geo(N, C, HW, G, 8).Q * 2;
+}
+
+extern "C" int amk_gnact_bf16_fwd(const void* x, const float* gamma, const float* beta, int N, int C, int64_t HW, int G,
+                                  float eps, int act, void* z, float* mean, float* rstd, float* ws, void* stream) {
+  AMK_CHECK_ARG(x && gamma && beta && z && mean && rstd && ws, "amk_gnact_bf16_fwd: null pointer");
+  AMK_GN_SHAPE("amk_gnact_bf16_fwd", 8);
+  AMK_CHECK_ARG(a16(x) && a16(z), "amk_gnact_bf16_fwd: x and z must be 16-byte aligned");
+  launch_fwd<__bf16>(static_cast<const __bf16*>(x), gamma, beta, N, C, HW, G, eps, act, static_cast<__bf16*>(z), mean,
+                     rstd, ws, static_cast<hipStream_t>(stream));
+  AMK_CHECK_LAUNCH("amk_gnact_bf16_fwd");
+  return AMK_OK;
+}
+
+extern "C" int amk_gnact_bf16_bwd(const void* gz, const void* x, const float* gamma, const float* beta,
+                                  const float* mean, const float* rstd, int N, int C, int64_t HW, int G, int act,
+                                  void* gx, float* dgamma, float* dbeta, float* ws, void* stream) {
+  AMK_CHECK_ARG(gz && x && gamma && beta && mean && rstd && gx && dgamma && dbeta && ws,
+                "amk_gnact_bf16_bwd: null pointer");
+  AMK_GN_SHAPE("amk_gnact_bf16_bwd", 8);
+  AMK_CHECK_ARG(a16(gz) && a16(x) && a16(gx), "amk_gnact_bf16_bwd: gz, x and gx must be 16-byte aligned");
+  launch_bwd<__bf16>(static_cast<const __bf16*>(gz), static_cast<const __bf16*>(x), gamma, beta, mean, rstd, N, C, HW,
+                     G, act, static_cast<__bf16*>(gx), dgamma, dbeta, ws, static_cast<hipStream_t>(stream));
+  AMK_CHECK_LAUNCH("amk_gnact_bf16_bwd");
   return AMK_OK;
 }

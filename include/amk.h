@@ -700,6 +700,21 @@ int amk_gnact_bwd(const float* gz, const float* x, const float* gamma, const flo
                   const float* rstd, int N, int C, int64_t HW, int G, int act, float* gx, float* dgamma, float* dbeta,
                   float* ws, void* stream);
 
+/* The same pair under bf16 autocast (csrc/gn_act.hip, the same kernels on bf16 elements): x, z, gz and gx are bf16
+ * (const void* / void*), gamma, beta, mean, rstd, dgamma and dbeta f32.  Replaces what models/vqgan.py:11-22 runs as under
+ * torch.autocast(dtype=bfloat16): the cast of the convolution's bf16 output to f32, the f32 GroupNorm, sigmoid and mul,
+ * and the cast back to bf16 at the next convolution's input.  The bf16 values of x and gz are widened to f32 on the load;
+ * statistics, y, sigma, swish' and every sum are the f32 arithmetic of amk_gnact_*; z and gx are rounded to bf16 once,
+ * to nearest even, on the store.  16-byte accesses hold 8 elements: a plane is walked as a scalar head of up to 7
+ * elements, an aligned body and a scalar tail.  The same refusals and return codes, launches and reproducibility as
+ * amk_gnact_*; ws holds amk_gnact_bf16_ws_floats(N, C, HW, G) floats. */
+int64_t amk_gnact_bf16_ws_floats(int N, int C, int64_t HW, int G);
+int amk_gnact_bf16_fwd(const void* x, const float* gamma, const float* beta, int N, int C, int64_t HW, int G, float eps,
+                       int act, void* z, float* mean, float* rstd, float* ws, void* stream);
+int amk_gnact_bf16_bwd(const void* gz, const void* x, const float* gamma, const float* beta, const float* mean,
+                       const float* rstd, int N, int C, int64_t HW, int G, int act, void* gx, float* dgamma, float* dbeta,
+                       float* ws, void* stream);
+
 /* --------------------------------------------------------------------------
  * Masked-token loss head (csrc/ce_head.hip): logits + cross-entropy on the rows that count, f32 on
  * v_mfma_f32_32x32x2_f32.  Replaces decoder.linear(...) followed by F.cross_entropy(logits.transpose(1, 2), tgt,

@@ -2,7 +2,12 @@
 against csrc/gn_act.hip (ops.group_norm_act), forward + backward, interleaved round by round in one process so both arms
 see the same warm chip.  Per arm: median ms with the spread over the rounds, GB/s on the algorithmic bytes (five array
 passes: x -> z, then x, gz -> gx) against the rate of a device copy measured in the same run, and the peak memory above the
-inputs (x, gz and the parameters) during one forward + backward."""
+inputs (x, gz and the parameters) during one forward + backward.
+
+--autocast bf16: the same under torch.autocast(dtype=bfloat16) on a bf16 x and gz, as the layers sit between two convolutions
+there: the module path (the cast to f32 that autocast puts in front of group_norm, the f32 norm, sigmoid and mul, and the cast
+of the result to bf16 that the next convolution makes) against amk_gnact_bf16_* (AMK_GN_ACT_BF16); the algorithmic bytes are
+the same five passes at 2 bytes per element."""
 import argparse
 import os
 import statistics
@@ -20,17 +25,20 @@ SHAPES = [(128, 256), (128, 128), (256, 64), (256, 32), (512, 16)]   # (C, H = W
 PASSES = 5
 
 
-def make(C, H, B, dev, fused):
+def make(C, H, B, dev, fused, bf16=False):
     gn = nn.GroupNorm(32, C, eps=1e-6).to(dev)
-    x = torch.randn(B, C, H, H, device=dev).requires_grad_()
-    gz = torch.randn(B, C, H, H, device=dev)
+    dtype = torch.bfloat16 if bf16 else torch.float32
+    x = torch.randn(B, C, H, H, device=dev).to(dtype).requires_grad_()
+    gz = torch.randn(B, C, H, H, device=dev).to(dtype)
 
     def step():
-        if fused:
-            z = ops.group_norm_act(x, gn, 1)
-        else:
-            y = gn(x)
-            z = y * torch.sigmoid(y)
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=bf16):
+            if fused:
+                z = ops.group_norm_act(x, gn, 1)
+            else:
+                y = gn(x)
+                z = (y * torch.sigmoid(y)).to(dtype)       # under autocast: the cast the next convolution makes
+        assert z.dtype == dtype and ("GNAct" in type(z.grad_fn).__name__) == fused
         z.backward(gz)
         x.grad = gn.weight.grad = gn.bias.grad = None
 
@@ -71,21 +79,25 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--autocast", choices=["bf16"], default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("kbench_gn_act needs an MI355X; no device is visible")
     assert ops.GN_ACT or os.environ.get("AMK_GN_ACT") is None, "AMK_GN_ACT=0 would time the modules twice"
     ops.GN_ACT = True
+    bf16 = args.autocast == "bf16"
+    assert not bf16 or ops.GN_ACT_BF16 or os.environ.get("AMK_GN_ACT_BF16") is None, "AMK_GN_ACT_BF16=0 would time the modules twice"
+    ops.GN_ACT_BF16 = True
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     peak = copy_rate(dev, args.iters)
-    print(f"batch {args.batch}, forward + backward, median [min, max] of {args.rounds} interleaved rounds x {args.iters} calls; "
+    print(f"batch {args.batch}, {'bf16 autocast' if bf16 else 'f32'}, forward + backward, median [min, max] of {args.rounds} interleaved rounds x {args.iters} calls; "
           f"device copy {peak / 1e9:.0f} GB/s")
     print(f"{'layer':>14} {'modules ms':>24} {'fused ms':>24} {'speedup':>8} {'mod GB/s':>9} {'fused GB/s':>10} {'of copy':>8} "
           f"{'mod MiB':>8} {'fused MiB':>9}")
     tot = {False: 0.0, True: 0.0}
     for C, H in SHAPES:
-        arms = {f: make(C, H, args.batch, dev, f) for f in (False, True)}
+        arms = {f: make(C, H, args.batch, dev, f, bf16) for f in (False, True)}
         res = {False: [], True: []}
         for r in range(args.rounds + 1):
             for f in (False, True):
@@ -93,7 +105,7 @@ def main():
                 if r:   # round 0 warms up
                     res[f].append(ms)
         mem = {f: peak_above_inputs(arms[f]) for f in (False, True)}
-        nbytes = PASSES * args.batch * C * H * H * 4
+        nbytes = PASSES * args.batch * C * H * H * (2 if bf16 else 4)
         med = {f: statistics.median(res[f]) for f in res}
         fmt = lambda f: f"{med[f]:8.4f} [{min(res[f]):.4f}, {max(res[f]):.4f}]"  # noqa: E731
         gbs = {f: nbytes / (med[f] * 1e-3) / 1e9 for f in res}

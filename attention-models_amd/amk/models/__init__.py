@@ -1,10 +1,13 @@
-"""Same export list as the reference's ``models`` package (models/__init__.py:1-14) for the
-classes on the hot path and their scaffolding."""
+"""The export list of the reference's ``models`` package (models/__init__.py:1-14), all fourteen names, and the
+scaffolding around them."""
 from .attention import AgentAttention, SoftmaxAttention, SwitchHeadAttention
 from .model_factory import build_model
 from .moe import MoELayer
 from .maskgit import BiDirectionalTransformer, MaskGitTransformer
 from .muse import MUSE, BidirectionalDecoder
+from .parti import Parti
+from .positional_encoding import AbsolutePositionalEmbedding, PositionalEncoding
+from .transformer import Transformer
 from .vit import ViT
 from .vit_moe import ViTMoE
 from .vitvqgan import Codebook, ViTVQGAN
@@ -12,4 +15,5 @@ from . import vqgan  # the conv VQGAN's own codebook stays vqgan.Codebook (model
 from .vqgan import VQGAN
 
 __all__ = ["SoftmaxAttention", "AgentAttention", "SwitchHeadAttention", "MoELayer", "Codebook", "ViTVQGAN", "VQGAN",
-           "ViT", "ViTMoE", "MUSE", "BidirectionalDecoder", "MaskGitTransformer", "BiDirectionalTransformer", "build_model"]
+           "ViT", "ViTMoE", "MUSE", "BidirectionalDecoder", "MaskGitTransformer", "BiDirectionalTransformer", "build_model",
+           "Parti", "Transformer", "PositionalEncoding", "AbsolutePositionalEmbedding"]

@@ -1,6 +1,6 @@
 """Pre-LN encoder / decoder stacks around SoftmaxAttention (scaffolding of SURVEY.md section 8
-a15; reference: models/transformer.py:11-135).  Plain PyTorch except for the attention cores.
-The seq2seq ``Transformer`` toy of the reference file is out of scope.
+a15; reference: models/transformer.py:11-135), and the seq2seq ``Transformer`` on top of them (reference :138-228).
+Plain PyTorch except for the attention cores, the LayerNorms and the Linear layers.
 """
 import torch
 import torch.nn as nn
@@ -8,6 +8,8 @@ import torch.nn.functional as F
 
 from .. import ops
 from .attention import SoftmaxAttention
+from .layers import Linear
+from .positional_encoding import PositionalEncoding
 
 
 class LayerNorm(nn.Module):
@@ -111,3 +113,55 @@ class Decoder(nn.Module):
         for layer in self.layers:
             out = layer(out, context, context_mask=context_mask, causal_mask=causal_mask)
         return out
+
+
+class Transformer(nn.Module):
+    """Encoder-decoder over token ids (reference: models/transformer.py:138-228): embeddings + sinusoidal positions,
+    the encoder over the source, the decoder over the target with the causal mask and an all-true context mask, a Linear
+    onto ``n_classes``.  The masks are built on the input's device (the reference builds them on the CPU and therefore
+    only runs there)."""
+
+    def __init__(self, dim, vocab_size=1000, n_heads=8, d_head=64, enc_depth=6, dec_depth=6, n_classes=None):
+        super().__init__()
+        self.enc_input_proj = nn.Embedding(vocab_size, dim)
+        self.dec_input_proj = nn.Embedding(vocab_size, dim)
+        self.pos_enc = PositionalEncoding(dim)
+        self.enc_init_norm = LayerNorm(dim)
+        self.encoder = Encoder(dim=dim, n_heads=n_heads, d_head=d_head, depth=enc_depth)
+        self.enc_final_norm = LayerNorm(dim)
+
+        self.dec_init_norm = LayerNorm(dim)
+        self.decoder = Decoder(dim=dim, n_heads=n_heads, d_head=d_head, depth=dec_depth)
+        self.dec_final_norm = LayerNorm(dim)
+        self.linear = Linear(dim, n_classes)
+
+    def get_decoder_mask(self, src_seq, tgt_seq):
+        """(context mask (B, S), all true: no PAD handling in the reference either; causal mask (T, T), True = masked)."""
+        t = tgt_seq.shape[1]
+        context_mask = torch.ones(src_seq.shape, dtype=torch.bool, device=src_seq.device)
+        return context_mask, ops.causal_mask(t, t, tgt_seq.device)
+
+    def forward(self, src_seq, tgt_seq):
+        context_mask, causal_mask = self.get_decoder_mask(src_seq, tgt_seq)
+        src = self.enc_init_norm(self.pos_enc(self.enc_input_proj(src_seq)))
+        context = self.enc_final_norm(self.encoder(src, context_mask=context_mask))
+        dec_in = self.dec_init_norm(self.pos_enc(self.dec_input_proj(tgt_seq)))
+        dec_out = self.decoder(dec_in=dec_in, context=context, context_mask=context_mask, causal_mask=causal_mask)
+        return self.linear(self.dec_final_norm(dec_out))
+
+    @torch.no_grad()
+    def generate(self, src_seq, max_len=None):
+        """Sampling as the reference writes it (:176-202): no norms, no masks, the whole prefix through the decoder at
+        every step, Gumbel-softmax sampling, stop when the FIRST sequence draws the end token 2.  max_len (an addition):
+        at most that many tokens are appended; None = the reference's unbounded loop."""
+        context = self.encoder(self.pos_enc(self.enc_input_proj(src_seq)))
+        end_token = 2
+        out_seq = torch.ones((src_seq.shape[0], 1), dtype=torch.long, device=src_seq.device)
+        while max_len is None or out_seq.shape[1] - 1 < max_len:
+            dec_out = self.decoder(dec_in=self.pos_enc(self.dec_input_proj(out_seq)), context=context)
+            logits = self.linear(dec_out)
+            last_token = F.gumbel_softmax(logits[:, -1, :], tau=1, hard=False).argmax(dim=-1)
+            if last_token[0] == end_token:
+                break
+            out_seq = torch.cat((out_seq, last_token.unsqueeze(1)), dim=1)
+        return out_seq

@@ -109,6 +109,23 @@ def _mask_u8(mask, shape, what):
     return m.to(torch.uint8).contiguous()
 
 
+# The reference's models build one causal mask only, torch.ones(I, J).triu(J - I + 1) (models/parti.py:111-112,
+# models/transformer.py:167-168): key j of query i is masked iff j >= i + (J - I + 1).  causal_mask returns it, one
+# tensor per (I, J, device), so that a model does not rebuild it every step.
+_causal_masks = {}
+
+
+def causal_mask(I, J, device):
+    """The reference's causal mask, bool (I, J), True = masked: torch.ones(I, J).triu(J - I + 1).  Cached per
+    (I, J, device); do not write to it."""
+    key = (int(I), int(J), torch.device(device))
+    m = _causal_masks.get(key)
+    if m is None:
+        m = torch.ones((key[0], key[1]), dtype=torch.bool, device=key[2]).triu(key[1] - key[0] + 1)
+        _causal_masks[key] = m
+    return m
+
+
 # Forward path of the attention core (head dim 64, f32): "f32" = exact-f32 MFMA (v_mfma_f32_32x32x2_f32); "bf16x6" = the
 # same algorithm with every product formed from three-way bf16 splits of its f32 operands (six exact partial products,
 # f32 accumulation, csrc/attn_fwd_x6.hip): f32-level error at 2.6x the matrix rate, for a pre-pass that splits K and V

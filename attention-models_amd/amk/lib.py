@@ -124,10 +124,14 @@ SIGNATURES = {
     "amk_ce_head_bwd_ws_bytes": (_L, [_L, _I, _I]),
     "amk_ce_head_fwd": (_I, [_P, _L, _P, _L, _P, _L, _L, _I, _I, _P, _P, _P, _P, _P, _L, _P]),
     "amk_ce_head_bwd": (_I, [_P, _L, _P, _L, _P, _L, _L, _I, _I, _P, _P, _P, _P, _P, _L, _P, _L, _P, _L, _P]),
+    "amk_ce_head_bias_fwd": (_I, [_P, _L, _P, _L, _P, _P, _L, _L, _I, _I, _P, _P, _P, _P, _P, _L, _P]),
+    "amk_ce_head_bias_bwd": (_I, [_P, _L, _P, _L, _P, _P, _L, _L, _I, _I, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _L, _P]),
     "amk_ce_head_bf16_fwd_ws_bytes": (_L, [_L, _I, _I]),
     "amk_ce_head_bf16_bwd_ws_bytes": (_L, [_L, _I, _I]),
     "amk_ce_head_bf16_fwd": (_I, [_P, _L, _P, _L, _P, _L, _L, _I, _I, _P, _P, _P, _P, _P, _L, _P]),
     "amk_ce_head_bf16_bwd": (_I, [_P, _L, _P, _L, _P, _L, _L, _I, _I, _P, _P, _P, _P, _P, _L, _P, _L, _P, _L, _P]),
+    "amk_ce_head_bias_bf16_fwd": (_I, [_P, _L, _P, _L, _P, _P, _L, _L, _I, _I, _P, _P, _P, _P, _P, _L, _P]),
+    "amk_ce_head_bias_bf16_bwd": (_I, [_P, _L, _P, _L, _P, _P, _L, _L, _I, _I, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _L, _P]),
     "amk_grouped_gemm_nt_bf16": (_I, [_P, _L, _I, _P, _P, _P, _P, _L, _I, _I, _I, _P, _P]),
     "amk_grouped_gemm_nn_bf16": (_I, [_P, _L, _I, _P, _P, _P, _P, _L, _I, _I, _I, _P, _P]),
     "amk_grouped_gemm_wgrad_bf16": (_I, [_P, _L, _I, _P, _L, _I, _P, _P, _P, _L, _I, _I, _I, _P, _P, _P]),

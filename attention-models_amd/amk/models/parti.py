@@ -36,7 +36,7 @@ class Parti(nn.Module):
         self.transformer_decoder = Decoder(dim, n_heads, d_head, depth)
         self.init_norm = LayerNorm(dim)
         self.final_norm = LayerNorm(dim)
-        self.to_logits = Linear(dim, codebook_size)   # (with a bias: the fused loss head of csrc/ce_head.hip takes none)
+        self.to_logits = Linear(dim, codebook_size)
 
         self.vq.requires_grad_(False)
 
@@ -58,8 +58,16 @@ class Parti(nn.Module):
         t = x.shape[1]
         x = self.init_norm(x)
         out = self.transformer_decoder(dec_in=x, context=text_embeds, causal_mask=ops.causal_mask(t, t, x.device))
+        if ops.ce_head_ok(out, self.to_logits.weight, self.to_logits.bias):
+            return self.loss_from_hidden(out, labels)
         logits = self.to_logits(self.final_norm(out))
         return F.cross_entropy(logits.transpose(1, 2), labels)
+
+    def loss_from_hidden(self, hidden, labels):
+        """The training loss from the decoder's output without the logits in memory: final_norm, then the fused logits +
+        bias + cross-entropy head (csrc/ce_head.hip, csrc/ce_head_bf16.hip under bf16 autocast)."""
+        return ops.linear_cross_entropy(self.final_norm(hidden), self.to_logits.weight, labels, -100,
+                                        bias=self.to_logits.bias)
 
     @torch.no_grad()
     def generate(self, text_hidden, gumbel=None, trace=None):

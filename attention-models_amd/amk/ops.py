@@ -2290,6 +2290,10 @@ def group_norm_act(x, gn, act):
 # Measured at the Muse head (8192 rows, 8192 words, dim 1024, cosine-schedule targets; tools/kbench_ce_head.py,
 # profiles/kbench_ce_head.log): 3.89 ms against 22.45 ms forward + backward, 336 MB against 805 MB of peak memory above the
 # inputs; bench.py --model muse 195.4 against 215.6 ms per step.  So the switch ships on.  Read once per process.
+# With a bias (Parti's to_logits; amk_ce_head_bias_*): at Parti's head (8192 rows x 8192 words x 512, every row valid;
+# tools/kbench_ce_head.py --bias, profiles/kbench_ce_head_bias.log) 3.32 ms against 21.07 ms in f32 and, under bf16
+# autocast (profiles/kbench_ce_head_bias_bf16.log), 0.88 ms against 18.40 ms; the Parti step (tools/kbench_parti.py, arms
+# alternating, profiles/kbench_parti_ce_head[_bf16].log) 21.8 against 40.3 ms in f32 and 12.5 against 29.3 ms under autocast.
 CE_HEAD = os.environ.get("AMK_CE_HEAD", "1") != "0"
 
 
@@ -2306,10 +2310,13 @@ def _bf16_autocast():
     return torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16
 
 
-def ce_head_ok(x, weight):
+def ce_head_ok(x, weight, bias=None):
     """The models' gate.  Without autocast: the switch is on, f32 HIP tensors, K a multiple of 4.  Under bf16 autocast:
-    both switches are on, HIP tensors, an f32 master weight, K a multiple of 8 (the bf16 head)."""
+    both switches are on, HIP tensors, an f32 master weight, K a multiple of 8 (the bf16 head).  A bias must be an f32
+    HIP tensor of shape (V,) (it stays f32 under autocast)."""
     if not (CE_HEAD and x.is_cuda and weight.dtype == torch.float32 and x.numel() > 0):
+        return False
+    if bias is not None and not (bias.is_cuda and bias.dtype == torch.float32 and bias.shape == (weight.shape[0],)):
         return False
     if torch.is_autocast_enabled():
         return (CE_HEAD_BF16 and _bf16_autocast() and x.dtype in (torch.float32, torch.bfloat16)
@@ -2385,6 +2392,157 @@ class _LinearCrossEntropy(torch.autograd.Function):
         return dx.view(ctx.x_shape), dw, None, None
 
 
+def _bias_view(bias, V):
+    """bias (V,) f32 as the kernels take it: contiguous and 16-byte aligned (copied when it is not)."""
+    if bias.dtype != torch.float32 or bias.shape != (V,):
+        raise RuntimeError(f"linear_cross_entropy: bias must be f32 of shape ({V},); got {bias.dtype} {tuple(bias.shape)}")
+    b = bias.detach()
+    if b.stride(0) != 1 or b.data_ptr() % 16:
+        b = b.contiguous()
+        if b.data_ptr() % 16:
+            b = b.clone()
+    return b
+
+
+def _claim_vec(p, V):
+    """_claim for a (V,) f32 gradient the kernels write directly: (reducer, view) or (None, None)."""
+    r, v = _claim(p)
+    if v is not None and (v.dtype != torch.float32 or v.shape != (V,) or v.stride(0) != 1 or v.data_ptr() % 16):
+        return None, None   # (not reached with the reducer's views: ALIGN-ed, contiguous)
+    return r, v
+
+
+class _LinearCrossEntropyBias(torch.autograd.Function):
+    """_LinearCrossEntropy with z = x W^T + b (amk_ce_head_bias_fwd / _bwd): the bias is the first term of each logit's
+    chain; db = the column sums of the G that dw reads, f32, into the reducer's bucket when it can be claimed."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, target, ignore_index):
+        K = x.shape[-1]
+        x2 = _row_major_view(x.reshape(-1, K))
+        w2 = _row_major_view(weight)
+        t = target.reshape(-1).contiguous()
+        M, V = x2.shape[0], w2.shape[0]
+        if t.shape[0] != M or w2.shape[1] != K:
+            raise RuntimeError(f"linear_cross_entropy: x {tuple(x.shape)}, weight {tuple(weight.shape)}, target "
+                               f"{tuple(target.shape)} do not fit")
+        b1 = _bias_view(bias, V)
+        L = _lib.load()
+        dev = x2.device
+        nbytes = L.amk_ce_head_fwd_ws_bytes(M, V, K)
+        ws = torch.empty(max(nbytes // 4, 4), device=dev, dtype=torch.float32)
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        lse = torch.empty(M, device=dev, dtype=torch.float32)
+        rows = torch.empty(M, device=dev, dtype=torch.int32)
+        count = torch.empty(1, device=dev, dtype=torch.int32)
+        with _timed(f"ce_head_bias_fwd M{M} V{V} K{K}"):
+            _lib.check(L.amk_ce_head_bias_fwd(_ptr(x2), x2.stride(0), _ptr(w2), w2.stride(0), _ptr(b1), _ptr(t),
+                                              int(ignore_index), M, V, K, _ptr(loss), _ptr(lse), _ptr(rows), _ptr(count),
+                                              _ptr(ws), nbytes, _stream()), "amk_ce_head_bias_fwd")
+        ctx.save_for_backward(x2, w2, b1, t, lse, rows, count)
+        ctx.ignore_index = int(ignore_index)
+        ctx.x_shape = x.shape
+        ctx.weight, ctx.bias = weight, bias
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_loss):
+        x2, w2, b1, t, lse, rows, count = ctx.saved_tensors
+        M, K = x2.shape
+        V = w2.shape[0]
+        L = _lib.load()
+        dev = x2.device
+        d = d_loss.reshape(1).to(torch.float32).contiguous()   # stays on the device
+        dx = torch.empty(M, K, device=dev, dtype=torch.float32)
+        wr, wv = _claim(ctx.weight) if ctx.needs_input_grad[1] else (None, None)
+        if wv is not None and (wv.stride(-1) != 1 or wv.data_ptr() % 16 or wv.shape != w2.shape or wv.stride(0) % 4):
+            wr, wv = None, None   # (not reached with the reducer's views: ALIGN-ed, contiguous)
+        dw = wv if wv is not None else torch.empty(V, K, device=dev, dtype=torch.float32)
+        br, bv = _claim_vec(ctx.bias, V) if ctx.needs_input_grad[2] else (None, None)
+        db = bv if bv is not None else torch.empty(V, device=dev, dtype=torch.float32)
+        nbytes = L.amk_ce_head_bwd_ws_bytes(M, V, K)
+        ws = torch.empty(max(nbytes // 4, 4), device=dev, dtype=torch.float32)
+        with _timed(f"ce_head_bias_bwd M{M} V{V} K{K}"):
+            _lib.check(L.amk_ce_head_bias_bwd(_ptr(x2), x2.stride(0), _ptr(w2), w2.stride(0), _ptr(b1), _ptr(t),
+                                              ctx.ignore_index, M, V, K, _ptr(d), _ptr(lse), _ptr(rows), _ptr(count),
+                                              _ptr(dx), dx.stride(0), _ptr(dw), dw.stride(0), _ptr(db), _ptr(ws), nbytes,
+                                              _stream()), "amk_ce_head_bias_bwd")
+        if wv is not None:
+            wr.wrote(ctx.weight)
+            dw = None
+        if bv is not None:
+            br.wrote(ctx.bias)
+            db = None
+        return dx.view(ctx.x_shape), dw, db, None, None
+
+
+class _LinearCrossEntropyBiasBF16(torch.autograd.Function):
+    """_LinearCrossEntropyBF16 with z = x W^T + b (amk_ce_head_bias_bf16_fwd / _bwd): the bias stays the f32 master, db in
+    f32."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, target, ignore_index):
+        K = x.shape[-1]
+        x16 = _row_major_view(x.reshape(-1, K).to(torch.bfloat16), 8)
+        w16 = _row_major_view(_w16(weight), 8)
+        t = target.reshape(-1).contiguous()
+        M, V = x16.shape[0], w16.shape[0]
+        if t.shape[0] != M or w16.shape[1] != K:
+            raise RuntimeError(f"linear_cross_entropy: x {tuple(x.shape)}, weight {tuple(weight.shape)}, target "
+                               f"{tuple(target.shape)} do not fit")
+        b1 = _bias_view(bias, V)
+        L = _lib.load()
+        dev = x16.device
+        nbytes = L.amk_ce_head_bf16_fwd_ws_bytes(M, V, K)
+        ws = torch.empty(max(nbytes // 4, 4), device=dev, dtype=torch.float32)
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        lse = torch.empty(M, device=dev, dtype=torch.float32)
+        rows = torch.empty(M, device=dev, dtype=torch.int32)
+        count = torch.empty(1, device=dev, dtype=torch.int32)
+        with _timed(f"bf16_ce_head_bias_fwd M{M} V{V} K{K}"):
+            _lib.check(L.amk_ce_head_bias_bf16_fwd(_ptr(x16), x16.stride(0), _ptr(w16), w16.stride(0), _ptr(b1), _ptr(t),
+                                                   int(ignore_index), M, V, K, _ptr(loss), _ptr(lse), _ptr(rows),
+                                                   _ptr(count), _ptr(ws), nbytes, _stream()), "amk_ce_head_bias_bf16_fwd")
+        ctx.save_for_backward(x16, w16, b1, t, lse, rows, count)
+        ctx.ignore_index = int(ignore_index)
+        ctx.x_shape, ctx.x_dtype = x.shape, x.dtype
+        ctx.weight, ctx.bias = weight, bias
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_loss):
+        x16, w16, b1, t, lse, rows, count = ctx.saved_tensors
+        M, K = x16.shape
+        V = w16.shape[0]
+        L = _lib.load()
+        dev = x16.device
+        d = d_loss.reshape(1).to(torch.float32).contiguous()   # stays on the device
+        dx = torch.empty(M, K, device=dev, dtype=torch.bfloat16)
+        wr, wv = _claim(ctx.weight) if ctx.needs_input_grad[1] else (None, None)
+        if wv is not None and (wv.stride(-1) != 1 or wv.data_ptr() % 16 or wv.shape != w16.shape or wv.stride(0) % 8
+                               or wv.dtype != torch.float32):
+            wr, wv = None, None   # (not reached with the reducer's views: ALIGN-ed, contiguous)
+        dw = wv if wv is not None else torch.empty(V, K, device=dev, dtype=torch.float32)
+        br, bv = _claim_vec(ctx.bias, V) if ctx.needs_input_grad[2] else (None, None)
+        db = bv if bv is not None else torch.empty(V, device=dev, dtype=torch.float32)
+        nbytes = L.amk_ce_head_bf16_bwd_ws_bytes(M, V, K)
+        ws = torch.empty(max(nbytes // 2, 8), device=dev, dtype=torch.bfloat16)
+        with _timed(f"bf16_ce_head_bias_bwd M{M} V{V} K{K}"):
+            _lib.check(L.amk_ce_head_bias_bf16_bwd(_ptr(x16), x16.stride(0), _ptr(w16), w16.stride(0), _ptr(b1), _ptr(t),
+                                                   ctx.ignore_index, M, V, K, _ptr(d), _ptr(lse), _ptr(rows), _ptr(count),
+                                                   _ptr(dx), dx.stride(0), _ptr(dw), dw.stride(0), _ptr(db), _ptr(ws),
+                                                   nbytes, _stream()), "amk_ce_head_bias_bf16_bwd")
+        if wv is not None:
+            wr.wrote(ctx.weight)
+            dw = None
+        if bv is not None:
+            br.wrote(ctx.bias)
+            db = None
+        return dx.view(ctx.x_shape).to(ctx.x_dtype), dw, db, None, None
+
+
 class _LinearCrossEntropyBF16(torch.autograd.Function):
     """_LinearCrossEntropy under bf16 autocast (csrc/ce_head_bf16.hip): x cast to bf16 if it arrives in f32, the weight
     through _w16 (the optimizer's bf16 shadow when it is current); loss and lse in f32, dx in x's dtype, dw in f32 --
@@ -2445,17 +2603,24 @@ class _LinearCrossEntropyBF16(torch.autograd.Function):
         return dx.view(ctx.x_shape).to(ctx.x_dtype), dw, None, None
 
 
-def linear_cross_entropy(x, weight, target, ignore_index=-100):
-    """F.cross_entropy(F.linear(x, weight).flatten(0, -2), target.flatten(), ignore_index=ignore_index) as one op that
-    never writes the logits: x (..., K) f32, weight (V, K), target (...) int64 -> scalar f32 (mean over the rows whose
+def linear_cross_entropy(x, weight, target, ignore_index=-100, bias=None):
+    """F.cross_entropy(F.linear(x, weight, bias).flatten(0, -2), target.flatten(), ignore_index=ignore_index) as one op
+    that never writes the logits: x (..., K) f32, weight (V, K), bias None or (V,) f32 (it stays f32 under autocast; its
+    gradient is f32), target (...) int64 -> scalar f32 (mean over the rows whose
     target is not ignore_index; NaN when there is none).  Inside bf16 autocast: x f32 or bf16, weight the f32 master, the
     products on bf16 operands with the logits and the softmax in f32 (csrc/ce_head_bf16.hip).  A target outside [0, V) that is not ignore_index poisons the
     loss (NaN) instead of raising: raising would need the host to read device data.  Once differentiable."""
     bf16 = _bf16_autocast()
     _require_device(*((weight, target) if bf16 and x.is_cuda and x.dtype == torch.bfloat16 else (x, weight, target)))
+    if bias is not None:
+        _require_device(bias)
     if target.dtype != torch.int64:
         raise RuntimeError(f"linear_cross_entropy: target must be int64; got {target.dtype}")
     if bf16:   # bf16 operands (x cast, the weight's bf16 shadow), f32 loss, dx in x's dtype, dw in f32
         with torch.autocast("cuda", enabled=False):
+            if bias is not None:
+                return _LinearCrossEntropyBiasBF16.apply(x, weight, bias, target, ignore_index)
             return _LinearCrossEntropyBF16.apply(x, weight, target, ignore_index)
+    if bias is not None:
+        return _LinearCrossEntropyBias.apply(x, weight, bias, target, ignore_index)
     return _LinearCrossEntropy.apply(x, weight, target, ignore_index)

@@ -24,6 +24,16 @@
 //   ce_bwd_dw    : dw[v, :] = sum_i G[i, v] x[rows[i], :]    (contraction in ascending i, up to count rounded to 16).
 // Every grid is sized from M; a row tile that starts at or past count exits before any load.
 //
+// With a bias (amk_ce_head_bias_fwd / _bwd: the HAS_BIAS instantiations of ce_fwd and ce_bwd_g; the biasless ones are the
+// code they were): the accumulator of the logits tile is PRELOADED with b[v0 + 32 b + acc_row(r, hf)] instead of being
+// cleared, so z = b[v] + sum_k x w is one MFMA chain whose first term is the bias -- no VALU instruction per MFMA.  A word
+// at or past the end of the slice is not loaded, preloads 0 and becomes -inf / a zero of G as before: nothing at or past
+// b[V] is read.
+//   ce_bwd_db    : db[v] = sum_i G[i, v] over the compacted rows, the f32 G that dw reads.  A workgroup of 1024 threads
+//                  owns 32 columns: thread (column c = tid & 31, group q = tid >> 5) adds rows q, q + 32, q + 64, ... in
+//                  ascending order (ceil(count / 32) terms, f32), the 32 group sums of a column fold as a binary tree in
+//                  LDS (q += q + 16, then 8, 4, 2, 1).  No atomics; count == 0 writes zeros.  No workspace beyond G.
+//
 // A target that is neither ignore_index nor in [0, V) is never used as an index: its row is counted (count includes
 // it), its loss is NaN -- so the mean is NaN -- and it receives and gives no gradient (its G row is zero, its dx row is
 // zero); d_loss / count still divides by the count that includes it.
@@ -153,23 +163,59 @@ __global__ __launch_bounds__(SCAN) void ce_compact_kernel(const int64_t* __restr
   if (tid == 0) count[0] = base;
 }
 
+// acc[b][r] = bias[v0 + 32 b + acc_row(r, hf)]: the bias is the first term of the logits' MFMA chain.  A whole tile inside
+// the slice (a workgroup-uniform test) takes sixteen 16-byte loads (registers 4 g .. 4 g + 3 of a block are four
+// consecutive words; bias is 16-byte aligned and v0 a multiple of 128); the slice's last, partial tile loads word by word
+// under a predicate (a word at or past vend is not loaded and keeps 0): nothing at or past bias[vend] is read.
+__device__ __forceinline__ void preload_bias(const float* __restrict__ bias, int v0, int vend, int hf, f32x16 (&acc)[4]) {
+  if (v0 + TA <= vend) {
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const float4 q = *reinterpret_cast<const float4*>(bias + v0 + 32 * b + 8 * g + 4 * hf);
+        acc[b][4 * g] = q.x; acc[b][4 * g + 1] = q.y; acc[b][4 * g + 2] = q.z; acc[b][4 * g + 3] = q.w;
+      }
+  } else {
+    const float* bp = bias + v0 + 4 * hf;   // one base, constant offsets: the loads are predicated, not clamped
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int o = 32 * b + 8 * (r >> 2) + (r & 3);   // acc_row(r, hf) - 4 hf
+        float bv = 0.f;
+        if (v0 + 4 * hf + o < vend) bv = bp[o];
+        acc[b][r] = bv;
+      }
+  }
+}
+
 // ---------------------------------------------------------------------------------------
 // The logits tile shared by ce_fwd and ce_bwd_g: z^T for words [v0, v0 + 128) x the workgroup's 128 compacted rows.
+template <bool HAS_BIAS>
 __device__ __forceinline__ void logits_tile(const float* __restrict__ x, int64_t ldx, const float* __restrict__ w, int64_t ldw,
-                                            int K, int v0, int vend, const int* srow, float* As, float* Bs, f32x16 (&acc)[4]) {
+                                            int K, int v0, int vend, const int* srow, float* As, float* Bs, f32x16 (&acc)[4],
+                                            const float* __restrict__ bias) {
   auto wrow = [&](int c) -> const float* { return v0 + c < vend ? w + (int64_t)(v0 + c) * ldw : nullptr; };
   auto xrow = [&](int c) -> const float* { const int r = srow[c]; return r >= 0 ? x + (int64_t)r * ldx : nullptr; };
-  clear(acc);
+  if constexpr (HAS_BIAS) {
+    const int hf = (threadIdx.x & 63) >> 5;
+    preload_bias(bias, v0, vend, hf, acc);
+  } else {
+    clear(acc);
+  }
   product(K, As, Bs, acc,
           [&](int k0, Stage& s) { load_t(wrow, k0, K, s); }, [&](float* T, const Stage& s) { store_t(T, s); },
           [&](int k0, Stage& s) { load_t(xrow, k0, K, s); }, [&](float* T, const Stage& s) { store_t(T, s); });
 }
 
+template <bool HAS_BIAS>
 __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ w,
                                                      int64_t ldw, const int64_t* __restrict__ target, int V, int K,
                                                      int nsplit, int vper, const int32_t* __restrict__ rows,
                                                      const int32_t* __restrict__ count, float* __restrict__ pm,
-                                                     float* __restrict__ ps, float* __restrict__ pz) {
+                                                     float* __restrict__ ps, float* __restrict__ pz,
+                                                     const float* __restrict__ bias) {
   __shared__ __attribute__((aligned(16))) float As[BK * LD];
   __shared__ __attribute__((aligned(16))) float Bs[BK * LD];
   __shared__ int srow[TR];
@@ -190,7 +236,7 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ x
   bool found = false;
   f32x16 acc[4];
   for (int v0 = vbeg; v0 < vend; v0 += TA) {
-    logits_tile(x, ldx, w, ldw, K, v0, vend, srow, As, Bs, acc);
+    logits_tile<HAS_BIAS>(x, ldx, w, ldw, K, v0, vend, srow, As, Bs, acc, bias);
     float tmax = -INFINITY;
 #pragma unroll
     for (int b = 0; b < 4; ++b)
@@ -261,11 +307,12 @@ __global__ __launch_bounds__(SCAN) void ce_finalize_kernel(const float* __restri
 }
 
 // ---------------------------------------------------------------------------------------
+template <bool HAS_BIAS>
 __global__ __launch_bounds__(256) void ce_bwd_g_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ w,
                                                        int64_t ldw, const int64_t* __restrict__ target, int V, int K, int nvt,
                                                        const float* __restrict__ d_loss, const float* __restrict__ lse,
                                                        const int32_t* __restrict__ rows, const int32_t* __restrict__ count,
-                                                       float* __restrict__ G, int64_t ldg) {
+                                                       float* __restrict__ G, int64_t ldg, const float* __restrict__ bias) {
   __shared__ __attribute__((aligned(16))) float As[BK * LD];
   __shared__ __attribute__((aligned(16))) float Bs[BK * LD];
   __shared__ int srow[TR];
@@ -278,7 +325,7 @@ __global__ __launch_bounds__(256) void ce_bwd_g_kernel(const float* __restrict__
   if (tid < TR) srow[tid] = r0 + tid < cnt ? rows[r0 + tid] : -1;
   __syncthreads();
   f32x16 acc[4];
-  logits_tile(x, ldx, w, ldw, K, v0, V, srow, As, Bs, acc);
+  logits_tile<HAS_BIAS>(x, ldx, w, ldw, K, v0, V, srow, As, Bs, acc, bias);
   const int i = r0 + 32 * wave + ln;
   const int src = srow[32 * wave + ln];
   if (src < 0) return;
@@ -385,6 +432,27 @@ __global__ __launch_bounds__(256) void ce_bwd_dw_kernel(const float* __restrict_
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// db[v] = sum_i G[i, v], i < count: see the file header for the order.
+constexpr int DBC = 32;   // columns per workgroup
+constexpr int DBQ = 32;   // row groups per column
+__global__ __launch_bounds__(DBC * DBQ) void ce_bwd_db_kernel(const float* __restrict__ G, int64_t ldg, int V,
+                                                              const int32_t* __restrict__ count, float* __restrict__ db) {
+  __shared__ float red[DBQ][DBC + 1];
+  const int c = threadIdx.x & (DBC - 1), q = threadIdx.x / DBC;
+  const int v = blockIdx.x * DBC + c;   // (< ldg: the grid covers ldg / DBC workgroups)
+  const int cnt = count[0];
+  float sum = 0.f;
+  for (int i = q; i < cnt; i += DBQ) sum += G[(int64_t)i * ldg + v];
+  red[q][c] = sum;
+  __syncthreads();
+  for (int o = DBQ / 2; o >= 1; o >>= 1) {
+    if (q < o) red[q][c] += red[q + o][c];
+    __syncthreads();
+  }
+  if (q == 0 && v < V) db[v] = red[0][c];
+}
+
 // vocabulary slices of the forward: enough workgroups for the machine when there are few row tiles; whole 128-word
 // tiles per slice, no empty slice
 static void slices(int64_t M, int V, int* nsplit, int* vper) {
@@ -438,15 +506,16 @@ static int ce_check_common(const char* who, int64_t ldx, int64_t ldw, int64_t M,
   return AMK_OK;
 }
 
-extern "C" int amk_ce_head_fwd(const float* x, int64_t ldx, const float* w, int64_t ldw, const int64_t* target,
-                               int64_t ignore_index, int64_t M, int V, int K, float* loss, float* lse, int32_t* rows,
-                               int32_t* count, void* ws, int64_t ws_bytes, void* stream) {
-  AMK_CHECK_ARG(x && w && target && loss && lse && rows && count && ws, "amk_ce_head_fwd: null pointer");
-  const int rc = ce_check_common("amk_ce_head_fwd", ldx, ldw, M, V, K);
+// bias == nullptr: the biasless head (who names the entry point in the messages)
+static int ce_fwd_impl(const char* who, const float* x, int64_t ldx, const float* w, int64_t ldw, const int64_t* target,
+                       int64_t ignore_index, int64_t M, int V, int K, float* loss, float* lse, int32_t* rows, int32_t* count,
+                       void* ws, int64_t ws_bytes, void* stream, const float* bias) {
+  AMK_CHECK_ARG(x && w && target && loss && lse && rows && count && ws, "%s: null pointer", who);
+  const int rc = ce_check_common(who, ldx, ldw, M, V, K);
   if (rc != AMK_OK) return rc;
   AMK_CHECK_ARG(ce_a16(x) && ce_a16(w) && ce_a16(ws) && ce_a8(target) && ce_a4(loss) && ce_a4(lse) && ce_a4(rows) && ce_a4(count),
-                "amk_ce_head_fwd: misaligned pointer (x, w, ws: 16 bytes; target: 8; loss, lse, rows, count: 4)");
-  AMK_CHECK_ARG(ws_bytes >= amk_ce_head_fwd_ws_bytes(M, V, K), "amk_ce_head_fwd: workspace of %lld bytes, %lld needed",
+                "%s: misaligned pointer (x, w, ws: 16 bytes; target: 8; loss, lse, rows, count: 4)", who);
+  AMK_CHECK_ARG(ws_bytes >= amk_ce_head_fwd_ws_bytes(M, V, K), "%s: workspace of %lld bytes, %lld needed", who,
                 (long long)ws_bytes, (long long)amk_ce_head_fwd_ws_bytes(M, V, K));
   int ns, vper;
   slices(M, V, &ns, &vper);
@@ -456,10 +525,69 @@ extern "C" int amk_ce_head_fwd(const float* x, int64_t ldx, const float* w, int6
   float* pz = ps + M * ns;
   const int64_t nrt = (M + TR - 1) / TR;
   hipLaunchKernelGGL(ce_compact_kernel, dim3(1), dim3(SCAN), 0, st, target, ignore_index, (int)M, rows, count);
-  hipLaunchKernelGGL(ce_fwd_kernel, dim3((unsigned)(nrt * ns)), dim3(256), 0, st, x, ldx, w, ldw, target, V, K, ns, vper, rows,
-                     count, pm, ps, pz);
+  if (bias)
+    hipLaunchKernelGGL(ce_fwd_kernel<true>, dim3((unsigned)(nrt * ns)), dim3(256), 0, st, x, ldx, w, ldw, target, V, K, ns, vper,
+                       rows, count, pm, ps, pz, bias);
+  else
+    hipLaunchKernelGGL(ce_fwd_kernel<false>, dim3((unsigned)(nrt * ns)), dim3(256), 0, st, x, ldx, w, ldw, target, V, K, ns, vper,
+                       rows, count, pm, ps, pz, bias);
   hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(SCAN), 0, st, pm, ps, pz, target, rows, count, V, ns, vper, lse, loss);
-  AMK_CHECK_LAUNCH("amk_ce_head_fwd");
+  AMK_CHECK_LAUNCH(who);
+  return AMK_OK;
+}
+
+extern "C" int amk_ce_head_fwd(const float* x, int64_t ldx, const float* w, int64_t ldw, const int64_t* target,
+                               int64_t ignore_index, int64_t M, int V, int K, float* loss, float* lse, int32_t* rows,
+                               int32_t* count, void* ws, int64_t ws_bytes, void* stream) {
+  return ce_fwd_impl("amk_ce_head_fwd", x, ldx, w, ldw, target, ignore_index, M, V, K, loss, lse, rows, count, ws, ws_bytes, stream,
+                     nullptr);
+}
+
+extern "C" int amk_ce_head_bias_fwd(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias,
+                                    const int64_t* target, int64_t ignore_index, int64_t M, int V, int K, float* loss, float* lse,
+                                    int32_t* rows, int32_t* count, void* ws, int64_t ws_bytes, void* stream) {
+  AMK_CHECK_ARG(bias, "amk_ce_head_bias_fwd: null pointer (bias)");
+  AMK_CHECK_ARG(ce_a16(bias), "amk_ce_head_bias_fwd: misaligned pointer (bias: 16 bytes)");
+  return ce_fwd_impl("amk_ce_head_bias_fwd", x, ldx, w, ldw, target, ignore_index, M, V, K, loss, lse, rows, count, ws, ws_bytes,
+                     stream, bias);
+}
+
+// bias == nullptr: the biasless head, dbias not used
+static int ce_bwd_impl(const char* who, const float* x, int64_t ldx, const float* w, int64_t ldw, const int64_t* target,
+                       int64_t ignore_index, int64_t M, int V, int K, const float* d_loss, const float* lse, const int32_t* rows,
+                       const int32_t* count, float* dx, int64_t lddx, float* dw, int64_t lddw, void* ws, int64_t ws_bytes,
+                       void* stream, const float* bias, float* dbias) {
+  AMK_CHECK_ARG(x && w && target && d_loss && lse && rows && count && dx && dw && ws, "%s: null pointer", who);
+  const int rc = ce_check_common(who, ldx, ldw, M, V, K);
+  if (rc != AMK_OK) return rc;
+  AMK_CHECK_SUPPORTED(lddx % 4 == 0 && lddw % 4 == 0, "%s: lddx=%lld and lddw=%lld must be multiples of 4", who, (long long)lddx,
+                      (long long)lddw);
+  AMK_CHECK_ARG(lddx >= K && lddw >= K, "%s: a leading dimension is below K", who);
+  AMK_CHECK_ARG(ce_a16(x) && ce_a16(w) && ce_a16(dx) && ce_a16(dw) && ce_a16(ws) && ce_a8(target) && ce_a4(d_loss) && ce_a4(lse) &&
+                    ce_a4(rows) && ce_a4(count),
+                "%s: misaligned pointer (x, w, dx, dw, ws: 16 bytes; target: 8; d_loss, lse, rows, count: 4)", who);
+  AMK_CHECK_ARG(ws_bytes >= amk_ce_head_bwd_ws_bytes(M, V, K), "%s: workspace of %lld bytes, %lld needed", who,
+                (long long)ws_bytes, (long long)amk_ce_head_bwd_ws_bytes(M, V, K));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  float* G = static_cast<float*>(ws);
+  const int64_t ldg = ldg_of(V);
+  const int64_t nrt = (M + TR - 1) / TR;
+  const int nvt = (int)(ldg / TA), nkt = (K + TA - 1) / TA;
+  if (bias)
+    hipLaunchKernelGGL(ce_bwd_g_kernel<true>, dim3((unsigned)(nrt * nvt)), dim3(256), 0, st, x, ldx, w, ldw, target, V, K, nvt,
+                       d_loss, lse, rows, count, G, ldg, bias);
+  else
+    hipLaunchKernelGGL(ce_bwd_g_kernel<false>, dim3((unsigned)(nrt * nvt)), dim3(256), 0, st, x, ldx, w, ldw, target, V, K, nvt,
+                       d_loss, lse, rows, count, G, ldg, bias);
+  hipLaunchKernelGGL(ce_zero_rows_kernel, dim3((unsigned)((M * (K / 4) + 255) / 256)), dim3(256), 0, st, target, ignore_index, M,
+                     V, K, dx, lddx);
+  hipLaunchKernelGGL(ce_bwd_dx_kernel, dim3((unsigned)(nrt * nkt)), dim3(256), 0, st, G, ldg, w, ldw, target, V, K, nkt, rows,
+                     count, dx, lddx);
+  hipLaunchKernelGGL(ce_bwd_dw_kernel, dim3((unsigned)(nvt * nkt)), dim3(256), 0, st, G, ldg, x, ldx, V, K, nkt, rows, count, dw,
+                     lddw);
+  if (bias)
+    hipLaunchKernelGGL(ce_bwd_db_kernel, dim3((unsigned)(ldg / DBC)), dim3(DBC * DBQ), 0, st, G, ldg, V, count, dbias);
+  AMK_CHECK_LAUNCH(who);
   return AMK_OK;
 }
 
@@ -467,30 +595,16 @@ extern "C" int amk_ce_head_bwd(const float* x, int64_t ldx, const float* w, int6
                                int64_t ignore_index, int64_t M, int V, int K, const float* d_loss, const float* lse,
                                const int32_t* rows, const int32_t* count, float* dx, int64_t lddx, float* dw, int64_t lddw,
                                void* ws, int64_t ws_bytes, void* stream) {
-  AMK_CHECK_ARG(x && w && target && d_loss && lse && rows && count && dx && dw && ws, "amk_ce_head_bwd: null pointer");
-  const int rc = ce_check_common("amk_ce_head_bwd", ldx, ldw, M, V, K);
-  if (rc != AMK_OK) return rc;
-  AMK_CHECK_SUPPORTED(lddx % 4 == 0 && lddw % 4 == 0, "amk_ce_head_bwd: lddx=%lld and lddw=%lld must be multiples of 4",
-                      (long long)lddx, (long long)lddw);
-  AMK_CHECK_ARG(lddx >= K && lddw >= K, "amk_ce_head_bwd: a leading dimension is below K");
-  AMK_CHECK_ARG(ce_a16(x) && ce_a16(w) && ce_a16(dx) && ce_a16(dw) && ce_a16(ws) && ce_a8(target) && ce_a4(d_loss) && ce_a4(lse) &&
-                    ce_a4(rows) && ce_a4(count),
-                "amk_ce_head_bwd: misaligned pointer (x, w, dx, dw, ws: 16 bytes; target: 8; d_loss, lse, rows, count: 4)");
-  AMK_CHECK_ARG(ws_bytes >= amk_ce_head_bwd_ws_bytes(M, V, K), "amk_ce_head_bwd: workspace of %lld bytes, %lld needed",
-                (long long)ws_bytes, (long long)amk_ce_head_bwd_ws_bytes(M, V, K));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  float* G = static_cast<float*>(ws);
-  const int64_t ldg = ldg_of(V);
-  const int64_t nrt = (M + TR - 1) / TR;
-  const int nvt = (int)(ldg / TA), nkt = (K + TA - 1) / TA;
-  hipLaunchKernelGGL(ce_bwd_g_kernel, dim3((unsigned)(nrt * nvt)), dim3(256), 0, st, x, ldx, w, ldw, target, V, K, nvt, d_loss,
-                     lse, rows, count, G, ldg);
-  hipLaunchKernelGGL(ce_zero_rows_kernel, dim3((unsigned)((M * (K / 4) + 255) / 256)), dim3(256), 0, st, target, ignore_index, M,
-                     V, K, dx, lddx);
-  hipLaunchKernelGGL(ce_bwd_dx_kernel, dim3((unsigned)(nrt * nkt)), dim3(256), 0, st, G, ldg, w, ldw, target, V, K, nkt, rows,
-                     count, dx, lddx);
-  hipLaunchKernelGGL(ce_bwd_dw_kernel, dim3((unsigned)(nvt * nkt)), dim3(256), 0, st, G, ldg, x, ldx, V, K, nkt, rows, count, dw,
-                     lddw);
-  AMK_CHECK_LAUNCH("amk_ce_head_bwd");
-  return AMK_OK;
+  return ce_bwd_impl("amk_ce_head_bwd", x, ldx, w, ldw, target, ignore_index, M, V, K, d_loss, lse, rows, count, dx, lddx, dw, lddw,
+                     ws, ws_bytes, stream, nullptr, nullptr);
+}
+
+extern "C" int amk_ce_head_bias_bwd(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias,
+                                    const int64_t* target, int64_t ignore_index, int64_t M, int V, int K, const float* d_loss,
+                                    const float* lse, const int32_t* rows, const int32_t* count, float* dx, int64_t lddx, float* dw,
+                                    int64_t lddw, float* dbias, void* ws, int64_t ws_bytes, void* stream) {
+  AMK_CHECK_ARG(bias && dbias, "amk_ce_head_bias_bwd: null pointer (bias or dbias)");
+  AMK_CHECK_ARG(ce_a16(bias) && ce_a16(dbias), "amk_ce_head_bias_bwd: misaligned pointer (bias, dbias: 16 bytes)");
+  return ce_bwd_impl("amk_ce_head_bias_bwd", x, ldx, w, ldw, target, ignore_index, M, V, K, d_loss, lse, rows, count,
+                     dx, lddx, dw, lddw, ws, ws_bytes, stream, bias, dbias);
 }

@@ -20,6 +20,16 @@
 //   ce_zero_rows : dx rows whose target is ignore_index or outside [0, V) are written as zeros.
 // Every grid is sized from M; a row tile that starts at or past count exits before any load.  No atomics.
 //
+// With a bias (amk_ce_head_bias_bf16_fwd / _bwd: the HAS_BIAS instantiations of ce_fwd and ce_bwd_g; the biasless ones are
+// the code they were): the f32 accumulator of the logits tile is PRELOADED with the F32 bias b[v0 + 32 b + acc_row(r, hf)]
+// instead of being cleared -- the bias is the first term of the f32 MFMA chain and is never rounded to bf16.  A word at or
+// past the end of the slice is not loaded and preloads 0: nothing at or past b[V] is read.
+//   ce_bwd_db : db[v] = sum_i G[i, v] over the compacted rows, the once-rounded bf16 G that dw reads, accumulated in f32.
+//               A workgroup of 1024 threads owns 64 columns: thread (column pair c = tid & 31, group q = tid >> 5) adds
+//               rows q, q + 32, q + 64, ... in ascending order (ceil(count / 32) terms per column), the 32 group sums of a
+//               column fold as a binary tree in LDS (q += q + 16, then 8, 4, 2, 1).  count == 0 writes zeros.  No
+//               workspace beyond G.
+//
 // The tile loops hold no branch around a memory instruction: a piece outside the problem is loaded from a clamped
 // address and replaced by zeros with a select.  One LDS-only barrier per step: the global prefetch stays in flight.
 #include "amk_common.h"
@@ -145,10 +155,39 @@ __global__ __launch_bounds__(SCAN) void ce_compact_kernel(const int64_t* __restr
   if (tid == 0) count[0] = base;
 }
 
+// acc[b][r] = bias[v0 + 32 b + acc_row(r, hf)]: the bias is the first term of the logits' MFMA chain.  A whole tile inside
+// the slice (a workgroup-uniform test) takes sixteen 16-byte loads (registers 4 g .. 4 g + 3 of a block are four
+// consecutive words; bias is 16-byte aligned and v0 a multiple of 128); the slice's last, partial tile loads word by word
+// under a predicate (a word at or past vend is not loaded and keeps 0): nothing at or past bias[vend] is read.
+__device__ __forceinline__ void preload_bias(const float* __restrict__ bias, int v0, int vend, int hf, f32x16 (&acc)[4]) {
+  if (v0 + TA <= vend) {
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const float4 q = *reinterpret_cast<const float4*>(bias + v0 + 32 * b + 8 * g + 4 * hf);
+        acc[b][4 * g] = q.x; acc[b][4 * g + 1] = q.y; acc[b][4 * g + 2] = q.z; acc[b][4 * g + 3] = q.w;
+      }
+  } else {
+    const float* bp = bias + v0 + 4 * hf;   // one base, constant offsets: the loads are predicated, not clamped
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int o = 32 * b + 8 * (r >> 2) + (r & 3);   // acc_row(r, hf) - 4 hf
+        float bv = 0.f;
+        if (v0 + 4 * hf + o < vend) bv = bp[o];
+        acc[b][r] = bv;
+      }
+  }
+}
+
 // ---------------------------------------------------------------------------------------
 // The logits tile shared by ce_fwd and ce_bwd_g: z^T for words [v0, v0 + 128) x the workgroup's 128 compacted rows.
+template <bool HAS_BIAS>
 __device__ __forceinline__ void logits_tile(const __bf16* __restrict__ x, int64_t ldx, const __bf16* __restrict__ w, int64_t ldw,
-                                            int K, int v0, int vend, const int* srow, __bf16* smem, f32x16 (&acc)[4]) {
+                                            int K, int v0, int vend, const int* srow, __bf16* smem, f32x16 (&acc)[4],
+                                            const float* __restrict__ bias) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, ln = lane & 31, hf = lane >> 5;
   const int ar = tid >> 2, ach = tid & 3;
   const __bf16 *wp[2], *xp[2];
@@ -161,7 +200,11 @@ __device__ __forceinline__ void logits_tile(const __bf16* __restrict__ x, int64_
     wp[i] = w + (int64_t)(wok[i] ? v0 + c : 0) * ldw + 8 * ach;
     xp[i] = x + (int64_t)(xok[i] ? r : 0) * ldx + 8 * ach;
   }
-  clear(acc);
+  if constexpr (HAS_BIAS) {
+    preload_bias(bias, v0, vend, hf, acc);
+  } else {
+    clear(acc);
+  }
   product((K + BK - 1) / BK, smem,
           [&](Stage& g, int t) {
             const bool kin = BK * t + 8 * ach < K;   // (K a multiple of 8: a piece is in or out)
@@ -183,11 +226,13 @@ __device__ __forceinline__ void logits_tile(const __bf16* __restrict__ x, int64_
           });
 }
 
+template <bool HAS_BIAS>
 __global__ __launch_bounds__(256) void ce_fwd_kernel(const __bf16* __restrict__ x, int64_t ldx, const __bf16* __restrict__ w,
                                                      int64_t ldw, const int64_t* __restrict__ target, int V, int K,
                                                      int nsplit, int vper, const int32_t* __restrict__ rows,
                                                      const int32_t* __restrict__ count, float* __restrict__ pm,
-                                                     float* __restrict__ ps, float* __restrict__ pz) {
+                                                     float* __restrict__ ps, float* __restrict__ pz,
+                                                     const float* __restrict__ bias) {
   __shared__ __attribute__((aligned(16))) __bf16 smem[2 * STAGE];
   __shared__ int srow[TR];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -207,7 +252,7 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const __bf16* __restrict__ 
   bool found = false;
   f32x16 acc[4];
   for (int v0 = vbeg; v0 < vend; v0 += TA) {
-    logits_tile(x, ldx, w, ldw, K, v0, vend, srow, smem, acc);
+    logits_tile<HAS_BIAS>(x, ldx, w, ldw, K, v0, vend, srow, smem, acc, bias);
     float tmax = -INFINITY;
 #pragma unroll
     for (int b = 0; b < 4; ++b)
@@ -278,11 +323,12 @@ __global__ __launch_bounds__(SCAN) void ce_finalize_kernel(const float* __restri
 }
 
 // ---------------------------------------------------------------------------------------
+template <bool HAS_BIAS>
 __global__ __launch_bounds__(256) void ce_bwd_g_kernel(const __bf16* __restrict__ x, int64_t ldx, const __bf16* __restrict__ w,
                                                        int64_t ldw, const int64_t* __restrict__ target, int V, int K, int nvt,
                                                        const float* __restrict__ d_loss, const float* __restrict__ lse,
                                                        const int32_t* __restrict__ rows, const int32_t* __restrict__ count,
-                                                       __bf16* __restrict__ G, int64_t ldg) {
+                                                       __bf16* __restrict__ G, int64_t ldg, const float* __restrict__ bias) {
   __shared__ __attribute__((aligned(16))) __bf16 smem[2 * STAGE];
   __shared__ int srow[TR];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -294,7 +340,7 @@ __global__ __launch_bounds__(256) void ce_bwd_g_kernel(const __bf16* __restrict_
   if (tid < TR) srow[tid] = r0 + tid < cnt ? rows[r0 + tid] : -1;
   __syncthreads();
   f32x16 acc[4];
-  logits_tile(x, ldx, w, ldw, K, v0, V, srow, smem, acc);
+  logits_tile<HAS_BIAS>(x, ldx, w, ldw, K, v0, V, srow, smem, acc, bias);
   const int i = r0 + 32 * wave + ln;
   const int src = srow[32 * wave + ln];
   if (src < 0) return;
@@ -442,6 +488,39 @@ __global__ __launch_bounds__(256) void ce_bwd_dw_kernel(const __bf16* __restrict
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// db[v] = sum_i G[i, v], i < count, in f32: see the file header for the order.
+constexpr int DBC = 64;   // columns per workgroup (two per thread: one 4-byte load)
+constexpr int DBQ = 32;   // row groups per column
+__global__ __launch_bounds__(DBC / 2 * DBQ) void ce_bwd_db_kernel(const __bf16* __restrict__ G, int64_t ldg, int V,
+                                                                  const int32_t* __restrict__ count, float* __restrict__ db) {
+  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+  __shared__ float red[DBQ][DBC + 1];
+  const int c = 2 * (threadIdx.x & (DBC / 2 - 1)), q = threadIdx.x / (DBC / 2);
+  const int v = blockIdx.x * DBC + c;   // (v + 1 < ldg: the grid covers ldg / DBC workgroups)
+  const int cnt = count[0];
+  float s0 = 0.f, s1 = 0.f;
+  for (int i = q; i < cnt; i += DBQ) {
+    const bf16x2 g = *reinterpret_cast<const bf16x2*>(G + (int64_t)i * ldg + v);
+    s0 += (float)g[0];
+    s1 += (float)g[1];
+  }
+  red[q][c] = s0;
+  red[q][c + 1] = s1;
+  __syncthreads();
+  for (int o = DBQ / 2; o >= 1; o >>= 1) {
+    if (q < o) {
+      red[q][c] += red[q + o][c];
+      red[q][c + 1] += red[q + o][c + 1];
+    }
+    __syncthreads();
+  }
+  if (q == 0) {
+    if (v < V) db[v] = red[0][c];
+    if (v + 1 < V) db[v + 1] = red[0][c + 1];
+  }
+}
+
 // vocabulary slices of the forward: as the f32 head's (tests restate it once for both)
 static void slices(int64_t M, int V, int* nsplit, int* vper) {
   const int64_t nrt = (M + TR - 1) / TR;
@@ -494,15 +573,16 @@ extern "C" int64_t amk_ce_head_bf16_bwd_ws_bytes(int64_t M, int V, int K) {
   return M * amk_ce16::ldg_of(V) * (int64_t)sizeof(__bf16);
 }
 
-extern "C" int amk_ce_head_bf16_fwd(const void* x, int64_t ldx, const void* w, int64_t ldw, const int64_t* target,
-                                    int64_t ignore_index, int64_t M, int V, int K, float* loss, float* lse, int32_t* rows,
-                                    int32_t* count, void* ws, int64_t ws_bytes, void* stream) {
-  AMK_CHECK_ARG(x && w && target && loss && lse && rows && count && ws, "amk_ce_head_bf16_fwd: null pointer");
-  const int rc = check_common("amk_ce_head_bf16_fwd", ldx, ldw, M, V, K);
+// bias == nullptr: the biasless head (who names the entry point in the messages)
+static int fwd_impl(const char* who, const void* x, int64_t ldx, const void* w, int64_t ldw, const int64_t* target,
+                    int64_t ignore_index, int64_t M, int V, int K, float* loss, float* lse, int32_t* rows, int32_t* count, void* ws,
+                    int64_t ws_bytes, void* stream, const float* bias) {
+  AMK_CHECK_ARG(x && w && target && loss && lse && rows && count && ws, "%s: null pointer", who);
+  const int rc = check_common(who, ldx, ldw, M, V, K);
   if (rc != AMK_OK) return rc;
   AMK_CHECK_ARG(a16(x) && a16(w) && a16(ws) && a8(target) && a4(loss) && a4(lse) && a4(rows) && a4(count),
-                "amk_ce_head_bf16_fwd: misaligned pointer (x, w, ws: 16 bytes; target: 8; loss, lse, rows, count: 4)");
-  AMK_CHECK_ARG(ws_bytes >= amk_ce_head_bf16_fwd_ws_bytes(M, V, K), "amk_ce_head_bf16_fwd: workspace of %lld bytes, %lld needed",
+                "%s: misaligned pointer (x, w, ws: 16 bytes; target: 8; loss, lse, rows, count: 4)", who);
+  AMK_CHECK_ARG(ws_bytes >= amk_ce_head_bf16_fwd_ws_bytes(M, V, K), "%s: workspace of %lld bytes, %lld needed", who,
                 (long long)ws_bytes, (long long)amk_ce_head_bf16_fwd_ws_bytes(M, V, K));
   int ns, vper;
   amk_ce16::slices(M, V, &ns, &vper);
@@ -514,27 +594,48 @@ extern "C" int amk_ce_head_bf16_fwd(const void* x, int64_t ldx, const void* w, i
   float* pz = ps + M * ns;
   const int64_t nrt = (M + TR - 1) / TR;
   hipLaunchKernelGGL(amk_ce16::ce_compact_kernel, dim3(1), dim3(SCAN), 0, st, target, ignore_index, (int)M, rows, count);
-  hipLaunchKernelGGL(amk_ce16::ce_fwd_kernel, dim3((unsigned)(nrt * ns)), dim3(256), 0, st, xb, ldx, wb, ldw, target, V, K, ns,
-                     vper, rows, count, pm, ps, pz);
+  if (bias)
+    hipLaunchKernelGGL(amk_ce16::ce_fwd_kernel<true>, dim3((unsigned)(nrt * ns)), dim3(256), 0, st, xb, ldx, wb, ldw, target, V, K,
+                       ns, vper, rows, count, pm, ps, pz, bias);
+  else
+    hipLaunchKernelGGL(amk_ce16::ce_fwd_kernel<false>, dim3((unsigned)(nrt * ns)), dim3(256), 0, st, xb, ldx, wb, ldw, target, V, K,
+                       ns, vper, rows, count, pm, ps, pz, bias);
   hipLaunchKernelGGL(amk_ce16::ce_finalize_kernel, dim3(1), dim3(SCAN), 0, st, pm, ps, pz, target, rows, count, V, ns, vper, lse,
                      loss);
-  AMK_CHECK_LAUNCH("amk_ce_head_bf16_fwd");
+  AMK_CHECK_LAUNCH(who);
   return AMK_OK;
 }
 
-extern "C" int amk_ce_head_bf16_bwd(const void* x, int64_t ldx, const void* w, int64_t ldw, const int64_t* target,
-                                    int64_t ignore_index, int64_t M, int V, int K, const float* d_loss, const float* lse,
-                                    const int32_t* rows, const int32_t* count, void* dx, int64_t lddx, float* dw, int64_t lddw,
-                                    void* ws, int64_t ws_bytes, void* stream) {
-  AMK_CHECK_ARG(x && w && target && d_loss && lse && rows && count && dx && dw && ws, "amk_ce_head_bf16_bwd: null pointer");
-  const int rc = check_common("amk_ce_head_bf16_bwd", ldx, ldw, M, V, K);
+extern "C" int amk_ce_head_bf16_fwd(const void* x, int64_t ldx, const void* w, int64_t ldw, const int64_t* target,
+                                    int64_t ignore_index, int64_t M, int V, int K, float* loss, float* lse, int32_t* rows,
+                                    int32_t* count, void* ws, int64_t ws_bytes, void* stream) {
+  return fwd_impl("amk_ce_head_bf16_fwd", x, ldx, w, ldw, target, ignore_index, M, V, K, loss, lse, rows, count, ws, ws_bytes, stream,
+                  nullptr);
+}
+
+extern "C" int amk_ce_head_bias_bf16_fwd(const void* x, int64_t ldx, const void* w, int64_t ldw, const float* bias,
+                                         const int64_t* target, int64_t ignore_index, int64_t M, int V, int K, float* loss,
+                                         float* lse, int32_t* rows, int32_t* count, void* ws, int64_t ws_bytes, void* stream) {
+  AMK_CHECK_ARG(bias, "amk_ce_head_bias_bf16_fwd: null pointer (bias)");
+  AMK_CHECK_ARG(a16(bias), "amk_ce_head_bias_bf16_fwd: misaligned pointer (bias: 16 bytes)");
+  return fwd_impl("amk_ce_head_bias_bf16_fwd", x, ldx, w, ldw, target, ignore_index, M, V, K, loss, lse, rows, count, ws, ws_bytes,
+                  stream, bias);
+}
+
+// bias == nullptr: the biasless head, dbias not used
+static int bwd_impl(const char* who, const void* x, int64_t ldx, const void* w, int64_t ldw, const int64_t* target,
+                    int64_t ignore_index, int64_t M, int V, int K, const float* d_loss, const float* lse, const int32_t* rows,
+                    const int32_t* count, void* dx, int64_t lddx, float* dw, int64_t lddw, void* ws, int64_t ws_bytes, void* stream,
+                    const float* bias, float* dbias) {
+  AMK_CHECK_ARG(x && w && target && d_loss && lse && rows && count && dx && dw && ws, "%s: null pointer", who);
+  const int rc = check_common(who, ldx, ldw, M, V, K);
   if (rc != AMK_OK) return rc;
-  AMK_CHECK_SUPPORTED(lddx % 8 == 0 && lddw % 8 == 0, "amk_ce_head_bf16_bwd: lddx=%lld and lddw=%lld must be multiples of 8",
-                      (long long)lddx, (long long)lddw);
-  AMK_CHECK_ARG(lddx >= K && lddw >= K, "amk_ce_head_bf16_bwd: a leading dimension is below K");
+  AMK_CHECK_SUPPORTED(lddx % 8 == 0 && lddw % 8 == 0, "%s: lddx=%lld and lddw=%lld must be multiples of 8", who, (long long)lddx,
+                      (long long)lddw);
+  AMK_CHECK_ARG(lddx >= K && lddw >= K, "%s: a leading dimension is below K", who);
   AMK_CHECK_ARG(a16(x) && a16(w) && a16(dx) && a16(dw) && a16(ws) && a8(target) && a4(d_loss) && a4(lse) && a4(rows) && a4(count),
-                "amk_ce_head_bf16_bwd: misaligned pointer (x, w, dx, dw, ws: 16 bytes; target: 8; d_loss, lse, rows, count: 4)");
-  AMK_CHECK_ARG(ws_bytes >= amk_ce_head_bf16_bwd_ws_bytes(M, V, K), "amk_ce_head_bf16_bwd: workspace of %lld bytes, %lld needed",
+                "%s: misaligned pointer (x, w, dx, dw, ws: 16 bytes; target: 8; d_loss, lse, rows, count: 4)", who);
+  AMK_CHECK_ARG(ws_bytes >= amk_ce_head_bf16_bwd_ws_bytes(M, V, K), "%s: workspace of %lld bytes, %lld needed", who,
                 (long long)ws_bytes, (long long)amk_ce_head_bf16_bwd_ws_bytes(M, V, K));
   hipStream_t st = static_cast<hipStream_t>(stream);
   const __bf16* xb = static_cast<const __bf16*>(x);
@@ -543,14 +644,38 @@ extern "C" int amk_ce_head_bf16_bwd(const void* x, int64_t ldx, const void* w, i
   const int64_t ldg = amk_ce16::ldg_of(V);
   const int64_t nrt = (M + TR - 1) / TR;
   const int nvt = (int)(ldg / TA), nkt = (K + TA - 1) / TA;
-  hipLaunchKernelGGL(amk_ce16::ce_bwd_g_kernel, dim3((unsigned)(nrt * nvt)), dim3(256), 0, st, xb, ldx, wb, ldw, target, V, K, nvt,
-                     d_loss, lse, rows, count, G, ldg);
+  if (bias)
+    hipLaunchKernelGGL(amk_ce16::ce_bwd_g_kernel<true>, dim3((unsigned)(nrt * nvt)), dim3(256), 0, st, xb, ldx, wb, ldw, target, V, K,
+                       nvt, d_loss, lse, rows, count, G, ldg, bias);
+  else
+    hipLaunchKernelGGL(amk_ce16::ce_bwd_g_kernel<false>, dim3((unsigned)(nrt * nvt)), dim3(256), 0, st, xb, ldx, wb, ldw, target, V,
+                       K, nvt, d_loss, lse, rows, count, G, ldg, bias);
   hipLaunchKernelGGL(amk_ce16::ce_zero_rows_kernel, dim3((unsigned)((M * (K / 8) + 255) / 256)), dim3(256), 0, st, target,
                      ignore_index, M, V, K, static_cast<__bf16*>(dx), lddx);
   hipLaunchKernelGGL(amk_ce16::ce_bwd_dx_kernel, dim3((unsigned)(nrt * nkt)), dim3(256), 0, st, G, ldg, wb, ldw, target, V, K, nkt,
                      rows, count, static_cast<__bf16*>(dx), lddx);
   hipLaunchKernelGGL(amk_ce16::ce_bwd_dw_kernel, dim3((unsigned)(nvt * nkt)), dim3(256), 0, st, G, ldg, xb, ldx, V, K, nkt, rows, count,
                      dw, lddw);
-  AMK_CHECK_LAUNCH("amk_ce_head_bf16_bwd");
+  if (bias)
+    hipLaunchKernelGGL(amk_ce16::ce_bwd_db_kernel, dim3((unsigned)(ldg / DBC)), dim3(DBC / 2 * DBQ), 0, st, G, ldg, V, count, dbias);
+  AMK_CHECK_LAUNCH(who);
   return AMK_OK;
+}
+
+extern "C" int amk_ce_head_bf16_bwd(const void* x, int64_t ldx, const void* w, int64_t ldw, const int64_t* target,
+                                    int64_t ignore_index, int64_t M, int V, int K, const float* d_loss, const float* lse,
+                                    const int32_t* rows, const int32_t* count, void* dx, int64_t lddx, float* dw, int64_t lddw,
+                                    void* ws, int64_t ws_bytes, void* stream) {
+  return bwd_impl("amk_ce_head_bf16_bwd", x, ldx, w, ldw, target, ignore_index, M, V, K, d_loss, lse, rows, count, dx, lddx, dw, lddw,
+                  ws, ws_bytes, stream, nullptr, nullptr);
+}
+
+extern "C" int amk_ce_head_bias_bf16_bwd(const void* x, int64_t ldx, const void* w, int64_t ldw, const float* bias,
+                                         const int64_t* target, int64_t ignore_index, int64_t M, int V, int K, const float* d_loss,
+                                         const float* lse, const int32_t* rows, const int32_t* count, void* dx, int64_t lddx,
+                                         float* dw, int64_t lddw, float* dbias, void* ws, int64_t ws_bytes, void* stream) {
+  AMK_CHECK_ARG(bias && dbias, "amk_ce_head_bias_bf16_bwd: null pointer (bias or dbias)");
+  AMK_CHECK_ARG(a16(bias) && a16(dbias), "amk_ce_head_bias_bf16_bwd: misaligned pointer (bias, dbias: 16 bytes)");
+  return bwd_impl("amk_ce_head_bias_bf16_bwd", x, ldx, w, ldw, target, ignore_index, M, V, K, d_loss, lse, rows, count, dx, lddx, dw,
+                  lddw, ws, ws_bytes, stream, bias, dbias);
 }

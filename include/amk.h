@@ -750,6 +750,23 @@ int amk_ce_head_bwd(const float* x, int64_t ldx, const float* w, int64_t ldw, co
                     void* ws, int64_t ws_bytes, void* stream);
 
 /* --------------------------------------------------------------------------
+ * The loss head with a bias (csrc/ce_head.hip): z[m, v] = sum_k x[m, k] w[v, k] + bias[v], everything else as
+ * amk_ce_head_fwd / _bwd above.  bias (V,) f32 is the first term of each logit's MFMA chain (the accumulator is preloaded
+ * with it); nothing at or past bias[V] is read, for any V.  The backward also writes dbias[v] = sum over the compacted
+ * rows of g[i, v] for every v < V, f32, in a fixed order without atomics (bitwise reproducible; zeros when no row is
+ * valid; a row whose target is out of range gives nothing).  dbias sums the g that dw reads and needs no workspace of
+ * its own: the biasless sizes amk_ce_head_fwd_ws_bytes / _bwd_ws_bytes apply.
+ * Refusals as above, and AMK_EINVAL for a null bias or dbias or one that is not 16-byte aligned.
+ * -------------------------------------------------------------------------- */
+int amk_ce_head_bias_fwd(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias,
+                         const int64_t* target, int64_t ignore_index, int64_t M, int V, int K, float* loss, float* lse,
+                         int32_t* rows, int32_t* count, void* ws, int64_t ws_bytes, void* stream);
+int amk_ce_head_bias_bwd(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias,
+                         const int64_t* target, int64_t ignore_index, int64_t M, int V, int K, const float* d_loss,
+                         const float* lse, const int32_t* rows, const int32_t* count, float* dx, int64_t lddx, float* dw,
+                         int64_t lddw, float* dbias, void* ws, int64_t ws_bytes, void* stream);
+
+/* --------------------------------------------------------------------------
  * The masked-token loss head under bf16 autocast (csrc/ce_head_bf16.hip): the head above with bf16 operands on
  * v_mfma_f32_32x32x16_bf16.  x (M, K) and w (V, K) are bf16, row-major with unit column stride; products accumulate in
  * f32 and every softmax quantity stays in f32 (running maximum, sum of exp, lse, the target logit, the loss,
@@ -782,6 +799,22 @@ int amk_ce_head_bf16_bwd(const void* x, int64_t ldx, const void* w, int64_t ldw,
                          int64_t ignore_index, int64_t M, int V, int K, const float* d_loss, const float* lse,
                          const int32_t* rows, const int32_t* count, void* dx, int64_t lddx, float* dw, int64_t lddw,
                          void* ws, int64_t ws_bytes, void* stream);
+
+/* --------------------------------------------------------------------------
+ * The bf16 loss head with a bias (csrc/ce_head_bf16.hip): amk_ce_head_bf16_fwd / _bwd with
+ * z[m, v] = sum_k x[m, k] w[v, k] + bias[v].  bias (V,) stays F32 -- the master bias is never rounded to bf16 -- and is
+ * the first term of each logit's f32 MFMA chain; nothing at or past bias[V] is read.  dbias[v] (f32, v < V) = the sum
+ * over the compacted rows of the once-rounded bf16 g that dw reads, accumulated in f32 in a fixed order without atomics;
+ * zeros when no row is valid.  No workspace of its own: amk_ce_head_bf16_fwd_ws_bytes / _bwd_ws_bytes apply.
+ * Refusals as above, and AMK_EINVAL for a null bias or dbias or one that is not 16-byte aligned.
+ * -------------------------------------------------------------------------- */
+int amk_ce_head_bias_bf16_fwd(const void* x, int64_t ldx, const void* w, int64_t ldw, const float* bias,
+                              const int64_t* target, int64_t ignore_index, int64_t M, int V, int K, float* loss, float* lse,
+                              int32_t* rows, int32_t* count, void* ws, int64_t ws_bytes, void* stream);
+int amk_ce_head_bias_bf16_bwd(const void* x, int64_t ldx, const void* w, int64_t ldw, const float* bias,
+                              const int64_t* target, int64_t ignore_index, int64_t M, int V, int K, const float* d_loss,
+                              const float* lse, const int32_t* rows, const int32_t* count, void* dx, int64_t lddx, float* dw,
+                              int64_t lddw, float* dbias, void* ws, int64_t ws_bytes, void* stream);
 
 /* --------------------------------------------------------------------------
  * The routed expert products of MoELayer under bf16 autocast (csrc/moe_bf16.hip): the per-expert nn.Linear layers of

@@ -13,7 +13,11 @@ more than the spread.
 --autocast bf16: the same three cases inside torch.autocast("cuda", bfloat16) with bf16 inputs and an f32 master weight,
 as the autocast train step has them: the fused op is then csrc/ce_head_bf16.hip, the parent path F.linear +
 F.cross_entropy as autocast runs them (bf16 GEMMs over all rows, bf16 logits, their f32 copy for the softmax), and the
-credited TFLOP/s are set against the dense bf16 MFMA peak.  The same rule decides the default of AMK_CE_HEAD_BF16."""
+credited TFLOP/s are set against the dense bf16 MFMA peak.  The same rule decides the default of AMK_CE_HEAD_BF16.
+
+--bias: the op with a bias (ops.linear_cross_entropy(..., bias=b): amk_ce_head_bias_*) against F.linear(x, w, b) +
+F.cross_entropy at Parti's head (8192 rows, all valid, 8192 words) at dim 512 and 1024, and beside them the BIASLESS fused
+op on the same tensors, a third arm of the same rounds: the difference is what the bias preload and db cost."""
 import argparse
 import contextlib
 import math
@@ -34,6 +38,8 @@ PEAK_BF16 = 2500.0   # TFLOP/s, dense bf16 MFMA (the figure DESIGN.md uses)
 CASES = [("muse 8x1024 d1024 V8192", 8, 1024, 1024, 8192, "schedule"),
          ("maskgit 8x256 d768 V8192", 8, 256, 768, 8192, "schedule"),
          ("muse, every row valid", 8, 1024, 1024, 8192, "all")]
+CASES_BIAS = [("parti 8x1024 d512 V8192", 8, 1024, 512, 8192, "all"),
+              ("parti rows, d1024 V8192", 8, 1024, 1024, 8192, "all")]
 
 
 def schedule_targets(B, T, V, dev, mode):
@@ -47,7 +53,7 @@ def schedule_targets(B, T, V, dev, mode):
     return tokens.masked_fill(~(order < n_masked.unsqueeze(-1)), -1)
 
 
-def make(B, T, K, V, mode, dev, autocast=None):
+def make(B, T, K, V, mode, dev, autocast=None, bias=False):
     x = torch.randn(B, T, K, device=dev, dtype=torch.bfloat16 if autocast else torch.float32).requires_grad_()
     w = (torch.randn(V, K, device=dev) * 0.02).requires_grad_()
     tgt = schedule_targets(B, T, V, dev, mode)
@@ -65,6 +71,20 @@ def make(B, T, K, V, mode, dev, autocast=None):
             loss = F.cross_entropy(F.linear(x, w).transpose(1, 2), tgt, ignore_index=-1)
         return torch.autograd.grad(loss, (x, w))
 
+    if bias:
+        b = torch.randn(V, device=dev).requires_grad_()
+
+        def fused_b():
+            with amp():
+                loss = ops.linear_cross_entropy(x, w, tgt, -1, bias=b)
+            return torch.autograd.grad(loss, (x, w, b))
+
+        def parent_b():
+            with amp():
+                loss = F.cross_entropy(F.linear(x, w, b).transpose(1, 2), tgt, ignore_index=-1)
+            return torch.autograd.grad(loss, (x, w, b))
+
+        return {"fused": fused_b, "parent": parent_b, "biasless": fused}, float((tgt != -1).float().mean())
     return {"fused": fused, "parent": parent}, float((tgt != -1).float().mean())
 
 
@@ -95,6 +115,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--autocast", choices=["none", "bf16"], default="none")
+    ap.add_argument("--bias", action="store_true")
     args = ap.parse_args()
     autocast = torch.bfloat16 if args.autocast == "bf16" else None
     peak = PEAK_BF16 if autocast else PEAK
@@ -104,12 +125,13 @@ def main():
           f"against {peak:g}")
     print(f"forward + backward, median of {args.rounds} alternating rounds x {args.iters} calls; spread = max - min of the rounds")
     print(f"{'case':>26} {'valid':>6} {'parent ms':>10} {'spread':>7} {'fused ms':>9} {'spread':>7} {'fused/parent':>12} "
-          f"{'parent MB':>10} {'fused MB':>9} {'credited TF':>11} {'of peak':>8}")
-    for name, B, T, K, V, mode in CASES:
-        fns, frac = make(B, T, K, V, mode, dev, autocast)
+          f"{'parent MB':>10} {'fused MB':>9} {'credited TF':>11} {'of peak':>8}"
+          + (f" {'biasless ms':>12} {'spread':>7} {'biasless MB':>12}" if args.bias else ""))
+    for name, B, T, K, V, mode in (CASES_BIAS if args.bias else CASES):
+        fns, frac = make(B, T, K, V, mode, dev, autocast, args.bias)
         res = {k: [] for k in fns}
         for r in range(args.rounds + 1):
-            for k in ("parent", "fused"):
+            for k in (("parent", "fused", "biasless") if args.bias else ("parent", "fused")):
                 ms = timed(fns[k], args.iters)
                 if r:   # round 0 warms up
                     res[k].append(ms)
@@ -118,7 +140,9 @@ def main():
         sp, sf = max(res["parent"]) - min(res["parent"]), max(res["fused"]) - min(res["fused"])
         tf = 3 * 2.0 * B * T * V * K / (f * 1e-3) / 1e12
         print(f"{name:>26} {frac:6.2f} {p:10.3f} {sp:7.3f} {f:9.3f} {sf:7.3f} {f / p:12.2f} {mem['parent']:10.0f} "
-              f"{mem['fused']:9.0f} {tf:11.1f} {tf / peak:8.3f}", flush=True)
+              f"{mem['fused']:9.0f} {tf:11.1f} {tf / peak:8.3f}"
+              + (f" {statistics.median(res['biasless']):12.3f} {max(res['biasless']) - min(res['biasless']):7.3f} "
+                 f"{mem['biasless']:12.0f}" if args.bias else ""), flush=True)
         del fns
 
 

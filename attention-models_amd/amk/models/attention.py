@@ -51,6 +51,23 @@ class SoftmaxAttention(nn.Module):
         )                                # (B, I, h*d) == 'b h t d -> b t (h d)'
         return self._drop(self.W_o(o))
 
+    # KV-cached decoding (inference; no dropout): one new row per call, see models/decoding.py
+    def project_context(self, context):
+        """The K|V of a cross-attention context (B, L, 2*h*d), projected once per decode."""
+        return self.kv(context).contiguous()
+
+    def decode_step(self, x, cache, n_dev=None, context_mask=None, append=True, ws=None):
+        """forward for ONE row x (B, 1, dim) on the decode kernel (ops.attention_decode).  append: self-attention --
+        the row's K|V become row ``n_dev`` of ``cache`` and the row attends rows 0 .. n_dev (the causal mask's row).
+        Otherwise cross-attention over the whole ``cache`` from project_context, with its key mask."""
+        if append:
+            q, kv = ops.linear2(x, self.q[0].weight, self.kv[0].weight)
+            o = ops.attention_decode(q, kv, cache, n_dev, self.num_heads, self.dim_head, self.scale, ws=ws)
+        else:
+            o = ops.attention_decode(self.q(x), None, cache, None, self.num_heads, self.dim_head, self.scale,
+                                     key_mask=context_mask, ws=ws)
+        return self.W_o(o)
+
 
 class SwitchHeadAttention(StackedExpertsMixin, nn.Module):
     """SwitchHead attention (reference: models/switchhead_attention.py:18-116).

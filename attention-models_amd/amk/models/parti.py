@@ -7,8 +7,15 @@ models/parti.py:36-37), which is not available here, so -- as ``MUSE`` does -- `
 ``max_length`` keep their places in the constructor and are not used.  Everything downstream follows the reference,
 quirks included: ``generate`` runs the whole prefix through the decoder at every step, WITHOUT a causal mask, without
 ``context_norm`` on the text embeddings, and discards the results of ``init_norm`` and ``final_norm`` (reference
-:142-144), so a KV-cached causal decode would not compute what it computes.
+:142-144), so a KV-cached causal decode would not compute what it computes.  ``generate`` stays that loop.
+
+Sampling from the distribution ``forward`` trains is a loop of its own next to it: ``begin_decode`` (context_norm, the
+context's K|V projected once), ``next_logits`` (one row through init_norm, ``Decoder.step`` on the single-token attention
+kernel of csrc/attn_decode.hip, final_norm, to_logits) and ``sample`` (``generate``'s top-k filter and Gumbel-argmax, one
+token per step against cached keys and values; ``graph=True`` replays one captured step for every position).
 """
+import weakref
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -18,6 +25,10 @@ from .layers import LayerNorm, Linear
 from .muse import filter_logits
 from .positional_encoding import PositionalEncoding
 from .transformer import Decoder
+
+
+# module -> its captured decode step (Parti._sample_graphed)
+_DECODE_GRAPHS = weakref.WeakKeyDictionary()
 
 
 class Parti(nn.Module):
@@ -39,6 +50,7 @@ class Parti(nn.Module):
         self.to_logits = Linear(dim, codebook_size)
 
         self.vq.requires_grad_(False)
+        self.decode_graph_captures = 0   # captures taken by sample(graph=True), for tests and diagnostics
 
     @staticmethod
     def _context(text_hidden):
@@ -90,3 +102,159 @@ class Parti(nn.Module):
                 token = (last + gumbel[i]).argmax(dim=-1)             # argmax softmax(x + g) = argmax (x + g)
             indices = torch.cat((indices, token.unsqueeze(1)), dim=1)
         return self.vq.decode_indices(indices)
+
+    # ---- KV-cached causal decoding: ``forward``'s arithmetic row by row, i.e. sampling from the trained distribution
+    @torch.no_grad()
+    def begin_decode(self, text_hidden, capacity=None, out=None):
+        """The decode state over ``context_norm(text_hidden)`` for up to ``capacity`` image tokens (default: all
+        ``vq.num_patches``).  out: a state to refill in place."""
+        capacity = self.vq.num_patches if capacity is None else int(capacity)
+        if capacity < self.vq.num_patches:
+            raise ValueError(f"capacity {capacity} is smaller than the {self.vq.num_patches} image tokens of a sample")
+        text_embeds = self.context_norm(self._context(text_hidden))
+        return self.transformer_decoder.init_state(text_embeds, capacity, out=out)
+
+    @torch.no_grad()
+    def next_logits(self, state, prev_tokens=None):
+        """(B, V) logits of the token at the state's position: row ``pos`` of ``forward``'s logits.  The decoder's input
+        row is the start token at position 0 (prev_tokens None) and token_emb(prev_tokens) + pe[pos - 1] after it; it
+        goes through init_norm, ``Decoder.step``, final_norm and to_logits, then the position advances.  The position
+        and the ``pe`` row are read on the device."""
+        if prev_tokens is None:
+            if state.host_pos != 0:
+                raise ValueError("only position 0 takes the start token; pass the previous tokens")
+            x = self.start_token.expand(state.batch, 1, -1)
+        else:
+            pe = self.pos_enc.pe.index_select(0, state.pos - 1)
+            x = self.pos_enc.dropout(self.token_emb(prev_tokens.view(-1, 1)) + pe)
+        out = self.transformer_decoder.step(self.init_norm(x), state)
+        logits = self.to_logits(self.final_norm(out))[:, 0, :]
+        state.advance()
+        return logits
+
+    def _draw(self, logits, ids, noise, tau, p):
+        """generate's sampler on (B, V) logits into ids (B, 1) int64, in place: top-ceil((1 - p) V) filter, then the
+        argmax of logits + Gumbel noise (= the argmax of the Gumbel-softmax at any temperature tau > 0).  noise None:
+        drawn by the kernel's own Philox stream (eager only: its seed and offset are host values)."""
+        v = logits.shape[-1]
+        if v % 4 == 0 and v <= 36864:     # csrc/sample.hip holds one row in LDS
+            if noise is None:
+                ops.sample_step(logits.unsqueeze(1), ids, tau=tau, p=p)
+            else:   # explicit noise: the kernel draws nothing; a fixed seed keeps torch's generator out of a capture
+                ops.sample_step(logits.unsqueeze(1), ids, tau=tau, p=p, gumbel=noise.unsqueeze(1), seed=0)
+            return
+        if noise is None:
+            noise = -torch.empty_like(logits).exponential_().log()
+        ids.copy_((filter_logits(logits.unsqueeze(1), p=p)[:, 0, :] + noise).argmax(dim=-1, keepdim=True))
+
+    @torch.no_grad()
+    def sample(self, text_hidden, gumbel=None, trace=None, tau=1.0, p=0.9, graph=False):
+        """Sample ``vq.num_patches`` tokens from the model as trained -- context_norm, init_norm, causal self-attention,
+        final_norm -- one token per step against cached keys and values, with ``generate``'s sampler; returns
+        ``vq.decode_indices(ids)``.  gumbel: explicit noise (steps, B, V); trace: a list that receives every step's
+        unfiltered logits (B, V).  graph=True: the step from the previous ids on the device to the next ids on the
+        device is captured once as a HIP graph and replayed ``num_patches - 1`` times (the start-token step stays
+        eager); without explicit noise the noise is then drawn inside the graph by torch's capture-aware generator.  The
+        captured step and its caches stay alive with the module until ``drop_decode_graph()`` (see ``_sample_graphed``)."""
+        if not tau > 0:
+            raise ValueError("sample needs a temperature tau > 0")
+        steps = self.vq.num_patches
+        text_hidden = self._context(text_hidden)
+        if gumbel is not None and gumbel.shape[0] < steps:
+            raise ValueError(f"gumbel holds {gumbel.shape[0]} steps of noise, the sample has {steps}")
+        if graph:
+            indices = self._sample_graphed(text_hidden, gumbel, trace, tau, p)
+            return self.vq.decode_indices(indices)
+        state = self.begin_decode(text_hidden)
+        b = state.batch
+        indices = torch.empty((b, steps), dtype=torch.long, device=state.device)
+        token = torch.zeros((b, 1), dtype=torch.long, device=state.device)
+        for i in range(steps):
+            logits = self.next_logits(state, token if i else None)
+            if trace is not None:
+                trace.append(logits.clone())
+            self._draw(logits, token, None if gumbel is None else gumbel[i], tau, p)
+            indices[:, i] = token[:, 0]
+        return self.vq.decode_indices(indices)
+
+    def drop_decode_graph(self):
+        """Free the captured step of ``sample(graph=True)`` with its caches and noise buffer (see ``_sample_graphed``)."""
+        _DECODE_GRAPHS.pop(self, None)
+
+    def _sample_graphed(self, text_hidden, gumbel, trace, tau, p):
+        """One captured step per module, kept in a table outside the module (weakly keyed: it goes with the module, is
+        not part of its attributes or state_dict, and copy.deepcopy does not meet it) until ``drop_decode_graph()`` or
+        a call whose key differs: it holds the DecoderState -- every layer's (B, capacity, 2*h*d) cache -- and the
+        noise buffer.  A captured graph replays against the ADDRESSES it was captured with, so the key holds, besides
+        the shapes and the sampler's settings, the train / eval mode, ops.GEMM_MODE and the data pointer of every
+        parameter and buffer: a module moved, cast or re-flattened is captured anew instead of replayed on stale
+        memory.  Parameter VALUES may change between calls (the graph reads them where they are)."""
+        steps = self.vq.num_patches
+        key = (tuple(text_hidden.shape), text_hidden.device, None if gumbel is None else tuple(gumbel.shape),
+               float(tau), float(p), steps, self.training, ops.GEMM_MODE,
+               tuple(t.data_ptr() for t in list(self.parameters()) + list(self.buffers())))
+        cached = _DECODE_GRAPHS.get(self)
+        if cached is None or cached["key"] != key:
+            cached = {"key": key, "state": self.begin_decode(text_hidden), "graph": None,
+                      "noise": None if gumbel is None else torch.empty_like(gumbel)}
+            b = cached["state"].batch
+            cached["token"] = torch.zeros((b, 1), dtype=torch.long, device=text_hidden.device)
+            _DECODE_GRAPHS[self] = cached
+        else:
+            self.begin_decode(text_hidden, out=cached["state"])   # new context K|V into the same buffers, position 0
+        state, token, noise = cached["state"], cached["token"], cached["noise"]
+        if noise is not None:
+            noise.copy_(gumbel)
+        indices = torch.empty((state.batch, steps), dtype=torch.long, device=state.device)
+        # the start-token step, eager
+        logits = self.next_logits(state, None)
+        if trace is not None:
+            trace.append(logits.clone())
+        self._draw(logits, token, None if noise is None else noise[0], tau, p)
+        indices[:, 0] = token[:, 0]
+        if steps == 1:
+            return indices
+
+        def step():
+            # previous ids (token) -> next ids (token, in place); position, pe row and noise row by the device position
+            if noise is not None:
+                g = noise.index_select(0, state.pos)[0]
+            else:
+                g = None
+            lg = self.next_logits(state, token)
+            if g is None:
+                g = -torch.empty_like(lg).exponential_().log()
+            self._draw(lg, token, g, tau, p)
+            return lg
+
+        if cached["graph"] is None:
+            first = token.clone()
+            check, ops.CHECK_INDICES = ops.CHECK_INDICES, False   # no host read inside a capture
+            try:
+                # warm-up on a side stream, then the capture, as amk.graphs.GraphedStep does; every run starts at
+                # position 1 (one stream, no parallel branches, no host reads in `step`)
+                side = torch.cuda.Stream()
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):
+                    for _ in range(3):
+                        state.set_position(1)
+                        step()
+                torch.cuda.current_stream().wait_stream(side)
+                state.set_position(1)
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    static_logits = step()
+                cached["graph"], cached["logits"] = graph, static_logits
+                self.decode_graph_captures += 1
+            finally:
+                ops.CHECK_INDICES = check
+            # the warm-up runs moved the position and the ids; the cache row they wrote is rewritten before it is read
+            state.set_position(1)
+            token.copy_(first)
+        for i in range(1, steps):
+            cached["graph"].replay()
+            if trace is not None:
+                trace.append(cached["logits"].clone())
+            indices[:, i] = token[:, 0]
+        state.host_pos = steps
+        return indices

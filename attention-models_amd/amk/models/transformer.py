@@ -1,6 +1,10 @@
 """Pre-LN encoder / decoder stacks around SoftmaxAttention (scaffolding of SURVEY.md section 8
 a15; reference: models/transformer.py:11-135), and the seq2seq ``Transformer`` on top of them (reference :138-228).
 Plain PyTorch except for the attention cores, the LayerNorms and the Linear layers.
+
+``Decoder.init_state`` / ``Decoder.step`` are the causal forward one row at a time against cached keys and values
+(models/decoding.py, the single-token kernel of csrc/attn_decode.hip); ``Transformer.begin_decode`` / ``next_logits`` /
+``sample`` build the trained model's sampling loop on them.  ``Transformer.generate`` stays the reference's loop.
 """
 import torch
 import torch.nn as nn
@@ -8,6 +12,7 @@ import torch.nn.functional as F
 
 from .. import ops
 from .attention import SoftmaxAttention
+from .decoding import DecoderState
 from .layers import Linear
 from .positional_encoding import PositionalEncoding
 
@@ -114,6 +119,51 @@ class Decoder(nn.Module):
             out = layer(out, context, context_mask=context_mask, causal_mask=causal_mask)
         return out
 
+    # ---- KV-cached decoding: the causal forward, one row per step (models/decoding.py, csrc/attn_decode.hip)
+    @torch.no_grad()
+    def init_state(self, context, capacity, context_mask=None, out=None):
+        """The state of a decode of up to ``capacity`` rows over ``context`` (B, L, dim): empty self-attention caches
+        and every layer's cross-attention K|V, projected here once.  out: a state of the same shapes to refill in place
+        (its buffers keep their addresses: a captured step stays valid)."""
+        if capacity < 1:
+            raise ValueError(f"capacity must be positive (got {capacity})")
+        cross = [layer.cross_attn.project_context(context) for layer in self.layers]
+        mask = ops._mask_u8(context_mask, (context.shape[0], context.shape[1]), "context_mask")
+        if out is not None:
+            if (out.capacity != capacity or out.cross_kv[0].shape != cross[0].shape or len(out.cross_kv) != len(cross)
+                    or (out.context_mask is None) != (mask is None)):
+                raise ValueError("init_state(out=...): the state was made for other shapes")
+            for dst, src in zip(out.cross_kv, cross):
+                dst.copy_(src)
+            if mask is not None:
+                out.context_mask.copy_(mask)
+            out.reset()
+            return out
+        b, width = context.shape[0], cross[0].shape[2]
+        self_kv = [torch.empty((b, capacity, width), device=context.device, dtype=torch.float32) for _ in self.layers]
+        ws = None
+        if context.is_cuda:   # one workspace for every decode call of a step: the calls are ordered on the stream
+            attn = self.layers[0].self_attn
+            need = max(ops.attention_decode_ws_floats(b, attn.num_heads, attn.dim_head, n) for n in (capacity, context.shape[1]))
+            ws = torch.empty((need,), device=context.device, dtype=torch.float32)
+        return DecoderState(self_kv, cross, mask, capacity, ws)
+
+    @torch.no_grad()
+    def step(self, x, state):
+        """``forward`` with the causal mask for ONE new row x (B, 1, dim) at the state's position: the row's keys and
+        values join the caches, the earlier rows are read from them.  The position itself is advanced by the caller
+        (``state.advance()``) once the row is through."""
+        if x.dim() != 3 or x.shape[1] != 1 or x.shape[0] != state.batch:
+            raise ValueError(f"step takes one row per sequence, (B={state.batch}, 1, dim); got {tuple(x.shape)}")
+        if state.host_pos >= state.capacity:
+            raise RuntimeError(f"the decode state is full: {state.host_pos} of {state.capacity} rows")
+        for layer, self_kv, cross_kv in zip(self.layers, state.self_kv, state.cross_kv):
+            x, y = layer.norm2(x, layer.self_attn.decode_step(layer.norm1(x), self_kv, state.pos, ws=state.ws))
+            x, y = layer.norm3(x, layer.cross_attn.decode_step(y, cross_kv, context_mask=state.context_mask, append=False,
+                                                                   ws=state.ws))
+            x = layer.feed_forward(y) + x
+        return x
+
 
 class Transformer(nn.Module):
     """Encoder-decoder over token ids (reference: models/transformer.py:138-228): embeddings + sinusoidal positions,
@@ -161,6 +211,46 @@ class Transformer(nn.Module):
             dec_out = self.decoder(dec_in=self.pos_enc(self.dec_input_proj(out_seq)), context=context)
             logits = self.linear(dec_out)
             last_token = F.gumbel_softmax(logits[:, -1, :], tau=1, hard=False).argmax(dim=-1)
+            if last_token[0] == end_token:
+                break
+            out_seq = torch.cat((out_seq, last_token.unsqueeze(1)), dim=1)
+        return out_seq
+
+    # ---- KV-cached causal decoding: ``forward``'s arithmetic row by row (``generate`` above stays the reference's loop)
+    @torch.no_grad()
+    def begin_decode(self, src_seq, capacity=256):
+        """Encode ``src_seq`` as ``forward`` does (enc_init_norm, the all-true context mask, enc_final_norm) and return
+        the decode state for up to ``capacity`` target positions."""
+        context_mask = torch.ones(src_seq.shape, dtype=torch.bool, device=src_seq.device)
+        src = self.enc_init_norm(self.pos_enc(self.enc_input_proj(src_seq)))
+        context = self.enc_final_norm(self.encoder(src, context_mask=context_mask))
+        return self.decoder.init_state(context, capacity, context_mask=context_mask)
+
+    @torch.no_grad()
+    def next_logits(self, state, prev_tokens):
+        """(B, n_classes) logits of the next position given the token ``prev_tokens`` (B,) at the state's position:
+        row ``pos`` of ``forward(src, tgt)`` with tgt[:, pos] = prev_tokens and the earlier columns as fed before."""
+        pe = self.pos_enc.pe.index_select(0, state.pos)
+        x = self.pos_enc.dropout(self.dec_input_proj(prev_tokens.view(-1, 1)) + pe)
+        out = self.decoder.step(self.dec_init_norm(x), state)
+        logits = self.linear(self.dec_final_norm(out))[:, 0, :]
+        state.advance()
+        return logits
+
+    @torch.no_grad()
+    def sample(self, src_seq, max_len, gumbel=None):
+        """``generate``'s loop on the trained (causal, normed) model with cached keys and values: start token 1,
+        Gumbel-argmax over the unfiltered logits, stop when the FIRST sequence draws the end token 2 (one host read per
+        step) or after ``max_len`` tokens.  gumbel: explicit noise (steps, B, n_classes)."""
+        if max_len is None or max_len < 1:
+            raise ValueError("Transformer.sample needs a positive max_len: it sizes the key / value cache")
+        end_token = 2
+        out_seq = torch.ones((src_seq.shape[0], 1), dtype=torch.long, device=src_seq.device)
+        state = self.begin_decode(src_seq, capacity=max_len)
+        for i in range(max_len):
+            logits = self.next_logits(state, out_seq[:, -1])
+            noise = gumbel[i] if gumbel is not None else -torch.empty_like(logits).exponential_().log()
+            last_token = (logits + noise).argmax(dim=-1)
             if last_token[0] == end_token:
                 break
             out_seq = torch.cat((out_seq, last_token.unsqueeze(1)), dim=1)

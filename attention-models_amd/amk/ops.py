@@ -454,6 +454,60 @@ def attention_fused_kv(q2, kv2, num_heads, dim_head, scale, key_mask=None, causa
     return _AttnFusedKV.apply(q2, kv2, km, cm, num_heads, dim_head, scale)
 
 
+def attention_decode(q2, kv_new2, cache, n_dev, num_heads, dim_head, scale, key_mask=None, ws=None):
+    """One new query row per (batch, head) against a key / value cache (csrc/attn_decode.hip), inference only.
+
+    q2 (B, 1, h*d); cache (B, capacity, 2*h*d) in the kv projection's '(kv h d)' columns; n_dev: int32 device tensor
+    holding the number of valid cache rows (the kernel reads it on the device, so a captured step replays for every
+    position).  kv_new2 (B, 1, 2*h*d): append mode -- row n of the cache becomes kv_new2 and the query attends rows
+    0 .. n.  kv_new2 None: read mode -- the query attends rows 0 .. n - 1, all `capacity` rows when n_dev is None.
+    key_mask: bool / uint8 (B, capacity), True = keep.  Returns (B, 1, h*d).  f32 outside autocast only.  q2, kv_new2
+    and cache are consumed in place and must be contiguous (the projection outputs are).  ws: a float32 workspace of at
+    least attention_decode_ws_floats(B, h, d, capacity) elements to reuse across calls (DecoderState keeps one); None
+    allocates one."""
+    if any(t is not None and t.requires_grad for t in (q2, kv_new2, cache)):
+        raise RuntimeError("attention_decode is inference only: it has no backward; call it under torch.no_grad() "
+                           "on tensors that do not require grad")
+    _require_device(q2, kv_new2, cache)
+    if torch.is_autocast_enabled():
+        raise RuntimeError("attention_decode runs on f32 tensors outside autocast; a bf16 cache is not implemented")
+    H, D = int(num_heads), int(dim_head)
+    B, capacity = cache.shape[0], cache.shape[1]
+    if q2.numel() != B * H * D or cache.shape[2] != 2 * H * D or not cache.is_contiguous():
+        raise RuntimeError(f"attention_decode: q {tuple(q2.shape)} / cache {tuple(cache.shape)} do not fit "
+                           f"B={B}, heads={H}, dim_head={D} (cache: contiguous (B, capacity, 2*h*d))")
+    if kv_new2 is not None and kv_new2.numel() != B * 2 * H * D:
+        raise RuntimeError(f"attention_decode: kv_new {tuple(kv_new2.shape)} is not one (kv h d) row per batch")
+    if n_dev is not None and (n_dev.dtype != torch.int32 or not n_dev.is_cuda or n_dev.numel() != 1):
+        raise RuntimeError("attention_decode: n_dev must be a one-element int32 device tensor")
+    if kv_new2 is not None and n_dev is None:
+        raise RuntimeError("attention_decode: append mode needs n_dev")
+    if not q2.is_contiguous() or (kv_new2 is not None and not kv_new2.is_contiguous()):
+        raise RuntimeError("attention_decode consumes q and kv_new in place: they must be contiguous")
+    q2c, kvn = q2, kv_new2
+    km = _mask_u8(key_mask, (B, capacity), "key_mask")
+    L = _lib.load()
+    o = torch.empty(q2.shape, device=q2.device, dtype=torch.float32)
+    need = L.amk_attn_decode_ws_floats(B, H, D, capacity)
+    if ws is None:
+        ws = torch.empty((need,), device=q2.device, dtype=torch.float32)
+    elif ws.dtype != torch.float32 or not ws.is_cuda or not ws.is_contiguous() or ws.numel() < need:
+        raise RuntimeError(f"attention_decode: ws must be a contiguous float32 device tensor of at least {need} elements")
+    hd = H * D
+    with _timed("attn_decode"):
+        rc = L.amk_attn_decode(_ptr(q2c), _ptr(kvn), ctypes.c_void_p(kvn.data_ptr() + 4 * hd) if kvn is not None else _NULL,
+                               _ptr(cache), ctypes.c_void_p(cache.data_ptr() + 4 * hd), _ptr(o), _ptr(ws), _ptr(n_dev), _ptr(km),
+                               B, H, D, capacity, hd, D, 2 * hd, D, capacity * 2 * hd, 2 * hd, D, hd, D,
+                               float(scale), _stream())
+    _lib.check(rc, "amk_attn_decode")
+    return o
+
+
+def attention_decode_ws_floats(B, num_heads, dim_head, capacity):
+    """Elements of the float32 workspace attention_decode needs at these sizes (amk_attn_decode_ws_floats)."""
+    return int(_lib.load().amk_attn_decode_ws_floats(int(B), int(num_heads), int(dim_head), int(capacity)))
+
+
 # ---------------------------------------------------------------------------- VQ lookup
 # vq_gather (indices_to_embeddings) takes indices from the caller: an index outside the codebook is never
 # dereferenced by the kernel, and with CHECK_INDICES the call raises IndexError like nn.Embedding does -- at

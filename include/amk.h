@@ -127,6 +127,52 @@ int amk_attn_fwd_x6_keep(const float* q, const float* k, const float* v, float* 
                          int64_t o_sb, int64_t o_st, int64_t o_sh,
                          float scale, void* stream);
 
+/* --------------------------------------------------------------------------
+ * Single-token attention against a key / value cache (KV-cached decoding), f32, with the cache append fused in
+ * (csrc/attn_decode.hip).  Replaces, for ONE new query row per (batch, head), the core of
+ * models/softmax_attention.py:62-76 as the sampling loop of models/parti.py:135-152 needs it once the keys and
+ * values of the earlier rows are kept instead of recomputed.  (Added within 0.4.0, same library version: an
+ * addition only, no signature changed.)
+ *
+ *   q, k_new, v_new  one row per (b, h), addressed  base + b*sb + h*sh + d: the (B, 1, h*D) and (B, 1, 2*h*D)
+ *                    projection outputs in place; k_new and v_new are two pointers into one '(kv h d)' row and
+ *                    share their strides (new_sb, new_sh).
+ *   k_cache, v_cache `capacity` rows per batch, addressed  b*c_sb + t*c_st + h*c_sh + d  (shared strides): one
+ *                    (B, capacity, 2*h*D) buffer per layer in the projection's own column layout.
+ *   n_dev            DEVICE int32: the number of rows already valid.  It lives in device memory so that one
+ *                    captured launch serves every position; the grid is sized from `capacity` on the host and
+ *                    workgroups whose key range is empty leave at once.  Never written by the kernel.
+ *   key_mask         uint8 (B, capacity) contiguous or NULL, 0 = fill -1e9 as in amk_attn_fwd; a row whose keys are
+ *                    all masked gets the uniform 1/J weights of that contract.
+ *
+ * Append mode (k_new, v_new non-null; self-attention): with n = *n_dev < capacity, row n of both caches becomes the
+ * new row and the query attends rows 0 .. n.  The workgroup that owns position n takes the row from k_new / v_new,
+ * never from the cache, and is the only writer of cache row n.  n_dev must not be NULL.
+ * Read mode (k_new, v_new NULL; cross-attention): the query attends rows 0 .. n - 1; n_dev NULL means
+ * n = capacity, with no device read.  The caches are not written.
+ * n out of range (append: n < 0 or n >= capacity; read: n < 1 or n > capacity): no byte outside the buffers is
+ * touched and o and the caches are left as they are.
+ *
+ * Scores are (q * scale) . k, the softmax runs in the exp2 domain, f32 throughout.  The keys are split over
+ * workgroups (64 per chunk); with more than one chunk each leaves (m, l, o[D]) in ws and a second launch on `stream`,
+ * one workgroup per (b, h), adds the partials in chunk order.  No f32 atomics on data, no counters and no memset:
+ * bitwise reproducible run to run and independent of B, and the workspace carries no state between calls (nothing
+ * in it needs zeroing).  An in-launch reduction on a ticket counter was measured against this form and lost
+ * (DESIGN.md section 4i); it is not in the library.
+ * ws: amk_attn_decode_ws_floats(B, H, D, capacity) floats, 16-byte aligned, contents undefined on entry and on
+ * return.
+ * D: a multiple of 32 from 32 to 256, else AMK_EUNSUPPORTED before any device work (as B or H above 65535).
+ * AMK_EINVAL: a null q, cache, o or ws, only one of k_new / v_new, append mode without n_dev, a non-positive size,
+ * a pointer not 16-byte aligned (n_dev: 4) or a stride that is not a multiple of 4 elements.
+ * -------------------------------------------------------------------------- */
+int64_t amk_attn_decode_ws_floats(int B, int H, int D, int capacity);
+int amk_attn_decode(const float* q, const float* k_new, const float* v_new, float* k_cache, float* v_cache,
+                    float* o, float* ws, const int32_t* n_dev, const uint8_t* key_mask,
+                    int B, int H, int D, int capacity,
+                    int64_t q_sb, int64_t q_sh, int64_t new_sb, int64_t new_sh,
+                    int64_t c_sb, int64_t c_st, int64_t c_sh, int64_t o_sb, int64_t o_sh,
+                    float scale, void* stream);
+
 /* Backward of amk_attn_fwd (autograd of the same reference lines).
  * Inputs: q,k,v,o,stats as in the forward, d_o (gradient of o, same addressing
  * as o with its own strides).  Outputs: dq (q-like), dk (k-like), dv (v-like),

@@ -1315,6 +1315,13 @@ def agent_attention(qkv2, conv_w, conv_b, num_heads, dim_head, pool, scale):
 
 
 # ---------------------------------------------------------------------------- SwiGLU gate
+def _c16(t):
+    """t contiguous on 16-byte aligned storage, as the float4 kernels read it: a copy only where a view's storage offset
+    (flat[1:1 + M * D].view(M, D)) or its strides force one."""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 class _SwiGLU(torch.autograd.Function):
     FWD, BWD = "amk_swiglu_fwd", "amk_swiglu_bwd"
 
@@ -1322,7 +1329,7 @@ class _SwiGLU(torch.autograd.Function):
     def forward(cls, ctx, ab):
         _require_device(ab)
         H = ab.shape[-1] // 2
-        ab2 = ab.contiguous().view(-1, 2 * H)
+        ab2 = _c16(ab).view(-1, 2 * H)
         M = ab2.shape[0]
         out = torch.empty((M, H), device=ab.device, dtype=torch.float32)
         L = _lib.load()
@@ -1335,7 +1342,7 @@ class _SwiGLU(torch.autograd.Function):
     def backward(cls, ctx, d_out):
         (ab2,) = ctx.saved_tensors
         M, H2 = ab2.shape
-        d_out = d_out.contiguous().view(M, H2 // 2)
+        d_out = _c16(d_out).view(M, H2 // 2)
         d_ab = torch.empty_like(ab2)
         L = _lib.load()
         _lib.check(getattr(L, cls.BWD)(_ptr(ab2), _ptr(d_out), M, H2 // 2, _ptr(d_ab), _stream()), cls.BWD)
@@ -1346,8 +1353,13 @@ class _GEGLU(_SwiGLU):
     FWD, BWD = "amk_geglu_fwd", "amk_geglu_bwd"
 
 
-def _f32_outside_autocast(fn, x):
-    """(the gate Functions are classmethod-based: no custom_fwd; under autocast the input is upcast here)"""
+def _f32_outside_autocast(fn, x, act):
+    """(the gate Functions are classmethod-based: no custom_fwd; under autocast the input is upcast here)
+    A half width that is no multiple of 4 has no kernel (16 bytes per lane): act(a) * b in torch, as layer_norm does
+    for the widths it has no kernel for."""
+    if x.shape[-1] % 8 != 0:
+        a, b = x.chunk(2, dim=-1)
+        return act(a) * b
     if torch.is_autocast_enabled():
         with torch.autocast("cuda", enabled=False):
             return fn(x.float())
@@ -1389,12 +1401,12 @@ def swiglu(ab):
     if MIXED_ELEMENTWISE and ab.dtype == torch.bfloat16 and ab.is_cuda and ab.shape[-1] % 8 == 0:
         with torch.autocast("cuda", enabled=False):
             return _SwiGLUBF16.apply(ab)
-    return _f32_outside_autocast(_SwiGLU.apply, ab)
+    return _f32_outside_autocast(_SwiGLU.apply, ab, torch.nn.functional.silu)
 
 
 def geglu(ab):
     """gelu(a) * b for ab = (..., 2H) = (a | b) (exact erf GELU): the transformer FFN gate."""
-    return _f32_outside_autocast(_GEGLU.apply, ab)
+    return _f32_outside_autocast(_GEGLU.apply, ab, torch.nn.functional.gelu)
 
 
 # ---------------------------------------------------------------------------- residual + LayerNorm
@@ -1445,12 +1457,12 @@ class _LayerNorm(torch.autograd.Function):
     def forward(ctx, x, weight, bias, eps):
         _require_device(x, weight, bias)
         D = x.shape[-1]
-        x2 = x.contiguous().view(-1, D)
+        x2 = _c16(x).view(-1, D)
         M = x2.shape[0]
         y = torch.empty_like(x2)
         mean = torch.empty((M,), device=x.device, dtype=torch.float32)
         rstd = torch.empty_like(mean)
-        w, b = weight.contiguous(), bias.contiguous()
+        w, b = _c16(weight), _c16(bias)
         L = _lib.load()
         _lib.check(L.amk_add_layernorm_fwd(_ptr(x2), _NULL, _ptr(w), _ptr(b), M, D, float(eps), _NULL, _ptr(y),
                                            _ptr(mean), _ptr(rstd), _stream()), "amk_add_layernorm_fwd")
@@ -1464,7 +1476,7 @@ class _LayerNorm(torch.autograd.Function):
     @_amp_bwd
     def backward(ctx, dy):
         x2, w, mean, rstd = ctx.saved_tensors
-        dx, dw, db = _ln_backward(dy.contiguous().view(x2.shape), x2, None, w, mean, rstd, ctx.params)
+        dx, dw, db = _ln_backward(_c16(dy).view(x2.shape), x2, None, w, mean, rstd, ctx.params)
         return dx.view(ctx.shape), dw, db, None
 
 
@@ -1476,14 +1488,14 @@ class _AddLayerNorm(torch.autograd.Function):
     def forward(ctx, x, res, weight, bias, eps):
         _require_device(x, res, weight, bias)
         D = x.shape[-1]
-        x2 = x.contiguous().view(-1, D)
-        r2 = res.contiguous().view(-1, D)
+        x2 = _c16(x).view(-1, D)
+        r2 = _c16(res).view(-1, D)
         M = x2.shape[0]
         h = torch.empty_like(x2)
         y = torch.empty_like(x2)
         mean = torch.empty((M,), device=x.device, dtype=torch.float32)
         rstd = torch.empty_like(mean)
-        w, b = weight.contiguous(), bias.contiguous()
+        w, b = _c16(weight), _c16(bias)
         L = _lib.load()
         _lib.check(L.amk_add_layernorm_fwd(_ptr(x2), _ptr(r2), _ptr(w), _ptr(b), M, D, float(eps), _ptr(h), _ptr(y),
                                            _ptr(mean), _ptr(rstd), _stream()), "amk_add_layernorm_fwd")
@@ -1502,8 +1514,8 @@ class _AddLayerNorm(torch.autograd.Function):
             if dh_in is None:
                 return None, None, None, None, None
             return dh_in, dh_in, None, None, None
-        dh2 = dh_in.contiguous().view(h.shape) if dh_in is not None else None
-        dh, dw, db = _ln_backward(dy.contiguous().view(h.shape), h, dh2, w, mean, rstd, ctx.params)
+        dh2 = _c16(dh_in).view(h.shape) if dh_in is not None else None
+        dh, dw, db = _ln_backward(_c16(dy).view(h.shape), h, dh2, w, mean, rstd, ctx.params)
         dh = dh.view(ctx.shape)
         return dh, dh, dw, db, None
 
@@ -1593,10 +1605,11 @@ def add_layer_norm(x, res, weight, bias, eps=1e-5, branch=False):
 
 # ---------------------------------------------------------------------------- Linear with bias
 def colsum(x2):
-    """Column sums of a contiguous (M, N) matrix (the bias gradient of a Linear)."""
+    """Column sums of an (M, N) matrix (the bias gradient of a Linear)."""
     M, N = x2.shape
     if N % 4 != 0 or N > 1024:  # wide matrices: torch's reduction is as fast (measured at N = 2736: 71 vs 88 us)
         return x2.sum(0)
+    x2 = _c16(x2)
     L = _lib.load()
     part = torch.empty((L.amk_rowsum_num_partials(M), N), device=x2.device, dtype=torch.float32)
     _lib.check(L.amk_colsum(_ptr(x2), M, N, _ptr(part), _stream()), "amk_colsum")

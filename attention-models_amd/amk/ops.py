@@ -2400,65 +2400,6 @@ def _row_major_view(t2, mult=4):
     return t2
 
 
-class _LinearCrossEntropy(torch.autograd.Function):
-    """mean over the rows with target != ignore_index of logsumexp(x W^T) - (x W^T)[target]; saves lse, the compacted row
-    list and the device-side count -- the number of valid rows is never read on the host."""
-
-    @staticmethod
-    def forward(ctx, x, weight, target, ignore_index):
-        K = x.shape[-1]
-        x2 = _row_major_view(x.reshape(-1, K))
-        w2 = _row_major_view(weight)
-        t = target.reshape(-1).contiguous()
-        M, V = x2.shape[0], w2.shape[0]
-        if t.shape[0] != M or w2.shape[1] != K:
-            raise RuntimeError(f"linear_cross_entropy: x {tuple(x.shape)}, weight {tuple(weight.shape)}, target "
-                               f"{tuple(target.shape)} do not fit")
-        L = _lib.load()
-        dev = x2.device
-        nbytes = L.amk_ce_head_fwd_ws_bytes(M, V, K)
-        ws = torch.empty(max(nbytes // 4, 4), device=dev, dtype=torch.float32)
-        loss = torch.empty((), device=dev, dtype=torch.float32)
-        lse = torch.empty(M, device=dev, dtype=torch.float32)
-        rows = torch.empty(M, device=dev, dtype=torch.int32)
-        count = torch.empty(1, device=dev, dtype=torch.int32)
-        with _timed(f"ce_head_fwd M{M} V{V} K{K}"):
-            _lib.check(L.amk_ce_head_fwd(_ptr(x2), x2.stride(0), _ptr(w2), w2.stride(0), _ptr(t), int(ignore_index), M, V, K,
-                                         _ptr(loss), _ptr(lse), _ptr(rows), _ptr(count), _ptr(ws), nbytes, _stream()),
-                       "amk_ce_head_fwd")
-        ctx.save_for_backward(x2, w2, t, lse, rows, count)
-        ctx.ignore_index = int(ignore_index)
-        ctx.x_shape = x.shape
-        ctx.weight = weight
-        return loss
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, d_loss):
-        x2, w2, t, lse, rows, count = ctx.saved_tensors
-        M, K = x2.shape
-        V = w2.shape[0]
-        L = _lib.load()
-        dev = x2.device
-        d = d_loss.reshape(1).to(torch.float32).contiguous()   # stays on the device
-        dx = torch.empty(M, K, device=dev, dtype=torch.float32)
-        wr, wv = _claim(ctx.weight) if ctx.needs_input_grad[1] else (None, None)
-        if wv is not None and (wv.stride(-1) != 1 or wv.data_ptr() % 16 or wv.shape != w2.shape or wv.stride(0) % 4):
-            wr, wv = None, None   # (not reached with the reducer's views: ALIGN-ed, contiguous)
-        dw = wv if wv is not None else torch.empty(V, K, device=dev, dtype=torch.float32)
-        nbytes = L.amk_ce_head_bwd_ws_bytes(M, V, K)
-        ws = torch.empty(max(nbytes // 4, 4), device=dev, dtype=torch.float32)
-        with _timed(f"ce_head_bwd M{M} V{V} K{K}"):
-            _lib.check(L.amk_ce_head_bwd(_ptr(x2), x2.stride(0), _ptr(w2), w2.stride(0), _ptr(t), ctx.ignore_index, M, V, K,
-                                         _ptr(d), _ptr(lse), _ptr(rows), _ptr(count), _ptr(dx), dx.stride(0),
-                                         _ptr(dw), dw.stride(0), _ptr(ws), nbytes, _stream()),
-                       "amk_ce_head_bwd")
-        if wv is not None:
-            wr.wrote(ctx.weight)
-            dw = None
-        return dx.view(ctx.x_shape), dw, None, None
-
-
 def _bias_view(bias, V):
     """bias (V,) f32 as the kernels take it: contiguous and 16-byte aligned (copied when it is not)."""
     if bias.dtype != torch.float32 or bias.shape != (V,):
@@ -2479,195 +2420,89 @@ def _claim_vec(p, V):
     return r, v
 
 
-class _LinearCrossEntropyBias(torch.autograd.Function):
-    """_LinearCrossEntropy with z = x W^T + b (amk_ce_head_bias_fwd / _bwd): the bias is the first term of each logit's
-    chain; db = the column sums of the G that dw reads, f32, into the reducer's bucket when it can be claimed."""
+# The two precisions of the head, indexed by `bf16`: (cast of x, cast of the weight, the multiple K and the row strides
+# must have, dtype of dx and of the backward workspace G, the entry points [2 * has_bias + is_backward], event prefix).
+# x is cast to bf16 if it arrives in f32, the weight goes through _w16 (the optimizer's bf16 shadow when it is current).
+_CE_HEADS = (
+    (lambda x: x, lambda w: w, 4, torch.float32,
+     ("amk_ce_head_fwd", "amk_ce_head_bwd", "amk_ce_head_bias_fwd", "amk_ce_head_bias_bwd"), ""),
+    (lambda x: x.to(torch.bfloat16), _w16, 8, torch.bfloat16,
+     ("amk_ce_head_bf16_fwd", "amk_ce_head_bf16_bwd", "amk_ce_head_bias_bf16_fwd", "amk_ce_head_bias_bf16_bwd"), "bf16_"),
+)
+
+
+class _LinearCrossEntropy(torch.autograd.Function):
+    """mean over the rows with target != ignore_index of logsumexp(x W^T + b) - (x W^T + b)[target], b = 0 without a
+    bias; f32 (csrc/ce_head.hip) or, with bf16, on bf16 operands (csrc/ce_head_bf16.hip).  loss and lse in f32, dx in x's
+    dtype, dw and db in f32 -- into the reducer's bucket when they can be claimed.  Saves the prepared x and w, the bias,
+    target, lse, the compacted row list and the device-side count only -- the number of valid rows is never read on the
+    host."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, target, ignore_index):
+    def forward(ctx, x, weight, bias, target, ignore_index, bf16):
+        cast_x, cast_w, mult, _, names, ev = _CE_HEADS[bf16]
         K = x.shape[-1]
-        x2 = _row_major_view(x.reshape(-1, K))
-        w2 = _row_major_view(weight)
+        x2 = _row_major_view(cast_x(x.reshape(-1, K)), mult)
+        w2 = _row_major_view(cast_w(weight), mult)
         t = target.reshape(-1).contiguous()
         M, V = x2.shape[0], w2.shape[0]
         if t.shape[0] != M or w2.shape[1] != K:
             raise RuntimeError(f"linear_cross_entropy: x {tuple(x.shape)}, weight {tuple(weight.shape)}, target "
                                f"{tuple(target.shape)} do not fit")
-        b1 = _bias_view(bias, V)
+        b1 = () if bias is None else (_bias_view(bias, V),)
         L = _lib.load()
         dev = x2.device
-        nbytes = L.amk_ce_head_fwd_ws_bytes(M, V, K)
+        nbytes = getattr(L, names[0] + "_ws_bytes")(M, V, K)
         ws = torch.empty(max(nbytes // 4, 4), device=dev, dtype=torch.float32)
         loss = torch.empty((), device=dev, dtype=torch.float32)
         lse = torch.empty(M, device=dev, dtype=torch.float32)
         rows = torch.empty(M, device=dev, dtype=torch.int32)
         count = torch.empty(1, device=dev, dtype=torch.int32)
-        with _timed(f"ce_head_bias_fwd M{M} V{V} K{K}"):
-            _lib.check(L.amk_ce_head_bias_fwd(_ptr(x2), x2.stride(0), _ptr(w2), w2.stride(0), _ptr(b1), _ptr(t),
-                                              int(ignore_index), M, V, K, _ptr(loss), _ptr(lse), _ptr(rows), _ptr(count),
-                                              _ptr(ws), nbytes, _stream()), "amk_ce_head_bias_fwd")
-        ctx.save_for_backward(x2, w2, b1, t, lse, rows, count)
-        ctx.ignore_index = int(ignore_index)
-        ctx.x_shape = x.shape
+        fn = names[2 * len(b1)]
+        with _timed(f"{ev}ce_head{'_bias' if b1 else ''}_fwd M{M} V{V} K{K}"):
+            _lib.check(getattr(L, fn)(_ptr(x2), x2.stride(0), _ptr(w2), w2.stride(0), *map(_ptr, b1), _ptr(t),
+                                      int(ignore_index), M, V, K, _ptr(loss), _ptr(lse), _ptr(rows), _ptr(count), _ptr(ws),
+                                      nbytes, _stream()), fn)
+        ctx.save_for_backward(x2, w2, *b1, t, lse, rows, count)
+        ctx.ignore_index, ctx.bf16 = int(ignore_index), bf16
+        ctx.x_shape, ctx.x_dtype = x.shape, x.dtype
         ctx.weight, ctx.bias = weight, bias
         return loss
 
     @staticmethod
     @once_differentiable
     def backward(ctx, d_loss):
-        x2, w2, b1, t, lse, rows, count = ctx.saved_tensors
+        x2, w2, *b1, t, lse, rows, count = ctx.saved_tensors
+        _, _, mult, dtype, names, ev = _CE_HEADS[ctx.bf16]
         M, K = x2.shape
         V = w2.shape[0]
         L = _lib.load()
         dev = x2.device
         d = d_loss.reshape(1).to(torch.float32).contiguous()   # stays on the device
-        dx = torch.empty(M, K, device=dev, dtype=torch.float32)
+        dx = torch.empty(M, K, device=dev, dtype=dtype)
         wr, wv = _claim(ctx.weight) if ctx.needs_input_grad[1] else (None, None)
-        if wv is not None and (wv.stride(-1) != 1 or wv.data_ptr() % 16 or wv.shape != w2.shape or wv.stride(0) % 4):
+        if wv is not None and (wv.stride(-1) != 1 or wv.data_ptr() % 16 or wv.shape != w2.shape or wv.stride(0) % mult
+                               or wv.dtype != torch.float32):
             wr, wv = None, None   # (not reached with the reducer's views: ALIGN-ed, contiguous)
         dw = wv if wv is not None else torch.empty(V, K, device=dev, dtype=torch.float32)
-        br, bv = _claim_vec(ctx.bias, V) if ctx.needs_input_grad[2] else (None, None)
-        db = bv if bv is not None else torch.empty(V, device=dev, dtype=torch.float32)
-        nbytes = L.amk_ce_head_bwd_ws_bytes(M, V, K)
-        ws = torch.empty(max(nbytes // 4, 4), device=dev, dtype=torch.float32)
-        with _timed(f"ce_head_bias_bwd M{M} V{V} K{K}"):
-            _lib.check(L.amk_ce_head_bias_bwd(_ptr(x2), x2.stride(0), _ptr(w2), w2.stride(0), _ptr(b1), _ptr(t),
-                                              ctx.ignore_index, M, V, K, _ptr(d), _ptr(lse), _ptr(rows), _ptr(count),
-                                              _ptr(dx), dx.stride(0), _ptr(dw), dw.stride(0), _ptr(db), _ptr(ws), nbytes,
-                                              _stream()), "amk_ce_head_bias_bwd")
+        br, bv, db = None, None, ()
+        if b1:
+            br, bv = _claim_vec(ctx.bias, V) if ctx.needs_input_grad[2] else (None, None)
+            db = (bv if bv is not None else torch.empty(V, device=dev, dtype=torch.float32),)
+        nbytes = getattr(L, names[1] + "_ws_bytes")(M, V, K)
+        ws = torch.empty(max(nbytes, 16) // dx.element_size(), device=dev, dtype=dtype)
+        fn = names[2 * len(b1) + 1]
+        with _timed(f"{ev}ce_head{'_bias' if b1 else ''}_bwd M{M} V{V} K{K}"):
+            _lib.check(getattr(L, fn)(_ptr(x2), x2.stride(0), _ptr(w2), w2.stride(0), *map(_ptr, b1), _ptr(t),
+                                      ctx.ignore_index, M, V, K, _ptr(d), _ptr(lse), _ptr(rows), _ptr(count), _ptr(dx),
+                                      dx.stride(0), _ptr(dw), dw.stride(0), *map(_ptr, db), _ptr(ws), nbytes, _stream()), fn)
         if wv is not None:
             wr.wrote(ctx.weight)
             dw = None
         if bv is not None:
             br.wrote(ctx.bias)
-            db = None
-        return dx.view(ctx.x_shape), dw, db, None, None
-
-
-class _LinearCrossEntropyBiasBF16(torch.autograd.Function):
-    """_LinearCrossEntropyBF16 with z = x W^T + b (amk_ce_head_bias_bf16_fwd / _bwd): the bias stays the f32 master, db in
-    f32."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, target, ignore_index):
-        K = x.shape[-1]
-        x16 = _row_major_view(x.reshape(-1, K).to(torch.bfloat16), 8)
-        w16 = _row_major_view(_w16(weight), 8)
-        t = target.reshape(-1).contiguous()
-        M, V = x16.shape[0], w16.shape[0]
-        if t.shape[0] != M or w16.shape[1] != K:
-            raise RuntimeError(f"linear_cross_entropy: x {tuple(x.shape)}, weight {tuple(weight.shape)}, target "
-                               f"{tuple(target.shape)} do not fit")
-        b1 = _bias_view(bias, V)
-        L = _lib.load()
-        dev = x16.device
-        nbytes = L.amk_ce_head_bf16_fwd_ws_bytes(M, V, K)
-        ws = torch.empty(max(nbytes // 4, 4), device=dev, dtype=torch.float32)
-        loss = torch.empty((), device=dev, dtype=torch.float32)
-        lse = torch.empty(M, device=dev, dtype=torch.float32)
-        rows = torch.empty(M, device=dev, dtype=torch.int32)
-        count = torch.empty(1, device=dev, dtype=torch.int32)
-        with _timed(f"bf16_ce_head_bias_fwd M{M} V{V} K{K}"):
-            _lib.check(L.amk_ce_head_bias_bf16_fwd(_ptr(x16), x16.stride(0), _ptr(w16), w16.stride(0), _ptr(b1), _ptr(t),
-                                                   int(ignore_index), M, V, K, _ptr(loss), _ptr(lse), _ptr(rows),
-                                                   _ptr(count), _ptr(ws), nbytes, _stream()), "amk_ce_head_bias_bf16_fwd")
-        ctx.save_for_backward(x16, w16, b1, t, lse, rows, count)
-        ctx.ignore_index = int(ignore_index)
-        ctx.x_shape, ctx.x_dtype = x.shape, x.dtype
-        ctx.weight, ctx.bias = weight, bias
-        return loss
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, d_loss):
-        x16, w16, b1, t, lse, rows, count = ctx.saved_tensors
-        M, K = x16.shape
-        V = w16.shape[0]
-        L = _lib.load()
-        dev = x16.device
-        d = d_loss.reshape(1).to(torch.float32).contiguous()   # stays on the device
-        dx = torch.empty(M, K, device=dev, dtype=torch.bfloat16)
-        wr, wv = _claim(ctx.weight) if ctx.needs_input_grad[1] else (None, None)
-        if wv is not None and (wv.stride(-1) != 1 or wv.data_ptr() % 16 or wv.shape != w16.shape or wv.stride(0) % 8
-                               or wv.dtype != torch.float32):
-            wr, wv = None, None   # (not reached with the reducer's views: ALIGN-ed, contiguous)
-        dw = wv if wv is not None else torch.empty(V, K, device=dev, dtype=torch.float32)
-        br, bv = _claim_vec(ctx.bias, V) if ctx.needs_input_grad[2] else (None, None)
-        db = bv if bv is not None else torch.empty(V, device=dev, dtype=torch.float32)
-        nbytes = L.amk_ce_head_bf16_bwd_ws_bytes(M, V, K)
-        ws = torch.empty(max(nbytes // 2, 8), device=dev, dtype=torch.bfloat16)
-        with _timed(f"bf16_ce_head_bias_bwd M{M} V{V} K{K}"):
-            _lib.check(L.amk_ce_head_bias_bf16_bwd(_ptr(x16), x16.stride(0), _ptr(w16), w16.stride(0), _ptr(b1), _ptr(t),
-                                                   ctx.ignore_index, M, V, K, _ptr(d), _ptr(lse), _ptr(rows), _ptr(count),
-                                                   _ptr(dx), dx.stride(0), _ptr(dw), dw.stride(0), _ptr(db), _ptr(ws),
-                                                   nbytes, _stream()), "amk_ce_head_bias_bf16_bwd")
-        if wv is not None:
-            wr.wrote(ctx.weight)
-            dw = None
-        if bv is not None:
-            br.wrote(ctx.bias)
-            db = None
-        return dx.view(ctx.x_shape).to(ctx.x_dtype), dw, db, None, None
-
-
-class _LinearCrossEntropyBF16(torch.autograd.Function):
-    """_LinearCrossEntropy under bf16 autocast (csrc/ce_head_bf16.hip): x cast to bf16 if it arrives in f32, the weight
-    through _w16 (the optimizer's bf16 shadow when it is current); loss and lse in f32, dx in x's dtype, dw in f32 --
-    into the reducer's bucket when it can be claimed.  Saves x16, w16, target, lse, rows and count only."""
-
-    @staticmethod
-    def forward(ctx, x, weight, target, ignore_index):
-        K = x.shape[-1]
-        x16 = _row_major_view(x.reshape(-1, K).to(torch.bfloat16), 8)
-        w16 = _row_major_view(_w16(weight), 8)
-        t = target.reshape(-1).contiguous()
-        M, V = x16.shape[0], w16.shape[0]
-        if t.shape[0] != M or w16.shape[1] != K:
-            raise RuntimeError(f"linear_cross_entropy: x {tuple(x.shape)}, weight {tuple(weight.shape)}, target "
-                               f"{tuple(target.shape)} do not fit")
-        L = _lib.load()
-        dev = x16.device
-        nbytes = L.amk_ce_head_bf16_fwd_ws_bytes(M, V, K)
-        ws = torch.empty(max(nbytes // 4, 4), device=dev, dtype=torch.float32)
-        loss = torch.empty((), device=dev, dtype=torch.float32)
-        lse = torch.empty(M, device=dev, dtype=torch.float32)
-        rows = torch.empty(M, device=dev, dtype=torch.int32)
-        count = torch.empty(1, device=dev, dtype=torch.int32)
-        with _timed(f"bf16_ce_head_fwd M{M} V{V} K{K}"):
-            _lib.check(L.amk_ce_head_bf16_fwd(_ptr(x16), x16.stride(0), _ptr(w16), w16.stride(0), _ptr(t), int(ignore_index),
-                                              M, V, K, _ptr(loss), _ptr(lse), _ptr(rows), _ptr(count), _ptr(ws), nbytes,
-                                              _stream()), "amk_ce_head_bf16_fwd")
-        ctx.save_for_backward(x16, w16, t, lse, rows, count)
-        ctx.ignore_index = int(ignore_index)
-        ctx.x_shape, ctx.x_dtype = x.shape, x.dtype
-        ctx.weight = weight
-        return loss
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, d_loss):
-        x16, w16, t, lse, rows, count = ctx.saved_tensors
-        M, K = x16.shape
-        V = w16.shape[0]
-        L = _lib.load()
-        dev = x16.device
-        d = d_loss.reshape(1).to(torch.float32).contiguous()   # stays on the device
-        dx = torch.empty(M, K, device=dev, dtype=torch.bfloat16)
-        wr, wv = _claim(ctx.weight) if ctx.needs_input_grad[1] else (None, None)
-        if wv is not None and (wv.stride(-1) != 1 or wv.data_ptr() % 16 or wv.shape != w16.shape or wv.stride(0) % 8
-                               or wv.dtype != torch.float32):
-            wr, wv = None, None   # (not reached with the reducer's views: ALIGN-ed, contiguous)
-        dw = wv if wv is not None else torch.empty(V, K, device=dev, dtype=torch.float32)
-        nbytes = L.amk_ce_head_bf16_bwd_ws_bytes(M, V, K)
-        ws = torch.empty(max(nbytes // 2, 8), device=dev, dtype=torch.bfloat16)
-        with _timed(f"bf16_ce_head_bwd M{M} V{V} K{K}"):
-            _lib.check(L.amk_ce_head_bf16_bwd(_ptr(x16), x16.stride(0), _ptr(w16), w16.stride(0), _ptr(t), ctx.ignore_index,
-                                              M, V, K, _ptr(d), _ptr(lse), _ptr(rows), _ptr(count), _ptr(dx), dx.stride(0),
-                                              _ptr(dw), dw.stride(0), _ptr(ws), nbytes, _stream()), "amk_ce_head_bf16_bwd")
-        if wv is not None:
-            wr.wrote(ctx.weight)
-            dw = None
-        return dx.view(ctx.x_shape).to(ctx.x_dtype), dw, None, None
+            db = ()
+        return dx.view(ctx.x_shape).to(ctx.x_dtype), dw, db[0] if db else None, None, None, None
 
 
 def linear_cross_entropy(x, weight, target, ignore_index=-100, bias=None):
@@ -2685,9 +2520,5 @@ def linear_cross_entropy(x, weight, target, ignore_index=-100, bias=None):
         raise RuntimeError(f"linear_cross_entropy: target must be int64; got {target.dtype}")
     if bf16:   # bf16 operands (x cast, the weight's bf16 shadow), f32 loss, dx in x's dtype, dw in f32
         with torch.autocast("cuda", enabled=False):
-            if bias is not None:
-                return _LinearCrossEntropyBiasBF16.apply(x, weight, bias, target, ignore_index)
-            return _LinearCrossEntropyBF16.apply(x, weight, target, ignore_index)
-    if bias is not None:
-        return _LinearCrossEntropyBias.apply(x, weight, bias, target, ignore_index)
-    return _LinearCrossEntropy.apply(x, weight, target, ignore_index)
+            return _LinearCrossEntropy.apply(x, weight, bias, target, ignore_index, True)
+    return _LinearCrossEntropy.apply(x, weight, bias, target, ignore_index, False)

@@ -37,15 +37,14 @@
 // A target that is neither ignore_index nor in [0, V) is never used as an index: its row is counted (count includes
 // it), its loss is NaN -- so the mean is NaN -- and it receives and gives no gradient (its G row is zero, its dx row is
 // zero); d_loss / count still divides by the count that includes it.
-#include "amk_common.h"
+#include "ce_head_common.h"
 
 namespace amk_ce {
 
-constexpr int TR = 128;      // B-side tile: 32 per wave, the lane's index
-constexpr int TA = 128;      // A-side tile: every wave sees all of it (4 MFMA blocks of 32)
+using namespace amk_ce_common;   // TR, TA, SCAN, the limits, slices, the host drivers
+
 constexpr int BK = 16;       // contraction depth per LDS stage
 constexpr int LD = 132;      // LDS row stride (floats): 16-byte aligned rows
-constexpr int SCAN = 1024;   // threads of ce_compact / ce_finalize
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
@@ -453,94 +452,43 @@ __global__ __launch_bounds__(DBC * DBQ) void ce_bwd_db_kernel(const float* __res
   if (q == 0 && v < V) db[v] = red[0][c];
 }
 
-// vocabulary slices of the forward: enough workgroups for the machine when there are few row tiles; whole 128-word
-// tiles per slice, no empty slice
-static void slices(int64_t M, int V, int* nsplit, int* vper) {
-  const int64_t nrt = (M + TR - 1) / TR;
-  const int nvt = (V + TA - 1) / TA;
-  int64_t want = (512 + nrt - 1) / nrt;
-  if (want > 16) want = 16;
-  if (want > nvt) want = nvt;
-  if (want < 1) want = 1;
-  const int per = (int)((nvt + want - 1) / want);
-  *vper = per * TA;
-  *nsplit = (nvt + per - 1) / per;
-}
-
-static int64_t ldg_of(int V) { return ((int64_t)V + TA - 1) / TA * TA; }
+// this file, as the drivers of ce_head_common.h see it
+struct Head {
+  using T = float;
+  static constexpr int MULT = 4;
+  static constexpr decltype(&ce_fwd_kernel<false>) fwd[2] = {ce_fwd_kernel<false>, ce_fwd_kernel<true>};
+  static constexpr decltype(&ce_bwd_g_kernel<false>) bwd_g[2] = {ce_bwd_g_kernel<false>, ce_bwd_g_kernel<true>};
+  static constexpr auto zero_rows = &ce_zero_rows_kernel;
+  static constexpr auto bwd_dx = &ce_bwd_dx_kernel;
+  static constexpr auto bwd_dw = &ce_bwd_dw_kernel;
+  static constexpr auto bwd_db = &ce_bwd_db_kernel;
+  static constexpr int DB_COLS = DBC, DB_THREADS = DBC * DBQ;
+};
 
 }  // namespace amk_ce
 
+// the one copy of the two kernels both heads launch
+void amk_ce_common::ce_compact(hipStream_t st, const int64_t* target, int64_t ignore_index, int M, int32_t* rows, int32_t* count) {
+  hipLaunchKernelGGL(amk_ce::ce_compact_kernel, dim3(1), dim3(SCAN), 0, st, target, ignore_index, M, rows, count);
+}
+
+void amk_ce_common::ce_finalize(hipStream_t st, const float* pm, const float* ps, const float* pz, const int64_t* target,
+                                const int32_t* rows, const int32_t* count, int V, int nsplit, int vper, float* lse, float* loss) {
+  hipLaunchKernelGGL(amk_ce::ce_finalize_kernel, dim3(1), dim3(SCAN), 0, st, pm, ps, pz, target, rows, count, V, nsplit, vper, lse,
+                     loss);
+}
+
 using namespace amk_ce;
 
-constexpr int64_t CE_MAX_M = 1ll << 24;   // count stays exact in f32; rows are int32
-constexpr int CE_MAX_V = 1 << 22;
-constexpr int CE_MAX_K = 1 << 16;
+extern "C" int64_t amk_ce_head_fwd_ws_bytes(int64_t M, int V, int K) { return ce_fwd_ws_bytes(M, V, K); }
 
-static bool ce_a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static bool ce_a4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-static bool ce_a8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
-
-extern "C" int64_t amk_ce_head_fwd_ws_bytes(int64_t M, int V, int K) {
-  if (M <= 0 || V <= 0 || K <= 0 || M > CE_MAX_M || V > CE_MAX_V) return 0;
-  int ns, vper;
-  slices(M, V, &ns, &vper);
-  return 3 * M * ns * (int64_t)sizeof(float);
-}
-
-extern "C" int64_t amk_ce_head_bwd_ws_bytes(int64_t M, int V, int K) {
-  if (M <= 0 || V <= 0 || K <= 0 || M > CE_MAX_M || V > CE_MAX_V) return 0;
-  return M * ldg_of(V) * (int64_t)sizeof(float);
-}
-
-static int ce_check_common(const char* who, int64_t ldx, int64_t ldw, int64_t M, int V, int K) {
-  AMK_CHECK_ARG(M > 0 && V > 0 && K > 0, "%s: non-positive size M=%lld V=%d K=%d", who, (long long)M, V, K);
-  AMK_CHECK_SUPPORTED(K % 4 == 0, "%s: K=%d must be a multiple of 4", who, K);
-  AMK_CHECK_SUPPORTED(ldx % 4 == 0 && ldw % 4 == 0, "%s: ldx=%lld and ldw=%lld must be multiples of 4", who, (long long)ldx,
-                      (long long)ldw);
-  AMK_CHECK_ARG(ldx >= K && ldw >= K, "%s: a leading dimension is below K", who);
-  AMK_CHECK_SUPPORTED(M <= CE_MAX_M && V <= CE_MAX_V && K <= CE_MAX_K,
-                      "%s: operand above the limits (M <= 2^24, V <= 2^22, K <= 2^16): M=%lld V=%d K=%d", who, (long long)M, V, K);
-  const int64_t nrt = (M + TR - 1) / TR, widest = ldg_of(V) / TA > (K + TA - 1) / TA ? ldg_of(V) / TA : (K + TA - 1) / TA;
-  AMK_CHECK_SUPPORTED(nrt * widest < (1ll << 31), "%s: grid too large (M=%lld V=%d K=%d)", who, (long long)M, V, K);
-  return AMK_OK;
-}
-
-// bias == nullptr: the biasless head (who names the entry point in the messages)
-static int ce_fwd_impl(const char* who, const float* x, int64_t ldx, const float* w, int64_t ldw, const int64_t* target,
-                       int64_t ignore_index, int64_t M, int V, int K, float* loss, float* lse, int32_t* rows, int32_t* count,
-                       void* ws, int64_t ws_bytes, void* stream, const float* bias) {
-  AMK_CHECK_ARG(x && w && target && loss && lse && rows && count && ws, "%s: null pointer", who);
-  const int rc = ce_check_common(who, ldx, ldw, M, V, K);
-  if (rc != AMK_OK) return rc;
-  AMK_CHECK_ARG(ce_a16(x) && ce_a16(w) && ce_a16(ws) && ce_a8(target) && ce_a4(loss) && ce_a4(lse) && ce_a4(rows) && ce_a4(count),
-                "%s: misaligned pointer (x, w, ws: 16 bytes; target: 8; loss, lse, rows, count: 4)", who);
-  AMK_CHECK_ARG(ws_bytes >= amk_ce_head_fwd_ws_bytes(M, V, K), "%s: workspace of %lld bytes, %lld needed", who,
-                (long long)ws_bytes, (long long)amk_ce_head_fwd_ws_bytes(M, V, K));
-  int ns, vper;
-  slices(M, V, &ns, &vper);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  float* pm = static_cast<float*>(ws);
-  float* ps = pm + M * ns;
-  float* pz = ps + M * ns;
-  const int64_t nrt = (M + TR - 1) / TR;
-  hipLaunchKernelGGL(ce_compact_kernel, dim3(1), dim3(SCAN), 0, st, target, ignore_index, (int)M, rows, count);
-  if (bias)
-    hipLaunchKernelGGL(ce_fwd_kernel<true>, dim3((unsigned)(nrt * ns)), dim3(256), 0, st, x, ldx, w, ldw, target, V, K, ns, vper,
-                       rows, count, pm, ps, pz, bias);
-  else
-    hipLaunchKernelGGL(ce_fwd_kernel<false>, dim3((unsigned)(nrt * ns)), dim3(256), 0, st, x, ldx, w, ldw, target, V, K, ns, vper,
-                       rows, count, pm, ps, pz, bias);
-  hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(SCAN), 0, st, pm, ps, pz, target, rows, count, V, ns, vper, lse, loss);
-  AMK_CHECK_LAUNCH(who);
-  return AMK_OK;
-}
+extern "C" int64_t amk_ce_head_bwd_ws_bytes(int64_t M, int V, int K) { return ce_bwd_ws_bytes(M, V, K, sizeof(Head::T)); }
 
 extern "C" int amk_ce_head_fwd(const float* x, int64_t ldx, const float* w, int64_t ldw, const int64_t* target,
                                int64_t ignore_index, int64_t M, int V, int K, float* loss, float* lse, int32_t* rows,
                                int32_t* count, void* ws, int64_t ws_bytes, void* stream) {
-  return ce_fwd_impl("amk_ce_head_fwd", x, ldx, w, ldw, target, ignore_index, M, V, K, loss, lse, rows, count, ws, ws_bytes, stream,
-                     nullptr);
+  return fwd_impl<Head>("amk_ce_head_fwd", x, ldx, w, ldw, target, ignore_index, M, V, K, loss, lse, rows, count, ws, ws_bytes,
+                        stream, nullptr);
 }
 
 extern "C" int amk_ce_head_bias_fwd(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias,
@@ -548,55 +496,16 @@ extern "C" int amk_ce_head_bias_fwd(const float* x, int64_t ldx, const float* w,
                                     int32_t* rows, int32_t* count, void* ws, int64_t ws_bytes, void* stream) {
   AMK_CHECK_ARG(bias, "amk_ce_head_bias_fwd: null pointer (bias)");
   AMK_CHECK_ARG(ce_a16(bias), "amk_ce_head_bias_fwd: misaligned pointer (bias: 16 bytes)");
-  return ce_fwd_impl("amk_ce_head_bias_fwd", x, ldx, w, ldw, target, ignore_index, M, V, K, loss, lse, rows, count, ws, ws_bytes,
-                     stream, bias);
-}
-
-// bias == nullptr: the biasless head, dbias not used
-static int ce_bwd_impl(const char* who, const float* x, int64_t ldx, const float* w, int64_t ldw, const int64_t* target,
-                       int64_t ignore_index, int64_t M, int V, int K, const float* d_loss, const float* lse, const int32_t* rows,
-                       const int32_t* count, float* dx, int64_t lddx, float* dw, int64_t lddw, void* ws, int64_t ws_bytes,
-                       void* stream, const float* bias, float* dbias) {
-  AMK_CHECK_ARG(x && w && target && d_loss && lse && rows && count && dx && dw && ws, "%s: null pointer", who);
-  const int rc = ce_check_common(who, ldx, ldw, M, V, K);
-  if (rc != AMK_OK) return rc;
-  AMK_CHECK_SUPPORTED(lddx % 4 == 0 && lddw % 4 == 0, "%s: lddx=%lld and lddw=%lld must be multiples of 4", who, (long long)lddx,
-                      (long long)lddw);
-  AMK_CHECK_ARG(lddx >= K && lddw >= K, "%s: a leading dimension is below K", who);
-  AMK_CHECK_ARG(ce_a16(x) && ce_a16(w) && ce_a16(dx) && ce_a16(dw) && ce_a16(ws) && ce_a8(target) && ce_a4(d_loss) && ce_a4(lse) &&
-                    ce_a4(rows) && ce_a4(count),
-                "%s: misaligned pointer (x, w, dx, dw, ws: 16 bytes; target: 8; d_loss, lse, rows, count: 4)", who);
-  AMK_CHECK_ARG(ws_bytes >= amk_ce_head_bwd_ws_bytes(M, V, K), "%s: workspace of %lld bytes, %lld needed", who,
-                (long long)ws_bytes, (long long)amk_ce_head_bwd_ws_bytes(M, V, K));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  float* G = static_cast<float*>(ws);
-  const int64_t ldg = ldg_of(V);
-  const int64_t nrt = (M + TR - 1) / TR;
-  const int nvt = (int)(ldg / TA), nkt = (K + TA - 1) / TA;
-  if (bias)
-    hipLaunchKernelGGL(ce_bwd_g_kernel<true>, dim3((unsigned)(nrt * nvt)), dim3(256), 0, st, x, ldx, w, ldw, target, V, K, nvt,
-                       d_loss, lse, rows, count, G, ldg, bias);
-  else
-    hipLaunchKernelGGL(ce_bwd_g_kernel<false>, dim3((unsigned)(nrt * nvt)), dim3(256), 0, st, x, ldx, w, ldw, target, V, K, nvt,
-                       d_loss, lse, rows, count, G, ldg, bias);
-  hipLaunchKernelGGL(ce_zero_rows_kernel, dim3((unsigned)((M * (K / 4) + 255) / 256)), dim3(256), 0, st, target, ignore_index, M,
-                     V, K, dx, lddx);
-  hipLaunchKernelGGL(ce_bwd_dx_kernel, dim3((unsigned)(nrt * nkt)), dim3(256), 0, st, G, ldg, w, ldw, target, V, K, nkt, rows,
-                     count, dx, lddx);
-  hipLaunchKernelGGL(ce_bwd_dw_kernel, dim3((unsigned)(nvt * nkt)), dim3(256), 0, st, G, ldg, x, ldx, V, K, nkt, rows, count, dw,
-                     lddw);
-  if (bias)
-    hipLaunchKernelGGL(ce_bwd_db_kernel, dim3((unsigned)(ldg / DBC)), dim3(DBC * DBQ), 0, st, G, ldg, V, count, dbias);
-  AMK_CHECK_LAUNCH(who);
-  return AMK_OK;
+  return fwd_impl<Head>("amk_ce_head_bias_fwd", x, ldx, w, ldw, target, ignore_index, M, V, K, loss, lse, rows, count, ws, ws_bytes,
+                        stream, bias);
 }
 
 extern "C" int amk_ce_head_bwd(const float* x, int64_t ldx, const float* w, int64_t ldw, const int64_t* target,
                                int64_t ignore_index, int64_t M, int V, int K, const float* d_loss, const float* lse,
                                const int32_t* rows, const int32_t* count, float* dx, int64_t lddx, float* dw, int64_t lddw,
                                void* ws, int64_t ws_bytes, void* stream) {
-  return ce_bwd_impl("amk_ce_head_bwd", x, ldx, w, ldw, target, ignore_index, M, V, K, d_loss, lse, rows, count, dx, lddx, dw, lddw,
-                     ws, ws_bytes, stream, nullptr, nullptr);
+  return bwd_impl<Head>("amk_ce_head_bwd", x, ldx, w, ldw, target, ignore_index, M, V, K, d_loss, lse, rows, count, dx, lddx, dw,
+                        lddw, ws, ws_bytes, stream, nullptr, nullptr);
 }
 
 extern "C" int amk_ce_head_bias_bwd(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias,
@@ -605,6 +514,7 @@ extern "C" int amk_ce_head_bias_bwd(const float* x, int64_t ldx, const float* w,
                                     int64_t lddw, float* dbias, void* ws, int64_t ws_bytes, void* stream) {
   AMK_CHECK_ARG(bias && dbias, "amk_ce_head_bias_bwd: null pointer (bias or dbias)");
   AMK_CHECK_ARG(ce_a16(bias) && ce_a16(dbias), "amk_ce_head_bias_bwd: misaligned pointer (bias, dbias: 16 bytes)");
-  return ce_bwd_impl("amk_ce_head_bias_bwd", x, ldx, w, ldw, target, ignore_index, M, V, K, d_loss, lse, rows, count,
-                     dx, lddx, dw, lddw, ws, ws_bytes, stream, bias, dbias);
+  return bwd_impl<Head>("amk_ce_head_bias_bwd", x, ldx, w, ldw, target, ignore_index, M, V, K, d_loss, lse, rows, count, dx, lddx,
+                        dw, lddw, ws, ws_bytes, stream, bias, dbias);
 }
+

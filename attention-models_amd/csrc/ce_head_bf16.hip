@@ -4,7 +4,7 @@
 // The semantics, the launches and the row-on-the-lane structure are those of csrc/ce_head.hip (read that file's header
 // first); what differs is the operand type and how the tiles reach the matrix unit:
 //
-//   ce_compact / ce_finalize : the f32 head's kernels again (they never touch x or w).
+//   ce_compact / ce_finalize : the f32 head's kernels themselves, through csrc/ce_head_common.h (they never touch x or w).
 //   ce_fwd    : z^T (128 words x 32 rows per wave) = w_tile (A operand) x x[rows]^T (B operand).  Both operands have the
 //               contraction index contiguous in memory: staged as stored, [128 rows][32 k] bf16 per step with the four
 //               16-byte chunks of a row XOR-swizzled (as the NT tiles of csrc/gemm_bf16.hip), fragments by ds_read_b128.
@@ -32,23 +32,22 @@
 //
 // The tile loops hold no branch around a memory instruction: a piece outside the problem is loaded from a clamped
 // address and replaced by zeros with a select.  One LDS-only barrier per step: the global prefetch stays in flight.
-#include "amk_common.h"
+#include "ce_head_common.h"
 
 namespace amk_ce16 {
+
+using namespace amk_ce_common;   // TR, TA, the limits, slices, the host drivers
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
-constexpr int TR = 128;      // B-side tile: 32 per wave, the lane's index
-constexpr int TA = 128;      // A-side tile: every wave sees all of it (4 MFMA blocks of 32)
 constexpr int BK = 32;       // contraction depth per LDS stage (two MFMA steps of 16)
 constexpr int FSTR = 32;     // bf16 per LDS row of a [128 rows][32 k] tile (chunk c of row r sits at c ^ ((r >> 2) & 3))
 constexpr int STR = 160;     // bf16 per LDS row of a [32 k][128 columns] tile (80 dwords = 16 mod 64: conflict-free
                              // transposing reads)
 constexpr int FT = BK * STR; // elements of one operand tile buffer (>= 128 * FSTR)
 constexpr int STAGE = 2 * FT;
-constexpr int SCAN = 1024;   // threads of ce_compact / ce_finalize
 static_assert(FT >= 128 * FSTR, "the two tile shapes share one buffer");
 
 __device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
@@ -125,34 +124,6 @@ __device__ __forceinline__ void clear(f32x16 (&acc)[4]) {
   for (int b = 0; b < 4; ++b)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
-}
-
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(SCAN) void ce_compact_kernel(const int64_t* __restrict__ target, int64_t ignore_index, int M,
-                                                          int32_t* __restrict__ rows, int32_t* __restrict__ count) {
-  __shared__ int wsum[SCAN / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int base = 0;
-  for (int c0 = 0; c0 < M; c0 += SCAN) {
-    const int m = c0 + tid;
-    const bool on = m < M && target[m] != ignore_index;
-    const unsigned long long bal = __ballot(on);
-    const int before = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) wsum[wave] = __popcll(bal);
-    __syncthreads();
-    int off = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < SCAN / 64; ++w) {
-      const int c = wsum[w];
-      off += w < wave ? c : 0;
-      total += c;
-    }
-    if (on) rows[base + off + before] = m;
-    base += total;
-    __syncthreads();
-  }
-  for (int i = base + tid; i < M; i += SCAN) rows[i] = -1;
-  if (tid == 0) count[0] = base;
 }
 
 // acc[b][r] = bias[v0 + 32 b + acc_row(r, hf)]: the bias is the first term of the logits' MFMA chain.  A whole tile inside
@@ -287,39 +258,6 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const __bf16* __restrict__ 
     ps[o] = s0 + s1;
     pz[o] = found ? zt : (of ? oz : 0.f);
   }
-}
-
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(SCAN) void ce_finalize_kernel(const float* __restrict__ pm, const float* __restrict__ ps,
-                                                           const float* __restrict__ pz, const int64_t* __restrict__ target,
-                                                           const int32_t* __restrict__ rows, const int32_t* __restrict__ count,
-                                                           int V, int nsplit, int vper, float* __restrict__ lse,
-                                                           float* __restrict__ loss) {
-  __shared__ float red[SCAN];
-  const int tid = threadIdx.x;
-  const int cnt = count[0];
-  float part = 0.f;
-  for (int i = tid; i < cnt; i += SCAN) {
-    const int64_t o = (int64_t)i * nsplit;
-    float m = pm[o], s = ps[o];
-    for (int sl = 1; sl < nsplit; ++sl) {
-      const float om = pm[o + sl], os = ps[o + sl];
-      const float mm = fmaxf(m, om);
-      s = s * __expf(m - mm) + os * __expf(om - mm);
-      m = mm;
-    }
-    const float l = m + logf(s);
-    lse[i] = l;
-    const int64_t t = target[rows[i]];
-    part += (t >= 0 && t < V) ? l - pz[o + (int)(t / vper)] : __builtin_nanf("");
-  }
-  red[tid] = part;
-  __syncthreads();
-  for (int o = SCAN / 2; o >= 1; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  if (tid == 0) loss[0] = red[0] / (float)cnt;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -521,153 +459,49 @@ __global__ __launch_bounds__(DBC / 2 * DBQ) void ce_bwd_db_kernel(const __bf16* 
   }
 }
 
-// vocabulary slices of the forward: as the f32 head's (tests restate it once for both)
-static void slices(int64_t M, int V, int* nsplit, int* vper) {
-  const int64_t nrt = (M + TR - 1) / TR;
-  const int nvt = (V + TA - 1) / TA;
-  int64_t want = (512 + nrt - 1) / nrt;
-  if (want > 16) want = 16;
-  if (want > nvt) want = nvt;
-  if (want < 1) want = 1;
-  const int per = (int)((nvt + want - 1) / want);
-  *vper = per * TA;
-  *nsplit = (nvt + per - 1) / per;
-}
-
-static int64_t ldg_of(int V) { return ((int64_t)V + TA - 1) / TA * TA; }
-
-constexpr int64_t CE_MAX_M = 1ll << 24;   // count stays exact in f32; rows are int32
-constexpr int CE_MAX_V = 1 << 22;
-constexpr int CE_MAX_K = 1 << 16;
-
-static bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static bool a4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-static bool a8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
-
-static int check_common(const char* who, int64_t ldx, int64_t ldw, int64_t M, int V, int K) {
-  AMK_CHECK_ARG(M > 0 && V > 0 && K > 0, "%s: non-positive size M=%lld V=%d K=%d", who, (long long)M, V, K);
-  AMK_CHECK_SUPPORTED(K % 8 == 0, "%s: K=%d must be a multiple of 8", who, K);
-  AMK_CHECK_SUPPORTED(ldx % 8 == 0 && ldw % 8 == 0, "%s: ldx=%lld and ldw=%lld must be multiples of 8", who, (long long)ldx,
-                      (long long)ldw);
-  AMK_CHECK_ARG(ldx >= K && ldw >= K, "%s: a leading dimension is below K", who);
-  AMK_CHECK_SUPPORTED(M <= CE_MAX_M && V <= CE_MAX_V && K <= CE_MAX_K,
-                      "%s: operand above the limits (M <= 2^24, V <= 2^22, K <= 2^16): M=%lld V=%d K=%d", who, (long long)M, V, K);
-  const int64_t nrt = (M + TR - 1) / TR, widest = ldg_of(V) / TA > (K + TA - 1) / TA ? ldg_of(V) / TA : (K + TA - 1) / TA;
-  AMK_CHECK_SUPPORTED(nrt * widest < (1ll << 31), "%s: grid too large (M=%lld V=%d K=%d)", who, (long long)M, V, K);
-  return AMK_OK;
-}
+// this file, as the drivers of ce_head_common.h see it
+struct Head {
+  using T = __bf16;
+  static constexpr int MULT = 8;
+  static constexpr decltype(&ce_fwd_kernel<false>) fwd[2] = {ce_fwd_kernel<false>, ce_fwd_kernel<true>};
+  static constexpr decltype(&ce_bwd_g_kernel<false>) bwd_g[2] = {ce_bwd_g_kernel<false>, ce_bwd_g_kernel<true>};
+  static constexpr auto zero_rows = &ce_zero_rows_kernel;
+  static constexpr auto bwd_dx = &ce_bwd_dx_kernel;
+  static constexpr auto bwd_dw = &ce_bwd_dw_kernel;
+  static constexpr auto bwd_db = &ce_bwd_db_kernel;
+  static constexpr int DB_COLS = DBC, DB_THREADS = DBC / 2 * DBQ;
+};
 
 }  // namespace amk_ce16
 
 using namespace amk_ce16;
 
-extern "C" int64_t amk_ce_head_bf16_fwd_ws_bytes(int64_t M, int V, int K) {
-  if (M <= 0 || V <= 0 || K <= 0 || M > CE_MAX_M || V > CE_MAX_V) return 0;
-  int ns, vper;
-  amk_ce16::slices(M, V, &ns, &vper);
-  return 3 * M * ns * (int64_t)sizeof(float);
-}
+extern "C" int64_t amk_ce_head_bf16_fwd_ws_bytes(int64_t M, int V, int K) { return ce_fwd_ws_bytes(M, V, K); }
 
-extern "C" int64_t amk_ce_head_bf16_bwd_ws_bytes(int64_t M, int V, int K) {
-  if (M <= 0 || V <= 0 || K <= 0 || M > CE_MAX_M || V > CE_MAX_V) return 0;
-  return M * amk_ce16::ldg_of(V) * (int64_t)sizeof(__bf16);
-}
-
-// bias == nullptr: the biasless head (who names the entry point in the messages)
-static int fwd_impl(const char* who, const void* x, int64_t ldx, const void* w, int64_t ldw, const int64_t* target,
-                    int64_t ignore_index, int64_t M, int V, int K, float* loss, float* lse, int32_t* rows, int32_t* count, void* ws,
-                    int64_t ws_bytes, void* stream, const float* bias) {
-  AMK_CHECK_ARG(x && w && target && loss && lse && rows && count && ws, "%s: null pointer", who);
-  const int rc = check_common(who, ldx, ldw, M, V, K);
-  if (rc != AMK_OK) return rc;
-  AMK_CHECK_ARG(a16(x) && a16(w) && a16(ws) && a8(target) && a4(loss) && a4(lse) && a4(rows) && a4(count),
-                "%s: misaligned pointer (x, w, ws: 16 bytes; target: 8; loss, lse, rows, count: 4)", who);
-  AMK_CHECK_ARG(ws_bytes >= amk_ce_head_bf16_fwd_ws_bytes(M, V, K), "%s: workspace of %lld bytes, %lld needed", who,
-                (long long)ws_bytes, (long long)amk_ce_head_bf16_fwd_ws_bytes(M, V, K));
-  int ns, vper;
-  amk_ce16::slices(M, V, &ns, &vper);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const __bf16* xb = static_cast<const __bf16*>(x);
-  const __bf16* wb = static_cast<const __bf16*>(w);
-  float* pm = static_cast<float*>(ws);
-  float* ps = pm + M * ns;
-  float* pz = ps + M * ns;
-  const int64_t nrt = (M + TR - 1) / TR;
-  hipLaunchKernelGGL(amk_ce16::ce_compact_kernel, dim3(1), dim3(SCAN), 0, st, target, ignore_index, (int)M, rows, count);
-  if (bias)
-    hipLaunchKernelGGL(amk_ce16::ce_fwd_kernel<true>, dim3((unsigned)(nrt * ns)), dim3(256), 0, st, xb, ldx, wb, ldw, target, V, K,
-                       ns, vper, rows, count, pm, ps, pz, bias);
-  else
-    hipLaunchKernelGGL(amk_ce16::ce_fwd_kernel<false>, dim3((unsigned)(nrt * ns)), dim3(256), 0, st, xb, ldx, wb, ldw, target, V, K,
-                       ns, vper, rows, count, pm, ps, pz, bias);
-  hipLaunchKernelGGL(amk_ce16::ce_finalize_kernel, dim3(1), dim3(SCAN), 0, st, pm, ps, pz, target, rows, count, V, ns, vper, lse,
-                     loss);
-  AMK_CHECK_LAUNCH(who);
-  return AMK_OK;
-}
+extern "C" int64_t amk_ce_head_bf16_bwd_ws_bytes(int64_t M, int V, int K) { return ce_bwd_ws_bytes(M, V, K, sizeof(Head::T)); }
 
 extern "C" int amk_ce_head_bf16_fwd(const void* x, int64_t ldx, const void* w, int64_t ldw, const int64_t* target,
                                     int64_t ignore_index, int64_t M, int V, int K, float* loss, float* lse, int32_t* rows,
                                     int32_t* count, void* ws, int64_t ws_bytes, void* stream) {
-  return fwd_impl("amk_ce_head_bf16_fwd", x, ldx, w, ldw, target, ignore_index, M, V, K, loss, lse, rows, count, ws, ws_bytes, stream,
-                  nullptr);
+  return fwd_impl<Head>("amk_ce_head_bf16_fwd", x, ldx, w, ldw, target, ignore_index, M, V, K, loss, lse, rows, count, ws, ws_bytes,
+                        stream, nullptr);
 }
 
 extern "C" int amk_ce_head_bias_bf16_fwd(const void* x, int64_t ldx, const void* w, int64_t ldw, const float* bias,
                                          const int64_t* target, int64_t ignore_index, int64_t M, int V, int K, float* loss,
                                          float* lse, int32_t* rows, int32_t* count, void* ws, int64_t ws_bytes, void* stream) {
   AMK_CHECK_ARG(bias, "amk_ce_head_bias_bf16_fwd: null pointer (bias)");
-  AMK_CHECK_ARG(a16(bias), "amk_ce_head_bias_bf16_fwd: misaligned pointer (bias: 16 bytes)");
-  return fwd_impl("amk_ce_head_bias_bf16_fwd", x, ldx, w, ldw, target, ignore_index, M, V, K, loss, lse, rows, count, ws, ws_bytes,
-                  stream, bias);
-}
-
-// bias == nullptr: the biasless head, dbias not used
-static int bwd_impl(const char* who, const void* x, int64_t ldx, const void* w, int64_t ldw, const int64_t* target,
-                    int64_t ignore_index, int64_t M, int V, int K, const float* d_loss, const float* lse, const int32_t* rows,
-                    const int32_t* count, void* dx, int64_t lddx, float* dw, int64_t lddw, void* ws, int64_t ws_bytes, void* stream,
-                    const float* bias, float* dbias) {
-  AMK_CHECK_ARG(x && w && target && d_loss && lse && rows && count && dx && dw && ws, "%s: null pointer", who);
-  const int rc = check_common(who, ldx, ldw, M, V, K);
-  if (rc != AMK_OK) return rc;
-  AMK_CHECK_SUPPORTED(lddx % 8 == 0 && lddw % 8 == 0, "%s: lddx=%lld and lddw=%lld must be multiples of 8", who, (long long)lddx,
-                      (long long)lddw);
-  AMK_CHECK_ARG(lddx >= K && lddw >= K, "%s: a leading dimension is below K", who);
-  AMK_CHECK_ARG(a16(x) && a16(w) && a16(dx) && a16(dw) && a16(ws) && a8(target) && a4(d_loss) && a4(lse) && a4(rows) && a4(count),
-                "%s: misaligned pointer (x, w, dx, dw, ws: 16 bytes; target: 8; d_loss, lse, rows, count: 4)", who);
-  AMK_CHECK_ARG(ws_bytes >= amk_ce_head_bf16_bwd_ws_bytes(M, V, K), "%s: workspace of %lld bytes, %lld needed", who,
-                (long long)ws_bytes, (long long)amk_ce_head_bf16_bwd_ws_bytes(M, V, K));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const __bf16* xb = static_cast<const __bf16*>(x);
-  const __bf16* wb = static_cast<const __bf16*>(w);
-  __bf16* G = static_cast<__bf16*>(ws);
-  const int64_t ldg = amk_ce16::ldg_of(V);
-  const int64_t nrt = (M + TR - 1) / TR;
-  const int nvt = (int)(ldg / TA), nkt = (K + TA - 1) / TA;
-  if (bias)
-    hipLaunchKernelGGL(amk_ce16::ce_bwd_g_kernel<true>, dim3((unsigned)(nrt * nvt)), dim3(256), 0, st, xb, ldx, wb, ldw, target, V, K,
-                       nvt, d_loss, lse, rows, count, G, ldg, bias);
-  else
-    hipLaunchKernelGGL(amk_ce16::ce_bwd_g_kernel<false>, dim3((unsigned)(nrt * nvt)), dim3(256), 0, st, xb, ldx, wb, ldw, target, V,
-                       K, nvt, d_loss, lse, rows, count, G, ldg, bias);
-  hipLaunchKernelGGL(amk_ce16::ce_zero_rows_kernel, dim3((unsigned)((M * (K / 8) + 255) / 256)), dim3(256), 0, st, target,
-                     ignore_index, M, V, K, static_cast<__bf16*>(dx), lddx);
-  hipLaunchKernelGGL(amk_ce16::ce_bwd_dx_kernel, dim3((unsigned)(nrt * nkt)), dim3(256), 0, st, G, ldg, wb, ldw, target, V, K, nkt,
-                     rows, count, static_cast<__bf16*>(dx), lddx);
-  hipLaunchKernelGGL(amk_ce16::ce_bwd_dw_kernel, dim3((unsigned)(nvt * nkt)), dim3(256), 0, st, G, ldg, xb, ldx, V, K, nkt, rows, count,
-                     dw, lddw);
-  if (bias)
-    hipLaunchKernelGGL(amk_ce16::ce_bwd_db_kernel, dim3((unsigned)(ldg / DBC)), dim3(DBC / 2 * DBQ), 0, st, G, ldg, V, count, dbias);
-  AMK_CHECK_LAUNCH(who);
-  return AMK_OK;
+  AMK_CHECK_ARG(ce_a16(bias), "amk_ce_head_bias_bf16_fwd: misaligned pointer (bias: 16 bytes)");
+  return fwd_impl<Head>("amk_ce_head_bias_bf16_fwd", x, ldx, w, ldw, target, ignore_index, M, V, K, loss, lse, rows, count, ws,
+                        ws_bytes, stream, bias);
 }
 
 extern "C" int amk_ce_head_bf16_bwd(const void* x, int64_t ldx, const void* w, int64_t ldw, const int64_t* target,
                                     int64_t ignore_index, int64_t M, int V, int K, const float* d_loss, const float* lse,
                                     const int32_t* rows, const int32_t* count, void* dx, int64_t lddx, float* dw, int64_t lddw,
                                     void* ws, int64_t ws_bytes, void* stream) {
-  return bwd_impl("amk_ce_head_bf16_bwd", x, ldx, w, ldw, target, ignore_index, M, V, K, d_loss, lse, rows, count, dx, lddx, dw, lddw,
-                  ws, ws_bytes, stream, nullptr, nullptr);
+  return bwd_impl<Head>("amk_ce_head_bf16_bwd", x, ldx, w, ldw, target, ignore_index, M, V, K, d_loss, lse, rows, count, dx, lddx,
+                        dw, lddw, ws, ws_bytes, stream, nullptr, nullptr);
 }
 
 extern "C" int amk_ce_head_bias_bf16_bwd(const void* x, int64_t ldx, const void* w, int64_t ldw, const float* bias,
@@ -675,7 +509,8 @@ extern "C" int amk_ce_head_bias_bf16_bwd(const void* x, int64_t ldx, const void*
                                          const float* lse, const int32_t* rows, const int32_t* count, void* dx, int64_t lddx,
                                          float* dw, int64_t lddw, float* dbias, void* ws, int64_t ws_bytes, void* stream) {
   AMK_CHECK_ARG(bias && dbias, "amk_ce_head_bias_bf16_bwd: null pointer (bias or dbias)");
-  AMK_CHECK_ARG(a16(bias) && a16(dbias), "amk_ce_head_bias_bf16_bwd: misaligned pointer (bias, dbias: 16 bytes)");
-  return bwd_impl("amk_ce_head_bias_bf16_bwd", x, ldx, w, ldw, target, ignore_index, M, V, K, d_loss, lse, rows, count, dx, lddx, dw,
-                  lddw, ws, ws_bytes, stream, bias, dbias);
+  AMK_CHECK_ARG(ce_a16(bias) && ce_a16(dbias), "amk_ce_head_bias_bf16_bwd: misaligned pointer (bias, dbias: 16 bytes)");
+  return bwd_impl<Head>("amk_ce_head_bias_bf16_bwd", x, ldx, w, ldw, target, ignore_index, M, V, K, d_loss, lse, rows, count, dx,
+                        lddx, dw, lddw, ws, ws_bytes, stream, bias, dbias);
 }
+

@@ -116,6 +116,9 @@ SIGNATURES = {
     "amk_bnact_fwd": (_I, [_P, _P, _P, _I, _I, _L, _F, _F, _F] + [_P] * 7),
     "amk_bnact_bwd": (_I, [_P] * 6 + [_I, _I, _L, _F] + [_P] * 6),
     "amk_bnact_bwd_bwd": (_I, [_P] * 10 + [_I, _I, _L, _F] + [_P] * 5),
+    "amk_bnact_bf16_fwd": (_I, [_P, _P, _P, _I, _I, _L, _F, _F, _F] + [_P] * 7),
+    "amk_bnact_bf16_bwd": (_I, [_P] * 6 + [_I, _I, _L, _F] + [_P] * 6),
+    "amk_bnact_bf16_bwd_bwd": (_I, [_P] * 10 + [_I, _I, _L, _F] + [_P] * 5),
     "amk_gnact_ws_floats": (_L, [_I, _I, _L, _I]),
     "amk_gnact_fwd": (_I, [_P, _P, _P, _I, _I, _L, _I, _F, _I] + [_P] * 5),
     "amk_gnact_bwd": (_I, [_P] * 6 + [_I, _I, _L, _I, _I] + [_P] * 5),

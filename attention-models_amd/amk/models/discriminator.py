@@ -6,8 +6,10 @@ keys (``model.N.*``) match the reference layer order.
 
 The training-mode BatchNorm2d + LeakyReLU pairs of layers 3, 6 and 9 run on csrc/discr_norm.hip (ops.bn_leaky_relu:
 forward, backward and the gradient penalty's double backward, two launches each) instead of MIOpen's batch norm and
-ATen's composite double backward; eval mode, CPU tensors and bf16 autocast keep the modules (AMK_DISCR_NORM=aten
-keeps them everywhere).
+ATen's composite double backward.  Under bf16 autocast the convolution in front returns bf16 and the pair runs on the
+same kernels over bf16 elements (ops.bn_leaky_relu_bf16: f32 arithmetic, f32 statistics and parameter gradients, each
+bf16 output rounded once; AMK_DISCR_NORM_BF16=0 keeps the modules there).  Eval mode, CPU tensors, bf16 parameters,
+f16 and non-contiguous inputs keep the modules (AMK_DISCR_NORM=aten keeps them everywhere).
 
 The gradient penalty of that step (trainers/vitgqgan.py:115-131) differentiates the
 discriminator's input gradient a second time.  ATen expresses the second derivative of a
@@ -131,6 +133,9 @@ class NLayerDiscriminator(nn.Module):
             nxt = layers[i + 1] if i + 1 < len(layers) else None
             if isinstance(m, nn.BatchNorm2d) and isinstance(nxt, nn.LeakyReLU) and ops.bn_leaky_relu_ok(m, x):
                 x = ops.bn_leaky_relu(x, m, nxt.negative_slope)
+                i += 2
+            elif isinstance(m, nn.BatchNorm2d) and isinstance(nxt, nn.LeakyReLU) and ops.bn_leaky_relu_bf16_ok(m, x):
+                x = ops.bn_leaky_relu_bf16(x, m, nxt.negative_slope)
                 i += 2
             else:
                 x = m(x)

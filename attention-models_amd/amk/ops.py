@@ -2219,6 +2219,123 @@ def bn_leaky_relu(x, bn, slope):
                         float(slope))
 
 
+# AMK_DISCR_NORM_BF16: the same pairs under bf16 autocast, where the convolution in front hands over a bf16 tensor and the
+# modules run MIOpen's batch norm on it, ATen's leaky_relu_ / leaky_relu_backward and, for the gradient penalty, ATen's
+# composite double backward.  "1" = amk_bnact_bf16_* (csrc/discr_norm.hip on bf16 x, z, gz, gx, ggx, g_gz and g_x: the f32
+# arithmetic of the f32 kernels, one rounding to bf16 on each store; the bf16 x and f32 mean / rstd / sums saved); "0" = the
+# modules.  Measured at batch 32, the whole GAN step under bf16 autocast with one captured step per arm replayed in turn
+# (tools/kbench_autocast.py --step --ab AMK_DISCR_NORM_BF16, profiles/kbench_autocast_discr_norm_bf16.log): 36.83 ms with the
+# modules, 34.16 ms fused, the arms' spreads 0.08 ms; the op alone (tools/kbench_discr_norm.py --bf16,
+# profiles/kbench_discr_norm_bf16.log) 3.91 -> 1.68 ms over a step's calls.  So the switch ships on.
+# AMK_DISCR_NORM=aten disables both.  Read per call, so one build A/Bs.
+def discr_norm_bf16_on():
+    return os.environ.get("AMK_DISCR_NORM_BF16", "1") != "0"
+
+
+def _bn_aligned_bf16(t):
+    return _bn_aligned(t.to(torch.bfloat16))
+
+
+def _bn_f32(t):
+    return None if t is None else t.to(torch.float32).contiguous()
+
+
+class _BNActGradBF16(torch.autograd.Function):
+    """_BNActGrad on bf16 gz and x: gx bf16, rounded once; dgamma, dbeta and the kept sums f32.  Its backward is the double
+    backward on bf16 ggx with bf16 g_gz and g_x and an f32 g_gamma."""
+
+    @staticmethod
+    def forward(ctx, gz, x, weight, bias, mean, rstd, slope):
+        gz = _bn_aligned_bf16(gz)
+        N, C, HW = _bn_dims(x)
+        L = _lib.load()
+        gx = torch.empty_like(x)
+        sums = torch.empty((2, C), device=x.device, dtype=torch.float32)
+        dw = torch.empty_like(weight)
+        db = torch.empty_like(bias)
+        _lib.check(L.amk_bnact_bf16_bwd(_ptr(gz), _ptr(x), _ptr(weight), _ptr(bias), _ptr(mean), _ptr(rstd), N, C, HW,
+                                        float(slope), _ptr(gx), _ptr(sums), _ptr(dw), _ptr(db), _ptr(_bn_ws(x)),
+                                        _stream()), "amk_bnact_bf16_bwd")
+        ctx.save_for_backward(gz, x, weight, bias, mean, rstd, sums)
+        ctx.slope = slope
+        ctx.set_materialize_grads(False)   # absent gradients of dgamma / dbeta cost nothing
+        return gx, dw, db
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, ggx, ggw, ggb):
+        gz, x, weight, bias, mean, rstd, sums = ctx.saved_tensors
+        if ggx is None and ggw is None and ggb is None:
+            return None, None, None, None, None, None, None
+        ggx = torch.zeros_like(x) if ggx is None else _bn_aligned_bf16(ggx)
+        N, C, HW = _bn_dims(x)
+        g_gz = torch.empty_like(x)
+        g_x = torch.empty_like(x)
+        g_w = torch.empty_like(weight) if ctx.needs_input_grad[2] else None
+        _lib.check(_lib.load().amk_bnact_bf16_bwd_bwd(
+            _ptr(ggx), _ptr(_bn_f32(ggw)), _ptr(_bn_f32(ggb)), _ptr(gz), _ptr(x), _ptr(weight), _ptr(bias), _ptr(mean),
+            _ptr(rstd), _ptr(sums), N, C, HW, float(ctx.slope), _ptr(g_gz), _ptr(g_x), _ptr(g_w), _ptr(_bn_ws(x)),
+            _stream()), "amk_bnact_bf16_bwd_bwd")
+        return (g_gz if ctx.needs_input_grad[0] else None, g_x if ctx.needs_input_grad[1] else None, g_w,
+                None, None, None, None)
+
+
+class _BNActBF16(torch.autograd.Function):
+    """_BNAct on a bf16 x with f32 parameters: z bf16, rounded once; mean, rstd and the running statistics f32."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, eps, momentum, slope):
+        N, C, HW = _bn_dims(x)
+        L = _lib.load()
+        z = torch.empty_like(x)
+        mean = torch.empty(C, device=x.device, dtype=torch.float32)
+        rstd = torch.empty(C, device=x.device, dtype=torch.float32)
+        _lib.check(L.amk_bnact_bf16_fwd(_ptr(x), _ptr(weight), _ptr(bias), N, C, HW, float(eps), float(momentum),
+                                        float(slope), _ptr(z), _ptr(mean), _ptr(rstd), _ptr(running_mean),
+                                        _ptr(running_var), _ptr(_bn_ws(x)), _stream()), "amk_bnact_bf16_fwd")
+        ctx.save_for_backward(x, weight, bias, mean, rstd)
+        ctx.slope = slope
+        ctx.set_materialize_grads(False)
+        return z
+
+    @staticmethod
+    def backward(ctx, gz):
+        if gz is None:
+            return (None,) * 8
+        x, weight, bias, mean, rstd = ctx.saved_tensors
+        from .models.discriminator import input_grad_only_active   # (lazy: the models package imports this module)
+
+        gx, dw, db = _BNActGradBF16.apply(gz, x, weight, bias, mean, rstd, ctx.slope)
+        if input_grad_only_active():
+            dw = db = None
+        return (gx if ctx.needs_input_grad[0] else None, dw if ctx.needs_input_grad[1] else None,
+                db if ctx.needs_input_grad[2] else None, None, None, None, None, None)
+
+
+def bn_leaky_relu_bf16_ok(bn, x):
+    """True when (bn, LeakyReLU) can run on amk_bnact_bf16_*: both switches on, training-mode statistics with running
+    averages, a momentum and an affine transform in f32, and a contiguous NCHW bf16 HIP tensor with more than one element per
+    channel (what the convolution in front returns under bf16 autocast).  Everything else (eval, CPU, bf16 parameters, f16,
+    non-contiguous or channels-last inputs) keeps the modules."""
+    return (discr_norm_mode() == "amk" and discr_norm_bf16_on() and isinstance(bn, torch.nn.BatchNorm2d)
+            and bn.training and bn.track_running_stats and bn.affine and bn.momentum is not None
+            and bn.running_mean is not None and bn.running_mean.dtype == torch.float32
+            and bn.weight.dtype == torch.float32 and bn.bias.dtype == torch.float32 and bn.weight.is_cuda
+            and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4 and x.is_contiguous() and x.numel() > 0
+            and x.shape[0] * x.shape[2] * x.shape[3] > 1)
+
+
+def bn_leaky_relu_bf16(x, bn, slope):
+    """leaky_relu(bn(x), slope) in bf16 for a training-mode nn.BatchNorm2d and a bf16 x (see bn_leaky_relu_bf16_ok)."""
+    _require_device(bn.weight, bn.bias)
+    if not x.is_cuda or x.dtype != torch.bfloat16:
+        raise RuntimeError(f"bn_leaky_relu_bf16 takes a bf16 HIP tensor; got {x.dtype} on {x.device}")
+    if bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+    return _BNActBF16.apply(_bn_aligned(x), bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum,
+                            float(slope))
+
+
 # ---------------------------------------------------------------------------- conv VQGAN GroupNorm + Swish
 # AMK_GN_ACT: "1" (default) = the GroupNorm (+ Swish) of amk.models.vqgan runs on csrc/gn_act.hip (x, mean and rstd saved; y
 # and sigma recomputed in the backward); "0" = nn.GroupNorm and x * sigmoid(x) as they are.  Measured on VQGAN(256, 8192),

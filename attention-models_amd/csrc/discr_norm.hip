@@ -1,5 +1,6 @@
-// Training-mode BatchNorm2d + LeakyReLU of the PatchGAN discriminator, f32 NCHW, for gfx950:
-// forward, first-order backward and the double backward the gradient penalty needs.
+// Training-mode BatchNorm2d + LeakyReLU of the PatchGAN discriminator, NCHW, for gfx950: forward, first-order
+// backward and the double backward the gradient penalty needs; f32 tensors (amk_bnact_*) and, under bf16 autocast,
+// bf16 x, z, gz, gx, ggx, g_gz and g_x (amk_bnact_bf16_*).
 //
 // ATen runs this stack as MIOpen batch-norm kernels plus separate LeakyReLU passes, and the
 // double backward as ~80 small reductions and element-wise launches per layer.  Here every entry
@@ -14,6 +15,13 @@
 // SEG pieces of one plane -- and workgroup (s, c) owns segment s of channel c in every kernel.  A
 // plane (n, c) starts at element (n C + c) HW, which is only 4-byte aligned when HW is odd: each
 // plane is walked as a scalar head, an aligned float4 body and a scalar tail.
+//
+// bf16: every kernel is a template on the element type T of the (N, C, HW) tensors.  T = __bf16 reads 8 elements per
+// 16-byte access (heads of (8 - base % 8) % 8 and tails of up to 7 elements, pieces of a plane multiples of 8), widens
+// them to f32 on the load and rounds each output to bf16 once, to nearest even, on the store.  Everything in between is
+// the f32 arithmetic of the f32 kernels: gamma, beta, mean, rstd, the running statistics, dgamma, dbeta, the kept
+// sums, gg_gamma, gg_beta, g_gamma and every partial stay f32; y is recomputed from x in every pass and s is taken from
+// that f32 y, never from a rounded z.  SEG stays 4096 elements, so S, Q and the workspace are those of f32.
 #include "amk_common.h"
 
 namespace amk_bn {
@@ -31,7 +39,8 @@ struct Geo {
   int S;      // segments per channel
 };
 
-static Geo make_geo(int N, int C, int64_t HW) {
+// VW: elements per 16-byte access (4 for f32, 8 for bf16); pieces are multiples of it.
+static Geo make_geo(int N, int C, int64_t HW, int VW = 4) {
   Geo g;
   g.N = N; g.C = C; g.HW = HW;
   if (HW <= SEG) {
@@ -42,7 +51,7 @@ static Geo make_geo(int N, int C, int64_t HW) {
   } else {
     g.PP = 1;
     g.Q = (int)((HW + SEG - 1) / SEG);
-    g.L = (((HW + g.Q - 1) / g.Q) + 3) & ~(int64_t)3;
+    g.L = (((HW + g.Q - 1) / g.Q) + VW - 1) & ~(int64_t)(VW - 1);
     g.S = N * g.Q;
   }
   return g;
@@ -89,21 +98,52 @@ __device__ __forceinline__ void st(float* p, const float (&v)[W]) {
   else *p = v[0];
 }
 
-// Calls f(Width<4>, off) for every aligned 4-element run and f(Width<1>, off) for every edge element
-// of segment s of channel c; `off` indexes the (N, C, HW) tensor.  Tensor bases are 16-byte aligned.
-template <class F>
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+template <int W>
+__device__ __forceinline__ void ld(const __bf16* p, float (&v)[W]) {
+  if constexpr (W == 8) {
+    const bf16x8 t = *reinterpret_cast<const bf16x8*>(p);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = (float)t[k];
+  } else {
+    v[0] = (float)*p;
+  }
+}
+
+// the one rounding of a bf16 output: f32 -> bf16, to nearest even
+template <int W>
+__device__ __forceinline__ void st(__bf16* p, const float (&v)[W]) {
+  if constexpr (W == 8) {
+    bf16x8 t;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) t[k] = (__bf16)v[k];
+    *reinterpret_cast<bf16x8*>(p) = t;
+  } else {
+    *p = (__bf16)v[0];
+  }
+}
+
+// elements per 16-byte access and its log2
+template <class T> struct Vec { static constexpr int W = 4, SH = 2; };
+template <> struct Vec<__bf16> { static constexpr int W = 8, SH = 3; };
+
+// Calls f(Width<VW>, off) for every aligned VW-element run (VW = 4 for f32, 8 for bf16) and f(Width<1>, off) for every
+// edge element of segment s of channel c; `off` indexes the (N, C, HW) tensor of T.  Tensor bases are 16-byte aligned.
+template <class T, class F>
 __device__ __forceinline__ void seg_walk(const Geo& g, int c, int s, F&& f) {
   const Seg r = seg_of(g, s);
   const int64_t len = r.e1 - r.e0;
   const int t = threadIdx.x;
   for (int p = r.p0; p < r.p1; ++p) {
     const int64_t base = ((int64_t)p * g.C + c) * g.HW + r.e0;
-    const int head = (int)min((int64_t)((4 - (base & 3)) & 3), len);
-    const int64_t nv = (len - head) >> 2;
-    const int tail = (int)(len - head - 4 * nv);
-    for (int64_t i = t; i < nv; i += BLOCK) f(Width<4>{}, base + head + 4 * i);
+    constexpr int VW = Vec<T>::W;
+    const int head = (int)min((int64_t)((VW - (base & (VW - 1))) & (VW - 1)), len);
+    const int64_t nv = (len - head) >> Vec<T>::SH;
+    const int tail = (int)(len - head - VW * nv);
+    for (int64_t i = t; i < nv; i += BLOCK) f(Width<VW>{}, base + head + VW * i);
     if (t < head) f(Width<1>{}, base + t);
-    else if (t < head + tail) f(Width<1>{}, base + 4 * nv + t);
+    else if (t < head + tail) f(Width<1>{}, base + VW * nv + t);
   }
 }
 
@@ -172,11 +212,12 @@ __device__ __forceinline__ void fold_sums(const float* __restrict__ part, const 
 
 // ---------------------------------------------------------------- forward
 // part (C, S, 2): per-segment mean and M2, each from two passes over the segment (the second hits L2).
-__global__ __launch_bounds__(BLOCK) void stats_kernel(const float* __restrict__ x, Geo g, float* __restrict__ part) {
+template <class T>
+__global__ __launch_bounds__(BLOCK) void stats_kernel(const T* __restrict__ x, Geo g, float* __restrict__ part) {
   __shared__ float lds[WAVES * 3];
   const int s = blockIdx.x, c = blockIdx.y;
   float v[1] = {0.f};
-  seg_walk(g, c, s, [&](auto w, int64_t off) {
+  seg_walk<T>(g, c, s, [&](auto w, int64_t off) {
     constexpr int W = decltype(w)::value;
     float xv[W];
     ld<W>(x + off, xv);
@@ -187,7 +228,7 @@ __global__ __launch_bounds__(BLOCK) void stats_kernel(const float* __restrict__ 
   const float cnt = seg_count(g, s);
   const float mean = cnt > 0.f ? v[0] / cnt : 0.f;
   float q[1] = {0.f};
-  seg_walk(g, c, s, [&](auto w, int64_t off) {
+  seg_walk<T>(g, c, s, [&](auto w, int64_t off) {
     constexpr int W = decltype(w)::value;
     float xv[W];
     ld<W>(x + off, xv);
@@ -201,9 +242,10 @@ __global__ __launch_bounds__(BLOCK) void stats_kernel(const float* __restrict__ 
   }
 }
 
+template <class T>
 __global__ __launch_bounds__(BLOCK) void fwd_apply_kernel(
-    const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta, Geo g,
-    const float* __restrict__ part, float eps, float momentum, float slope, float* __restrict__ z,
+    const T* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta, Geo g,
+    const float* __restrict__ part, float eps, float momentum, float slope, T* __restrict__ z,
     float* __restrict__ mean_out, float* __restrict__ rstd_out, float* __restrict__ run_mean,
     float* __restrict__ run_var) {
   __shared__ float lds[WAVES * 3];
@@ -223,7 +265,7 @@ __global__ __launch_bounds__(BLOCK) void fwd_apply_kernel(
     if (run_mean) run_mean[c] = (1.f - momentum) * run_mean[c] + momentum * mu;
     if (run_var) run_var[c] = (1.f - momentum) * run_var[c] + momentum * (a[2] / (n - 1.f));
   }
-  seg_walk(g, c, s, [&](auto w, int64_t off) {
+  seg_walk<T>(g, c, s, [&](auto w, int64_t off) {
     constexpr int W = decltype(w)::value;
     float xv[W];
     ld<W>(x + off, xv);
@@ -251,15 +293,16 @@ __device__ __forceinline__ Chn chn(const float* gamma, const float* beta, const 
 
 // ---------------------------------------------------------------- first-order backward
 // part (C, S, 2): per-segment sums of gy and gy * xh, gy = s * gz.
+template <class T>
 __global__ __launch_bounds__(BLOCK) void bwd_reduce_kernel(
-    const float* __restrict__ gz, const float* __restrict__ x, const float* __restrict__ gamma,
+    const T* __restrict__ gz, const T* __restrict__ x, const float* __restrict__ gamma,
     const float* __restrict__ beta, const float* __restrict__ mean, const float* __restrict__ rstd, Geo g, float slope,
     float* __restrict__ part) {
   __shared__ float lds[WAVES * 3];
   const int s = blockIdx.x, c = blockIdx.y;
   const Chn h = chn(gamma, beta, mean, rstd, c);
   float v[2] = {0.f, 0.f};
-  seg_walk(g, c, s, [&](auto w, int64_t off) {
+  seg_walk<T>(g, c, s, [&](auto w, int64_t off) {
     constexpr int W = decltype(w)::value;
     float xv[W], gv[W];
     ld<W>(x + off, xv);
@@ -279,10 +322,11 @@ __global__ __launch_bounds__(BLOCK) void bwd_reduce_kernel(
 }
 
 // gx = gamma r (gy - Sgy/n - xh Sgyx/n); sums (2, C) = (Sgy, Sgyx), dbeta = Sgy, dgamma = Sgyx.
+template <class T>
 __global__ __launch_bounds__(BLOCK) void bwd_apply_kernel(
-    const float* __restrict__ gz, const float* __restrict__ x, const float* __restrict__ gamma,
+    const T* __restrict__ gz, const T* __restrict__ x, const float* __restrict__ gamma,
     const float* __restrict__ beta, const float* __restrict__ mean, const float* __restrict__ rstd, Geo g, float slope,
-    const float* __restrict__ part, float* __restrict__ gx, float* __restrict__ sums, float* __restrict__ dgamma,
+    const float* __restrict__ part, T* __restrict__ gx, float* __restrict__ sums, float* __restrict__ dgamma,
     float* __restrict__ dbeta) {
   __shared__ float lds[WAVES * 3];
   const int s = blockIdx.x, c = blockIdx.y;
@@ -297,7 +341,7 @@ __global__ __launch_bounds__(BLOCK) void bwd_apply_kernel(
   }
   const float inv_n = 1.f / (float)((double)g.N * (double)g.HW);
   const float A = v[0] * inv_n, B = v[1] * inv_n;
-  seg_walk(g, c, s, [&](auto w, int64_t off) {
+  seg_walk<T>(g, c, s, [&](auto w, int64_t off) {
     constexpr int W = decltype(w)::value;
     float xv[W], gv[W];
     ld<W>(x + off, xv);
@@ -314,15 +358,16 @@ __global__ __launch_bounds__(BLOCK) void bwd_apply_kernel(
 
 // ---------------------------------------------------------------- double backward
 // part (C, S, 3): per-segment sums of ggx, ggx * xh, ggx * gy.
+template <class T>
 __global__ __launch_bounds__(BLOCK) void bwd_bwd_reduce_kernel(
-    const float* __restrict__ ggx, const float* __restrict__ gz, const float* __restrict__ x,
+    const T* __restrict__ ggx, const T* __restrict__ gz, const T* __restrict__ x,
     const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ mean,
     const float* __restrict__ rstd, Geo g, float slope, float* __restrict__ part) {
   __shared__ float lds[WAVES * 3];
   const int s = blockIdx.x, c = blockIdx.y;
   const Chn h = chn(gamma, beta, mean, rstd, c);
   float v[3] = {0.f, 0.f, 0.f};
-  seg_walk(g, c, s, [&](auto w, int64_t off) {
+  seg_walk<T>(g, c, s, [&](auto w, int64_t off) {
     constexpr int W = decltype(w)::value;
     float xv[W], gv[W], qv[W];
     ld<W>(x + off, xv);
@@ -347,12 +392,13 @@ __global__ __launch_bounds__(BLOCK) void bwd_bwd_reduce_kernel(
 //   g_gz = s [gamma r (ggx - C - xh D) + gg_gamma xh + gg_beta]
 //   g_x  = -gamma r^2 [xh (E - AC - 3BD) + B (ggx - C) + D (gy - A)] + gg_gamma r (gy - A - xh B)
 //   g_gamma = n r (E - AC - BD)
+template <class T>
 __global__ __launch_bounds__(BLOCK) void bwd_bwd_apply_kernel(
-    const float* __restrict__ ggx, const float* __restrict__ gg_gamma, const float* __restrict__ gg_beta,
-    const float* __restrict__ gz, const float* __restrict__ x, const float* __restrict__ gamma,
+    const T* __restrict__ ggx, const float* __restrict__ gg_gamma, const float* __restrict__ gg_beta,
+    const T* __restrict__ gz, const T* __restrict__ x, const float* __restrict__ gamma,
     const float* __restrict__ beta, const float* __restrict__ mean, const float* __restrict__ rstd,
-    const float* __restrict__ sums, Geo g, float slope, const float* __restrict__ part, float* __restrict__ g_gz,
-    float* __restrict__ g_x, float* __restrict__ g_gamma) {
+    const float* __restrict__ sums, Geo g, float slope, const float* __restrict__ part, T* __restrict__ g_gz,
+    T* __restrict__ g_x, float* __restrict__ g_gamma) {
   __shared__ float lds[WAVES * 3];
   const int s = blockIdx.x, c = blockIdx.y;
   const Chn h = chn(gamma, beta, mean, rstd, c);
@@ -366,7 +412,7 @@ __global__ __launch_bounds__(BLOCK) void bwd_bwd_apply_kernel(
   const float k1 = E - A * Cc - 3.f * B * D;       // coefficient of xh in g_x's bracket
   const float gr2 = h.scale * h.r;                  // gamma r^2
   const float gr = ggg * h.r;
-  seg_walk(g, c, s, [&](auto w, int64_t off) {
+  seg_walk<T>(g, c, s, [&](auto w, int64_t off) {
     constexpr int W = decltype(w)::value;
     float xv[W], gv[W], qv[W];
     ld<W>(x + off, xv);
@@ -398,9 +444,43 @@ static bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) ==
   AMK_CHECK_SUPPORTED(C <= 65535 && (int64_t)N * HW <= ((int64_t)1 << 31),                       \
                       what ": shape N %d C %d HW %lld not supported", N, C, (long long)HW)
 
+template <class T>
+static void launch_fwd(const T* x, const float* gamma, const float* beta, int N, int C, int64_t HW, float eps,
+                       float momentum, float slope, T* z, float* mean, float* rstd, float* running_mean,
+                       float* running_var, float* ws, hipStream_t st) {
+  const Geo g = make_geo(N, C, HW, Vec<T>::W);
+  const dim3 grid(g.S, C), block(BLOCK);
+  hipLaunchKernelGGL(stats_kernel<T>, grid, block, 0, st, x, g, ws);
+  hipLaunchKernelGGL(fwd_apply_kernel<T>, grid, block, 0, st, x, gamma, beta, g, ws, eps, momentum, slope, z, mean,
+                     rstd, running_mean, running_var);
+}
+
+template <class T>
+static void launch_bwd(const T* gz, const T* x, const float* gamma, const float* beta, const float* mean,
+                       const float* rstd, int N, int C, int64_t HW, float slope, T* gx, float* sums, float* dgamma,
+                       float* dbeta, float* ws, hipStream_t st) {
+  const Geo g = make_geo(N, C, HW, Vec<T>::W);
+  const dim3 grid(g.S, C), block(BLOCK);
+  hipLaunchKernelGGL(bwd_reduce_kernel<T>, grid, block, 0, st, gz, x, gamma, beta, mean, rstd, g, slope, ws);
+  hipLaunchKernelGGL(bwd_apply_kernel<T>, grid, block, 0, st, gz, x, gamma, beta, mean, rstd, g, slope, ws, gx, sums,
+                     dgamma, dbeta);
+}
+
+template <class T>
+static void launch_bwd_bwd(const T* ggx, const float* gg_gamma, const float* gg_beta, const T* gz, const T* x,
+                           const float* gamma, const float* beta, const float* mean, const float* rstd,
+                           const float* sums, int N, int C, int64_t HW, float slope, T* g_gz, T* g_x, float* g_gamma,
+                           float* ws, hipStream_t st) {
+  const Geo g = make_geo(N, C, HW, Vec<T>::W);
+  const dim3 grid(g.S, C), block(BLOCK);
+  hipLaunchKernelGGL(bwd_bwd_reduce_kernel<T>, grid, block, 0, st, ggx, gz, x, gamma, beta, mean, rstd, g, slope, ws);
+  hipLaunchKernelGGL(bwd_bwd_apply_kernel<T>, grid, block, 0, st, ggx, gg_gamma, gg_beta, gz, x, gamma, beta, mean,
+                     rstd, sums, g, slope, ws, g_gz, g_x, g_gamma);
+}
+
 extern "C" int64_t amk_bnact_ws_floats(int N, int C, int64_t HW) {
   if (N <= 0 || C <= 0 || HW <= 0) return 0;
-  return (int64_t)C * make_geo(N, C, HW).S * 3;
+  return (int64_t)C * make_geo(N, C, HW).S * 3;   // S does not depend on the element type
 }
 
 extern "C" int amk_bnact_fwd(const float* x, const float* gamma, const float* beta, int N, int C, int64_t HW,
@@ -410,12 +490,8 @@ extern "C" int amk_bnact_fwd(const float* x, const float* gamma, const float* be
   AMK_BN_SHAPE("amk_bnact_fwd");
   AMK_CHECK_ARG(N * HW > 1, "amk_bnact_fwd: a channel needs more than one value");
   AMK_CHECK_ARG(a16(x) && a16(z), "amk_bnact_fwd: x and z must be 16-byte aligned");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const Geo g = make_geo(N, C, HW);
-  const dim3 grid(g.S, C), block(BLOCK);
-  hipLaunchKernelGGL(stats_kernel, grid, block, 0, st, x, g, ws);
-  hipLaunchKernelGGL(fwd_apply_kernel, grid, block, 0, st, x, gamma, beta, g, ws, eps, momentum, slope, z, mean, rstd,
-                     running_mean, running_var);
+  launch_fwd<float>(x, gamma, beta, N, C, HW, eps, momentum, slope, z, mean, rstd, running_mean, running_var, ws,
+                    static_cast<hipStream_t>(stream));
   AMK_CHECK_LAUNCH("amk_bnact_fwd");
   return AMK_OK;
 }
@@ -426,12 +502,8 @@ extern "C" int amk_bnact_bwd(const float* gz, const float* x, const float* gamma
   AMK_CHECK_ARG(gz && x && gamma && beta && mean && rstd && gx && sums && ws, "amk_bnact_bwd: null pointer");
   AMK_BN_SHAPE("amk_bnact_bwd");
   AMK_CHECK_ARG(a16(gz) && a16(x) && a16(gx), "amk_bnact_bwd: gz, x and gx must be 16-byte aligned");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const Geo g = make_geo(N, C, HW);
-  const dim3 grid(g.S, C), block(BLOCK);
-  hipLaunchKernelGGL(bwd_reduce_kernel, grid, block, 0, st, gz, x, gamma, beta, mean, rstd, g, slope, ws);
-  hipLaunchKernelGGL(bwd_apply_kernel, grid, block, 0, st, gz, x, gamma, beta, mean, rstd, g, slope, ws, gx, sums,
-                     dgamma, dbeta);
+  launch_bwd<float>(gz, x, gamma, beta, mean, rstd, N, C, HW, slope, gx, sums, dgamma, dbeta, ws,
+                    static_cast<hipStream_t>(stream));
   AMK_CHECK_LAUNCH("amk_bnact_bwd");
   return AMK_OK;
 }
@@ -445,12 +517,52 @@ extern "C" int amk_bnact_bwd_bwd(const float* ggx, const float* gg_gamma, const 
   AMK_BN_SHAPE("amk_bnact_bwd_bwd");
   AMK_CHECK_ARG(a16(ggx) && a16(gz) && a16(x) && a16(g_gz) && a16(g_x),
                 "amk_bnact_bwd_bwd: ggx, gz, x, g_gz and g_x must be 16-byte aligned");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const Geo g = make_geo(N, C, HW);
-  const dim3 grid(g.S, C), block(BLOCK);
-  hipLaunchKernelGGL(bwd_bwd_reduce_kernel, grid, block, 0, st, ggx, gz, x, gamma, beta, mean, rstd, g, slope, ws);
-  hipLaunchKernelGGL(bwd_bwd_apply_kernel, grid, block, 0, st, ggx, gg_gamma, gg_beta, gz, x, gamma, beta, mean, rstd,
-                     sums, g, slope, ws, g_gz, g_x, g_gamma);
+  launch_bwd_bwd<float>(ggx, gg_gamma, gg_beta, gz, x, gamma, beta, mean, rstd, sums, N, C, HW, slope, g_gz, g_x,
+                        g_gamma, ws, static_cast<hipStream_t>(stream));
   AMK_CHECK_LAUNCH("amk_bnact_bwd_bwd");
+  return AMK_OK;
+}
+
+// ---------------------------------------------------------------- bf16 x, z, gz, gx, ggx, g_gz, g_x
+static const __bf16* cb(const void* p) { return static_cast<const __bf16*>(p); }
+static __bf16* mb(void* p) { return static_cast<__bf16*>(p); }
+
+extern "C" int amk_bnact_bf16_fwd(const void* x, const float* gamma, const float* beta, int N, int C, int64_t HW,
+                                  float eps, float momentum, float slope, void* z, float* mean, float* rstd,
+                                  float* running_mean, float* running_var, float* ws, void* stream) {
+  AMK_CHECK_ARG(x && gamma && beta && z && mean && rstd && ws, "amk_bnact_bf16_fwd: null pointer");
+  AMK_BN_SHAPE("amk_bnact_bf16_fwd");
+  AMK_CHECK_ARG(N * HW > 1, "amk_bnact_bf16_fwd: a channel needs more than one value");
+  AMK_CHECK_ARG(a16(x) && a16(z), "amk_bnact_bf16_fwd: x and z must be 16-byte aligned");
+  launch_fwd<__bf16>(cb(x), gamma, beta, N, C, HW, eps, momentum, slope, mb(z), mean, rstd, running_mean, running_var,
+                     ws, static_cast<hipStream_t>(stream));
+  AMK_CHECK_LAUNCH("amk_bnact_bf16_fwd");
+  return AMK_OK;
+}
+
+extern "C" int amk_bnact_bf16_bwd(const void* gz, const void* x, const float* gamma, const float* beta,
+                                  const float* mean, const float* rstd, int N, int C, int64_t HW, float slope,
+                                  void* gx, float* sums, float* dgamma, float* dbeta, float* ws, void* stream) {
+  AMK_CHECK_ARG(gz && x && gamma && beta && mean && rstd && gx && sums && ws, "amk_bnact_bf16_bwd: null pointer");
+  AMK_BN_SHAPE("amk_bnact_bf16_bwd");
+  AMK_CHECK_ARG(a16(gz) && a16(x) && a16(gx), "amk_bnact_bf16_bwd: gz, x and gx must be 16-byte aligned");
+  launch_bwd<__bf16>(cb(gz), cb(x), gamma, beta, mean, rstd, N, C, HW, slope, mb(gx), sums, dgamma, dbeta, ws,
+                     static_cast<hipStream_t>(stream));
+  AMK_CHECK_LAUNCH("amk_bnact_bf16_bwd");
+  return AMK_OK;
+}
+
+extern "C" int amk_bnact_bf16_bwd_bwd(const void* ggx, const float* gg_gamma, const float* gg_beta, const void* gz,
+                                      const void* x, const float* gamma, const float* beta, const float* mean,
+                                      const float* rstd, const float* sums, int N, int C, int64_t HW, float slope,
+                                      void* g_gz, void* g_x, float* g_gamma, float* ws, void* stream) {
+  AMK_CHECK_ARG(ggx && gz && x && gamma && beta && mean && rstd && sums && g_gz && g_x && ws,
+                "amk_bnact_bf16_bwd_bwd: null pointer");
+  AMK_BN_SHAPE("amk_bnact_bf16_bwd_bwd");
+  AMK_CHECK_ARG(a16(ggx) && a16(gz) && a16(x) && a16(g_gz) && a16(g_x),
+                "amk_bnact_bf16_bwd_bwd: ggx, gz, x, g_gz and g_x must be 16-byte aligned");
+  launch_bwd_bwd<__bf16>(cb(ggx), gg_gamma, gg_beta, cb(gz), cb(x), gamma, beta, mean, rstd, sums, N, C, HW, slope,
+                         mb(g_gz), mb(g_x), g_gamma, ws, static_cast<hipStream_t>(stream));
+  AMK_CHECK_LAUNCH("amk_bnact_bf16_bwd_bwd");
   return AMK_OK;
 }

@@ -698,7 +698,8 @@ int amk_gemm_bf16_swiglu_bwd(const void* dy, int64_t lddy, const void* w3, int64
 
 /* --------------------------------------------------------------------------
  * Training-mode BatchNorm2d + LeakyReLU(slope) of the PatchGAN discriminator (csrc/discr_norm.hip), f32, contiguous
- * NCHW x (N, C, HW); reference: models/utils/discriminator.py (BatchNorm2d followed by LeakyReLU(0.2)).
+ * NCHW x (N, C, HW); reference: models/utils/discriminator.py:34-35,42-43 (BatchNorm2d followed by LeakyReLU(0.2)).
+ * (The bf16 form for the autocast step, amk_bnact_bf16_*, follows below.)
  * Per channel, n = N HW: mu and var are the biased batch statistics, r = (var + eps)^-1/2, xh = (x - mu) r,
  * y = gamma xh + beta, z = y > 0 ? y : slope y, s = dz/dy (1 or slope).  y is recomputed from x, never stored.
  *   fwd     : z; mean, rstd (C) for the backward; running_mean / running_var (C, may be NULL) updated as torch does
@@ -724,6 +725,28 @@ int amk_bnact_bwd_bwd(const float* ggx, const float* gg_gamma, const float* gg_b
                       const float* gamma, const float* beta, const float* mean, const float* rstd, const float* sums,
                       int N, int C, int64_t HW, float slope, float* g_gz, float* g_x, float* g_gamma, float* ws,
                       void* stream);
+
+/* The same three entry points under bf16 autocast (csrc/discr_norm.hip, the same kernels on bf16 elements): x, z, gz, gx,
+ * ggx, g_gz and g_x are bf16 (const void* / void*); gamma, beta, mean, rstd, the running statistics, dgamma, dbeta, sums,
+ * gg_gamma, gg_beta, g_gamma and ws f32.  Replaces what models/utils/discriminator.py:34-35 and :42-43 (BatchNorm2d
+ * followed by LeakyReLU(0.2, True)) run as under torch.autocast(dtype=bfloat16), the precision cfg/vitvqgan.yaml:73
+ * trains in: MIOpen's batch norm on the convolution's bf16 output, ATen's leaky_relu_ and leaky_relu_backward, and for
+ * the gradient penalty (trainers/vitgqgan.py:115-131) ATen's composite double backward.  The bf16 values are widened to f32
+ * on the load; the statistics (two passes, Chan's merge), y = fmaf(x, scale, shift) recomputed from x in every pass, s
+ * taken from that f32 y and every sum are the f32 arithmetic of amk_bnact_*; each bf16 output is rounded once, to nearest
+ * even, on the store.  16-byte accesses hold 8 elements: a plane is walked as a scalar head of (8 - base % 8) % 8 elements,
+ * an aligned body and a scalar tail of up to 7.  The same refusals and return codes, launches, workspace
+ * (amk_bnact_ws_floats) and reproducibility as amk_bnact_*. */
+int amk_bnact_bf16_fwd(const void* x, const float* gamma, const float* beta, int N, int C, int64_t HW, float eps,
+                       float momentum, float slope, void* z, float* mean, float* rstd, float* running_mean,
+                       float* running_var, float* ws, void* stream);
+int amk_bnact_bf16_bwd(const void* gz, const void* x, const float* gamma, const float* beta, const float* mean,
+                       const float* rstd, int N, int C, int64_t HW, float slope, void* gx, float* sums, float* dgamma,
+                       float* dbeta, float* ws, void* stream);
+int amk_bnact_bf16_bwd_bwd(const void* ggx, const float* gg_gamma, const float* gg_beta, const void* gz, const void* x,
+                           const float* gamma, const float* beta, const float* mean, const float* rstd,
+                           const float* sums, int N, int C, int64_t HW, float slope, void* g_gz, void* g_x,
+                           float* g_gamma, float* ws, void* stream);
 
 /* --------------------------------------------------------------------------
  * GroupNorm(G, C, eps) + optional Swish of the conv VQGAN (csrc/gn_act.hip), f32, contiguous NCHW x (N, C, HW);

@@ -112,7 +112,7 @@ class Parti(nn.Module):
         if capacity < self.vq.num_patches:
             raise ValueError(f"capacity {capacity} is smaller than the {self.vq.num_patches} image tokens of a sample")
         text_embeds = self.context_norm(self._context(text_hidden))
-        return self.transformer_decoder.init_state(text_embeds, capacity, out=out)
+        return self.transformer_decoder.init_state(text_embeds, capacity, out=out, head=self.to_logits)
 
     @torch.no_grad()
     def next_logits(self, state, prev_tokens=None):
@@ -128,7 +128,7 @@ class Parti(nn.Module):
             pe = self.pos_enc.pe.index_select(0, state.pos - 1)
             x = self.pos_enc.dropout(self.token_emb(prev_tokens.view(-1, 1)) + pe)
         out = self.transformer_decoder.step(self.init_norm(x), state)
-        logits = self.to_logits(self.final_norm(out))[:, 0, :]
+        logits = self.transformer_decoder.logits(out, state, self.final_norm, self.to_logits)
         state.advance()
         return logits
 
@@ -192,6 +192,7 @@ class Parti(nn.Module):
         steps = self.vq.num_patches
         key = (tuple(text_hidden.shape), text_hidden.device, None if gumbel is None else tuple(gumbel.shape),
                float(tau), float(p), steps, self.training, ops.GEMM_MODE,
+               self.transformer_decoder.decode_dtype(text_hidden.device), ops.DECODE_BF16,
                tuple(t.data_ptr() for t in list(self.parameters()) + list(self.buffers())))
         cached = _DECODE_GRAPHS.get(self)
         if cached is None or cached["key"] != key:

@@ -120,15 +120,78 @@ class Decoder(nn.Module):
         return out
 
     # ---- KV-cached decoding: the causal forward, one row per step (models/decoding.py, csrc/attn_decode.hip)
+    @staticmethod
+    def decode_dtype(device, dtype=None):
+        """The dtype of a new decode state: ``dtype`` if given, else bf16 where bf16 autocast is enabled for the device
+        and AMK_DECODE_BF16 is on, else f32."""
+        if dtype is not None:
+            if dtype not in (torch.float32, torch.bfloat16):
+                raise ValueError(f"a decode state is float32 or bfloat16, not {dtype}")
+            return dtype
+        device = torch.device(device)
+        if (ops.DECODE_BF16 and device.type == "cuda" and torch.is_autocast_enabled()
+                and torch.get_autocast_dtype("cuda") == torch.bfloat16):
+            return torch.bfloat16
+        return torch.float32
+
+    def _decode_weights(self, head):
+        """[(name, [parameters stacked by rows])] per layer, then the head's: every Linear weight a bf16 step reads."""
+        per_layer = []
+        for layer in self.layers:
+            sa, ca, ff = layer.self_attn, layer.cross_attn, layer.feed_forward.ff
+            per_layer.append({"qkv": [sa.q[0].weight, sa.kv[0].weight], "wo": [sa.W_o.weight], "cq": [ca.q[0].weight],
+                              "ckv": [ca.kv[0].weight], "cwo": [ca.W_o.weight], "ff1": [ff[0].weight], "ff2": [ff[3].weight]})
+        return per_layer, ({"head": [head.weight]} if head is not None else None)
+
+    @staticmethod
+    def _fill_weights(dst, src):
+        for name, params in src.items():
+            r = 0
+            for p in params:
+                ops.fill_w16(dst[name][r:r + p.shape[0]], p)
+                r += p.shape[0]
+
     @torch.no_grad()
-    def init_state(self, context, capacity, context_mask=None, out=None):
+    def init_state(self, context, capacity, context_mask=None, out=None, dtype=None, head=None):
         """The state of a decode of up to ``capacity`` rows over ``context`` (B, L, dim): empty self-attention caches
         and every layer's cross-attention K|V, projected here once.  out: a state of the same shapes to refill in place
-        (its buffers keep their addresses: a captured step stays valid)."""
+        (its buffers keep their addresses: a captured step stays valid).
+
+        dtype: None = bf16 where bf16 autocast is enabled for the device and AMK_DECODE_BF16 is on, else f32.  A bf16
+        state holds bf16 caches and cross K|V and ITS OWN bf16 copies of every Linear weight the step reads (self-attention
+        q and kv as one (3*h*d, dim) matrix; ``head``: the Linear onto the logits, read by ``logits``), filled from the
+        optimizer's current bf16 shadow or the f32 master; ``out=`` refills them in place."""
         if capacity < 1:
             raise ValueError(f"capacity must be positive (got {capacity})")
-        cross = [layer.cross_attn.project_context(context) for layer in self.layers]
+        if out is not None and dtype is not None and dtype != out.dtype:
+            raise ValueError("init_state(out=...): the state was made for another dtype")
+        dtype = out.dtype if out is not None else self.decode_dtype(context.device, dtype)
         mask = ops._mask_u8(context_mask, (context.shape[0], context.shape[1]), "context_mask")
+        weights = head_w = None
+        if dtype == torch.bfloat16:
+            if torch.is_autocast_enabled() and not ops.DECODE_BF16:
+                raise RuntimeError(ops.DECODE_AUTOCAST_REFUSAL)
+            if not context.is_cuda:
+                raise RuntimeError("amk ops run only on MI355X (HIP) tensors; got a CPU tensor. There is no CPU fallback.")
+            src_layers, src_head = self._decode_weights(head)
+            if out is not None:
+                weights, head_w = out.weights, out.head
+                if (head_w is None) != (src_head is None):
+                    raise ValueError("init_state(out=...): the state was made with / without a head")
+            else:
+                alloc = lambda src: {k: ops.empty_w16(sum(p.shape[0] for p in ps), ps[0].shape[1], context.device)  # noqa: E731
+                                     for k, ps in src.items()}
+                weights = [alloc(src) for src in src_layers]
+                head_w = alloc(src_head) if src_head is not None else None
+            for dst, src in zip(weights, src_layers):
+                self._fill_weights(dst, src)
+            if src_head is not None:
+                self._fill_weights(head_w, src_head)
+            with torch.autocast("cuda", enabled=False):
+                c16 = context.to(torch.bfloat16)
+                cross = [F.linear(c16, w["ckv"]) for w in weights]   # (B, L, 2*h*d) bf16, once per decode
+        else:
+            cross = [layer.cross_attn.project_context(context) for layer in self.layers]
         if out is not None:
             if (out.capacity != capacity or out.cross_kv[0].shape != cross[0].shape or len(out.cross_kv) != len(cross)
                     or (out.context_mask is None) != (mask is None)):
@@ -140,29 +203,90 @@ class Decoder(nn.Module):
             out.reset()
             return out
         b, width = context.shape[0], cross[0].shape[2]
-        self_kv = [torch.empty((b, capacity, width), device=context.device, dtype=torch.float32) for _ in self.layers]
+        self_kv = [torch.empty((b, capacity, width), device=context.device, dtype=dtype) for _ in self.layers]
         ws = None
         if context.is_cuda:   # one workspace for every decode call of a step: the calls are ordered on the stream
             attn = self.layers[0].self_attn
             need = max(ops.attention_decode_ws_floats(b, attn.num_heads, attn.dim_head, n) for n in (capacity, context.shape[1]))
             ws = torch.empty((need,), device=context.device, dtype=torch.float32)
-        return DecoderState(self_kv, cross, mask, capacity, ws)
+        return DecoderState(self_kv, [c.contiguous() for c in cross], mask, capacity, ws, weights=weights, head=head_w)
 
     @torch.no_grad()
     def step(self, x, state):
         """``forward`` with the causal mask for ONE new row x (B, 1, dim) at the state's position: the row's keys and
         values join the caches, the earlier rows are read from them.  The position itself is advanced by the caller
-        (``state.advance()``) once the row is through."""
+        (``state.advance()``) once the row is through.  On a bf16 state the step runs with autocast disabled inside,
+        whatever the caller's context (``_step_bf16``); an f32 state runs outside autocast only."""
         if x.dim() != 3 or x.shape[1] != 1 or x.shape[0] != state.batch:
             raise ValueError(f"step takes one row per sequence, (B={state.batch}, 1, dim); got {tuple(x.shape)}")
         if state.host_pos >= state.capacity:
             raise RuntimeError(f"the decode state is full: {state.host_pos} of {state.capacity} rows")
+        if state.dtype == torch.bfloat16:
+            with torch.autocast("cuda", enabled=False):
+                return self._step_bf16(x.float(), state)
+        if x.is_cuda and torch.is_autocast_enabled():
+            raise RuntimeError(ops.DECODE_AUTOCAST_REFUSAL)
         for layer, self_kv, cross_kv in zip(self.layers, state.self_kv, state.cross_kv):
             x, y = layer.norm2(x, layer.self_attn.decode_step(layer.norm1(x), self_kv, state.pos, ws=state.ws))
             x, y = layer.norm3(x, layer.cross_attn.decode_step(y, cross_kv, context_mask=state.context_mask, append=False,
                                                                    ws=state.ws))
             x = layer.feed_forward(y) + x
         return x
+
+    def _step_bf16(self, x, state):
+        """The step on a bf16 state.  The residual stream x stays f32; every LayerNorm that only feeds projections
+        writes bf16 directly (amk_add_layernorm_mixed_fwd, the bf16 branch output as its bf16 operand and the f32
+        stream as the residual); projections, W_o and the FFN's two Linear layers run on the row GEMM
+        (amk_gemm_rows_bf16) with bf16 output, q and kv of self-attention as ONE product whose column slices the
+        attention kernel reads in place; the FFN's gate + LayerNorm is amk_geglu_ln_bf16_fwd, or -- where its inner
+        width is no multiple of 8 or above 4096, as int(dim * 8 / 3) is at dim 64 and 512 -- gelu(val) * gate and the
+        LayerNorm as f32 torch ops on the bf16 pre-activations.  A layer's FFN output joins the stream inside the
+        next layer's first LayerNorm."""
+        b = state.batch
+        branch = None                       # the bf16 branch output not yet added to the stream
+        for layer, w, self_kv, cross_kv in zip(self.layers, state.weights, state.self_kv, state.cross_kv):
+            sa, ca = layer.self_attn, layer.cross_attn
+            hd = sa.num_heads * sa.dim_head
+            if branch is None:
+                y = ops.layer_norm_to_bf16(x, None, layer.norm1.gamma, layer.norm1.beta)[1]
+            else:
+                x, y = ops.layer_norm_to_bf16(branch, x, layer.norm1.gamma, layer.norm1.beta)
+            qkv = ops.linear_rows(y.view(b, -1), w["qkv"]).view(b, 1, 3 * hd)
+            o = ops.attention_decode(qkv[:, :, :hd], qkv[:, :, hd:], self_kv, state.pos, sa.num_heads, sa.dim_head, sa.scale,
+                                     ws=state.ws)
+            o = ops.linear_rows(o.view(b, hd), w["wo"], sa.W_o.bias)
+            x, y = ops.layer_norm_to_bf16(o.view(b, 1, -1), x, layer.norm2.gamma, layer.norm2.beta)
+            q = ops.linear_rows(y.view(b, -1), w["cq"]).view(b, 1, hd)
+            o = ops.attention_decode(q, None, cross_kv, None, ca.num_heads, ca.dim_head, ca.scale,
+                                     key_mask=state.context_mask, ws=state.ws)
+            o = ops.linear_rows(o.view(b, hd), w["cwo"], ca.W_o.bias)
+            x, y = ops.layer_norm_to_bf16(o.view(b, 1, -1), x, layer.norm3.gamma, layer.norm3.beta)
+            norm = layer.feed_forward.ff[2]
+            ab = ops.linear_rows(y.view(b, -1), w["ff1"])
+            inner = ab.shape[1] // 2
+            if inner % 8 == 0 and inner <= 4096 and ab.stride(0) % 8 == 0:
+                g = ops.geglu_ln_bf16_fwd(ab, norm.gamma, norm.beta)[0]
+            else:
+                val, gate = ab.float().chunk(2, dim=-1)
+                g = torch.empty((b, (inner + 7) // 8 * 8), device=ab.device, dtype=torch.bfloat16)[:, :inner]
+                g.copy_(F.layer_norm(gate * F.gelu(val), (inner,), norm.gamma, norm.beta))   # rows at a stride of 8
+            branch = ops.linear_rows(g, w["ff2"]).view(b, 1, -1)
+        return x + branch.float() if branch is not None else x
+
+    @torch.no_grad()
+    def logits(self, out, state, norm, linear):
+        """(B, n) f32 logits of a step's output ``out`` (B, 1, dim): ``linear(norm(out))``.  On a bf16 state: the
+        LayerNorm writes bf16, the product runs on the row GEMM over the state's bf16 copy of the head with the f32
+        master bias added in f32, and the logits stay f32 (the sampler and ``trace`` read f32)."""
+        if state.dtype != torch.bfloat16:
+            return linear(norm(out))[:, 0, :]
+        if state.head is None:
+            raise RuntimeError("this decode state was made without a head: pass init_state(head=...)")
+        with torch.autocast("cuda", enabled=False):
+            gamma, beta = (norm.gamma, norm.beta) if hasattr(norm, "gamma") else (norm.weight, norm.bias)
+            y = ops.layer_norm_to_bf16(out.float(), None, gamma, beta)[1]
+            lg = ops.linear_rows(y.view(state.batch, -1), state.head["head"], linear.bias, torch.float32, w32=linear.weight)
+            return lg if lg.is_contiguous() else lg.contiguous()
 
 
 class Transformer(nn.Module):
@@ -218,13 +342,14 @@ class Transformer(nn.Module):
 
     # ---- KV-cached causal decoding: ``forward``'s arithmetic row by row (``generate`` above stays the reference's loop)
     @torch.no_grad()
-    def begin_decode(self, src_seq, capacity=256):
+    def begin_decode(self, src_seq, capacity=256, out=None):
         """Encode ``src_seq`` as ``forward`` does (enc_init_norm, the all-true context mask, enc_final_norm) and return
-        the decode state for up to ``capacity`` target positions."""
+        the decode state for up to ``capacity`` target positions (bf16 under bf16 autocast, see ``Decoder.init_state``).
+        out: a state to refill in place."""
         context_mask = torch.ones(src_seq.shape, dtype=torch.bool, device=src_seq.device)
         src = self.enc_init_norm(self.pos_enc(self.enc_input_proj(src_seq)))
         context = self.enc_final_norm(self.encoder(src, context_mask=context_mask))
-        return self.decoder.init_state(context, capacity, context_mask=context_mask)
+        return self.decoder.init_state(context, capacity, context_mask=context_mask, out=out, head=self.linear)
 
     @torch.no_grad()
     def next_logits(self, state, prev_tokens):
@@ -233,7 +358,7 @@ class Transformer(nn.Module):
         pe = self.pos_enc.pe.index_select(0, state.pos)
         x = self.pos_enc.dropout(self.dec_input_proj(prev_tokens.view(-1, 1)) + pe)
         out = self.decoder.step(self.dec_init_norm(x), state)
-        logits = self.linear(self.dec_final_norm(out))[:, 0, :]
+        logits = self.decoder.logits(out, state, self.dec_final_norm, self.linear)
         state.advance()
         return logits
 

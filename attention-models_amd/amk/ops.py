@@ -461,51 +461,153 @@ def attention_decode(q2, kv_new2, cache, n_dev, num_heads, dim_head, scale, key_
     holding the number of valid cache rows (the kernel reads it on the device, so a captured step replays for every
     position).  kv_new2 (B, 1, 2*h*d): append mode -- row n of the cache becomes kv_new2 and the query attends rows
     0 .. n.  kv_new2 None: read mode -- the query attends rows 0 .. n - 1, all `capacity` rows when n_dev is None.
-    key_mask: bool / uint8 (B, capacity), True = keep.  Returns (B, 1, h*d).  f32 outside autocast only.  q2, kv_new2
-    and cache are consumed in place and must be contiguous (the projection outputs are).  ws: a float32 workspace of at
-    least attention_decode_ws_floats(B, h, d, capacity) elements to reuse across calls (DecoderState keeps one); None
+    key_mask: bool / uint8 (B, capacity), True = keep.  Returns (B, 1, h*d) in the cache's dtype.
+
+    The cache's dtype picks the kernel: float32 (amk_attn_decode) or bfloat16 (amk_attn_decode_bf16: f32 scores, softmax
+    and sums on bf16 operands, the output rounded once); q2 and kv_new2 must have the cache's dtype.  Inside or outside
+    autocast alike -- the call casts nothing.  The cache is consumed in place and must be contiguous; q2 and kv_new2 are
+    consumed in place too and may be column slices of one projection output: unit last stride, the row stride and the
+    offset multiples of 4 elements (f32) or 8 (bf16).  ws: a float32 workspace of at least
+    attention_decode_ws_floats(B, h, d, capacity) elements to reuse across calls (DecoderState keeps one); None
     allocates one."""
     if any(t is not None and t.requires_grad for t in (q2, kv_new2, cache)):
         raise RuntimeError("attention_decode is inference only: it has no backward; call it under torch.no_grad() "
                            "on tensors that do not require grad")
-    _require_device(q2, kv_new2, cache)
-    if torch.is_autocast_enabled():
-        raise RuntimeError("attention_decode runs on f32 tensors outside autocast; a bf16 cache is not implemented")
+    if cache.dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError(f"attention_decode runs on a float32 or a bfloat16 cache; got {cache.dtype}")
+    for t in (q2, kv_new2, cache):
+        if t is not None and not t.is_cuda:
+            raise RuntimeError("amk ops run only on MI355X (HIP) tensors; got a CPU tensor. There is no CPU fallback.")
+    if q2.dtype != cache.dtype or (kv_new2 is not None and kv_new2.dtype != cache.dtype):
+        raise RuntimeError(f"attention_decode: q ({q2.dtype}) and kv_new ({None if kv_new2 is None else kv_new2.dtype}) "
+                           f"must have the cache's dtype ({cache.dtype})")
+    b16 = cache.dtype == torch.bfloat16
     H, D = int(num_heads), int(dim_head)
     B, capacity = cache.shape[0], cache.shape[1]
-    if q2.numel() != B * H * D or cache.shape[2] != 2 * H * D or not cache.is_contiguous():
+    hd = H * D
+    if tuple(q2.shape) != (B, 1, hd) or cache.dim() != 3 or cache.shape[2] != 2 * hd or not cache.is_contiguous():
         raise RuntimeError(f"attention_decode: q {tuple(q2.shape)} / cache {tuple(cache.shape)} do not fit "
-                           f"B={B}, heads={H}, dim_head={D} (cache: contiguous (B, capacity, 2*h*d))")
-    if kv_new2 is not None and kv_new2.numel() != B * 2 * H * D:
+                           f"B={B}, heads={H}, dim_head={D} (q (B, 1, h*d); cache: contiguous (B, capacity, 2*h*d))")
+    if kv_new2 is not None and tuple(kv_new2.shape) != (B, 1, 2 * hd):
         raise RuntimeError(f"attention_decode: kv_new {tuple(kv_new2.shape)} is not one (kv h d) row per batch")
     if n_dev is not None and (n_dev.dtype != torch.int32 or not n_dev.is_cuda or n_dev.numel() != 1):
         raise RuntimeError("attention_decode: n_dev must be a one-element int32 device tensor")
     if kv_new2 is not None and n_dev is None:
         raise RuntimeError("attention_decode: append mode needs n_dev")
-    if not q2.is_contiguous() or (kv_new2 is not None and not kv_new2.is_contiguous()):
-        raise RuntimeError("attention_decode consumes q and kv_new in place: they must be contiguous")
-    q2c, kvn = q2, kv_new2
+    unit = 8 if b16 else 4
+    for t, what in ((q2, "q"), (kv_new2, "kv_new")):
+        if t is not None and (t.stride(2) != 1 or (B > 1 and t.stride(0) % unit) or t.data_ptr() % 16):
+            raise RuntimeError(f"attention_decode consumes {what} in place: unit last stride, a row stride that is a multiple "
+                               f"of {unit} elements and a 16-byte aligned start (a contiguous tensor or a column slice of one)")
     km = _mask_u8(key_mask, (B, capacity), "key_mask")
     L = _lib.load()
-    o = torch.empty(q2.shape, device=q2.device, dtype=torch.float32)
+    o = torch.empty((B, 1, hd), device=q2.device, dtype=cache.dtype)
     need = L.amk_attn_decode_ws_floats(B, H, D, capacity)
     if ws is None:
         ws = torch.empty((need,), device=q2.device, dtype=torch.float32)
     elif ws.dtype != torch.float32 or not ws.is_cuda or not ws.is_contiguous() or ws.numel() < need:
         raise RuntimeError(f"attention_decode: ws must be a contiguous float32 device tensor of at least {need} elements")
-    hd = H * D
+    esz = 2 if b16 else 4
+    q_sb = q2.stride(0) if B > 1 else hd
+    n_sb = (kv_new2.stride(0) if B > 1 else 2 * hd) if kv_new2 is not None else 2 * hd
+    fn, name = (L.amk_attn_decode_bf16, "amk_attn_decode_bf16") if b16 else (L.amk_attn_decode, "amk_attn_decode")
     with _timed("attn_decode"):
-        rc = L.amk_attn_decode(_ptr(q2c), _ptr(kvn), ctypes.c_void_p(kvn.data_ptr() + 4 * hd) if kvn is not None else _NULL,
-                               _ptr(cache), ctypes.c_void_p(cache.data_ptr() + 4 * hd), _ptr(o), _ptr(ws), _ptr(n_dev), _ptr(km),
-                               B, H, D, capacity, hd, D, 2 * hd, D, capacity * 2 * hd, 2 * hd, D, hd, D,
-                               float(scale), _stream())
-    _lib.check(rc, "amk_attn_decode")
+        rc = fn(_ptr(q2), _ptr(kv_new2), ctypes.c_void_p(kv_new2.data_ptr() + esz * hd) if kv_new2 is not None else _NULL,
+                _ptr(cache), ctypes.c_void_p(cache.data_ptr() + esz * hd), _ptr(o), _ptr(ws), _ptr(n_dev), _ptr(km),
+                B, H, D, capacity, q_sb, D, n_sb, D, capacity * 2 * hd, 2 * hd, D, hd, D,
+                float(scale), _stream())
+    _lib.check(rc, name)
     return o
 
 
 def attention_decode_ws_floats(B, num_heads, dim_head, capacity):
     """Elements of the float32 workspace attention_decode needs at these sizes (amk_attn_decode_ws_floats)."""
     return int(_lib.load().amk_attn_decode_ws_floats(int(B), int(num_heads), int(dim_head), int(capacity)))
+
+
+# AMK_DECODE_BF16 (default 1): under bf16 autocast Decoder.init_state builds a bf16 decode state -- bf16 caches, the state's
+# own bf16 weight copies, the step on amk_attn_decode_bf16 and amk_gemm_rows_bf16 (models/transformer.py).  0: the decode
+# refuses to run under autocast, as it did before that path existed.  Read once per process.
+DECODE_BF16 = os.environ.get("AMK_DECODE_BF16", "1") != "0"
+DECODE_AUTOCAST_REFUSAL = ("attention_decode runs on f32 tensors outside autocast; a bf16 cache is not implemented "
+                           "with AMK_DECODE_BF16=0 (an f32 decode state does not run under autocast)")
+
+
+def empty_w16(rows, k, device):
+    """A zeroed bf16 (rows, k) matrix whose row stride is a multiple of 8 elements, as the row GEMM takes it."""
+    return torch.zeros((rows, (k + 7) // 8 * 8), device=device, dtype=torch.bfloat16)[:, :k]
+
+
+def fill_w16(dst, param):
+    """dst (bf16, in place) <- the parameter: its bf16 shadow where FlatAdam(bf16_shadow=True) keeps one current, else
+    the f32 master rounded to nearest even."""
+    shadow = getattr(param, "_amk_bf16", None)
+    current = shadow is not None and param._version == param._amk_bf16_version
+    dst.copy_(shadow if current else param.detach())
+
+
+def layer_norm_to_bf16(x, res, gamma, beta, eps=1e-5):
+    """(h, y): h = x + res in f32 (x itself with res None), y = LayerNorm(h) written in bf16 (amk_add_layernorm_mixed_fwd);
+    x f32 or bf16, res f32 or None.  For callers that have autocast disabled and feed y to bf16 products."""
+    if not _ln_supported(x.shape[-1]):
+        raise RuntimeError(f"layer_norm_to_bf16: width {x.shape[-1]} not supported (a multiple of 4 up to 4096)")
+    return _AddLayerNormMixed.apply(x, res, gamma, beta, eps)
+
+
+# rows up to which linear_rows takes the row GEMM; above it the library's bf16 GEMM (F.linear) on the same operands
+ROWS_GEMM_MAX_M = 64
+
+
+def linear_rows_bf16(x16, w16, bias32=None, out_dtype=torch.bfloat16):
+    """x16 (M, K) . w16 (N, K)^T + bias32 on amk_gemm_rows_bf16 (csrc/gemm_rows_bf16.hip): bf16 operands with unit column
+    stride and row strides that are multiples of 8, an f32 bias added in f32, f32 accumulation; out_dtype float32, or
+    bfloat16 rounded once.  Built for M of a decode batch: row m of the result is bitwise independent of M.  Inference
+    only, no autograd."""
+    if x16.dtype != torch.bfloat16 or w16.dtype != torch.bfloat16 or x16.dim() != 2 or w16.dim() != 2:
+        raise RuntimeError(f"linear_rows_bf16 takes bf16 matrices; got {x16.dtype} {tuple(x16.shape)}, {w16.dtype} {tuple(w16.shape)}")
+    if not x16.is_cuda or not w16.is_cuda:
+        raise RuntimeError("amk ops run only on MI355X (HIP) tensors; got a CPU tensor. There is no CPU fallback.")
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError(f"linear_rows_bf16 writes float32 or bfloat16, not {out_dtype}")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x16, w16, bias32)):
+        raise RuntimeError("linear_rows_bf16 is inference only: it has no backward; call it under torch.no_grad()")
+    M, K = x16.shape
+    N = w16.shape[0]
+    if w16.shape[1] != K or (bias32 is not None and (bias32.dtype != torch.float32 or tuple(bias32.shape) != (N,)
+                                                     or not bias32.is_contiguous())):
+        raise RuntimeError(f"linear_rows_bf16: x {tuple(x16.shape)}, w {tuple(w16.shape)} and an f32 bias (N,) do not fit")
+    if x16.stride(1) != 1 or (M > 1 and x16.stride(0) % 8) or x16.data_ptr() % 16:
+        x16 = _rows_padded(x16)
+    if w16.stride(1) != 1 or (N > 1 and w16.stride(0) % 8) or w16.data_ptr() % 16:
+        w16 = _rows_padded(w16)
+    ldx = x16.stride(0) if M > 1 else (K + 7) // 8 * 8
+    ldw = w16.stride(0) if N > 1 else (K + 7) // 8 * 8
+    ldy = (N + 3) // 4 * 4
+    y = torch.empty((M, ldy), device=x16.device, dtype=out_dtype)
+    with _timed(f"gemm_rows_bf16 N{N} K{K}"):
+        rc = _lib.load().amk_gemm_rows_bf16(_ptr(x16), ldx, _ptr(w16), ldw, _ptr(bias32), _ptr(y), ldy, M, N, K,
+                                            1 if out_dtype == torch.bfloat16 else 0, _stream())
+    _lib.check(rc, "amk_gemm_rows_bf16")
+    return y if ldy == N else y[:, :N]
+
+
+def _rows_padded(t):
+    """A copy of a bf16 matrix with its rows at a stride that is a multiple of 8 elements (a view of the padded buffer)."""
+    r, k = t.shape
+    buf = torch.zeros((r, (k + 7) // 8 * 8), device=t.device, dtype=t.dtype)
+    buf[:, :k].copy_(t)
+    return buf[:, :k]
+
+
+def linear_rows(x16, w16, bias32=None, out_dtype=torch.bfloat16, w32=None):
+    """The decode step's Linear on bf16 weights: the row GEMM up to ROWS_GEMM_MAX_M rows, above it F.linear on the same
+    bf16 operands (with an f32 result -- the head -- on the f32 master w32)."""
+    if x16.shape[0] <= ROWS_GEMM_MAX_M:
+        return linear_rows_bf16(x16, w16, bias32, out_dtype)
+    if out_dtype == torch.float32 and w32 is not None:
+        return torch.nn.functional.linear(x16.float(), w32, bias32)
+    y = torch.nn.functional.linear(x16, w16, None if bias32 is None else bias32.to(torch.bfloat16))
+    return y if out_dtype == torch.bfloat16 else y.float()
 
 
 # ---------------------------------------------------------------------------- VQ lookup

@@ -173,6 +173,39 @@ int amk_attn_decode(const float* q, const float* k_new, const float* v_new, floa
                     int64_t c_sb, int64_t c_st, int64_t c_sh, int64_t o_sb, int64_t o_sh,
                     float scale, void* stream);
 
+/* amk_attn_decode on a bf16 cache, for the decode under bf16 autocast (csrc/attn_decode.hip; replaces the same lines,
+ * models/softmax_attention.py:62-76 for one new row inside the loop of models/parti.py:135-152, under torch.autocast).
+ * The contract above holds word for word -- append and read mode, n_dev on the device, key_mask, out-of-range n, the
+ * two launches, no atomics, bitwise reproducible and independent of B -- with these differences:
+ *   q, k_new, v_new, k_cache, v_cache and o are bf16.  Every stride is in elements and a multiple of 8; the pointers
+ *   are 16-byte aligned.  ws is the same f32 workspace, amk_attn_decode_ws_floats(B, H, D, capacity) floats.
+ *   bf16 -> f32 is exact; q is scaled in f32 after the conversion; scores, maxima, exp2, l and o stay f32 and p is never
+ *   rounded to bf16.  o is rounded ONCE, to nearest even, on its final store.  Append mode writes cache row n as the bits
+ *   of k_new / v_new.
+ * (Added within 0.4.0, same library version: an addition only.) */
+int amk_attn_decode_bf16(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache,
+                         void* o, float* ws, const int32_t* n_dev, const uint8_t* key_mask,
+                         int B, int H, int D, int capacity,
+                         int64_t q_sb, int64_t q_sh, int64_t new_sb, int64_t new_sh,
+                         int64_t c_sb, int64_t c_st, int64_t c_sh, int64_t o_sb, int64_t o_sh,
+                         float scale, void* stream);
+
+/* A few rows times a weight matrix on bf16 MFMA (csrc/gemm_rows_bf16.hip):  y (M, N) = x (M, K) . w (N, K)^T + bias.
+ * Replaces nn.Linear under torch.autocast where M is the batch of a decode step: the projections of
+ * models/softmax_attention.py:30-44 and :78-81, the two Linear layers of models/transformer.py:22-43 and the logits of
+ * models/parti.py:146, each for ONE new row per sequence.
+ *   x (M, K) and w (N, K) bf16, row strides ldx / ldw in elements (multiples of 8, at least K), 16-byte aligned;
+ *   bias (N) f32 or NULL, added in f32; accumulation f32; y f32 (out_bf16 = 0) or bf16 rounded once to nearest even
+ *   (out_bf16 != 0), row stride ldy (a multiple of 4, at least N).
+ * Any M, N, K >= 1.  Tails are predicates: no byte past a row's K elements is read, whatever the padding up to ldx / ldw
+ * holds.  Rows go in blocks of 16 on v_mfma_f32_16x16x32_bf16; one workgroup per (16 columns, 16 rows) whose four waves
+ * split K and add their partial tiles in wave order.  No atomics, nothing split across workgroups: bitwise reproducible,
+ * and row m of y is bitwise independent of M and of the other rows.
+ * AMK_EINVAL: a null x, w or y, a non-positive size, a leading dimension below its row length or off its multiple, a
+ * misaligned pointer.  (Added within 0.4.0, same library version: an addition only.) */
+int amk_gemm_rows_bf16(const void* x, int64_t ldx, const void* w, int64_t ldw, const float* bias,
+                       void* y, int64_t ldy, int M, int N, int K, int out_bf16, void* stream);
+
 /* Backward of amk_attn_fwd (autograd of the same reference lines).
  * Inputs: q,k,v,o,stats as in the forward, d_o (gradient of o, same addressing
  * as o with its own strides).  Outputs: dq (q-like), dk (k-like), dv (v-like),

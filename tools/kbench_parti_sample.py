@@ -15,6 +15,14 @@ time).  Every arm is 50 calls captured into one HIP graph and timed over 20 repl
 time per call, not the host's launch rate; the decode arm reuses one workspace, as DecoderState does.  The
 keys per chunk are a build-time default that AMK_ATTN_DECODE_KEYS = 32 / 64 / 128 overrides, read once per process: run this part once per value to compare split counts (the line printed names the value in force).
     python tools/kbench_parti_sample.py [--part all|model|kernel] [--steps 1024] [--rounds 3] [--batch 8]
+
+``--autocast bf16``: the decode under bf16 autocast against the f32 one (profiles/kbench_parti_sample_bf16.log):
+  model   ``sample(graph=True)`` in f32 (the parent's arm) and under bf16 autocast on a bf16 decode state, on two modules
+          with the same weights, ALTERNATING round by round in one process; the eager bf16 ``sample`` rides along.
+  kernel  amk_attn_decode_bf16 alone at n = 128 / 512 / 1024 against amk_attn_decode on the same values in f32 and
+          against a device copy of the same bf16 bytes, captured-replay timing as above.
+  gemm    amk_gemm_rows_bf16 against F.linear on the same bf16 operands at M = batch for the step's weight shapes,
+          captured-replay timing; a bf16 result, and f32 with the f32 bias for the head.
 """
 import argparse
 import os
@@ -32,7 +40,8 @@ from amk import ops  # noqa: E402
 from amk.models import Parti  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--part", choices=["all", "model", "kernel"], default="all")
+ap.add_argument("--part", choices=["all", "model", "kernel", "gemm"], default="all")
+ap.add_argument("--autocast", choices=["none", "bf16"], default="none")
 ap.add_argument("--steps", type=int, default=1024)
 ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--batch", type=int, default=8)
@@ -46,6 +55,162 @@ B = a.batch
 
 def med_spread(xs):
     return statistics.median(xs), max(xs) - min(xs)
+
+
+def graphed(fn, launches=50):
+    """`launches` calls of fn captured into one HIP graph: a replay is device time, free of the host's launch cost."""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        fn()
+    torch.cuda.current_stream().wait_stream(side)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(launches):
+            fn()
+    return g, launches
+
+
+def timed(graph, replays=20):
+    g, launches = graph
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for _ in range(replays):
+        g.replay()
+    t1.record()
+    torch.cuda.synchronize()
+    return t0.elapsed_time(t1) * 1e3 / (replays * launches)   # us per call
+
+
+def alternate(arms):
+    """{arm: [us per call]} over a.rounds alternating rounds after three warm-up rounds."""
+    with torch.no_grad():
+        graphs = {k: graphed(fn) for k, fn in arms.items()}
+        res = {k: [] for k in arms}
+        for r in range(a.rounds + 3):
+            for k in arms:
+                us = timed(graphs[k])
+                if r >= 3:
+                    res[k].append(us)
+    return res
+
+
+def kernel_part_bf16():
+    keys = os.environ.get("AMK_ATTN_DECODE_KEYS", "64 (default)")
+    cap, H, D = 1024, HEADS, D_HEAD
+    scale = D ** -0.5
+    cache16 = torch.randn(B, cap, 2 * H * D, device=dev).to(torch.bfloat16)
+    q16 = torch.randn(B, 1, H * D, device=dev).to(torch.bfloat16)
+    cache32, q32 = cache16.float(), q16.float()
+    sink = torch.empty_like(cache16)
+    ws = torch.empty(ops.attention_decode_ws_floats(B, H, D, cap), device=dev)
+    print(f"amk_attn_decode_bf16 alone: B {B}, H {H}, D {D}, capacity {cap}, keys per chunk {keys}, read mode; "
+          f"{a.rounds} alternating rounds, spread = max - min")
+    for n in (128, 512, 1024):
+        n_dev = torch.tensor([n], dtype=torch.int32, device=dev)
+        arms = {
+            "decode bf16": lambda: ops.attention_decode(q16, None, cache16, n_dev, H, D, scale, ws=ws),
+            "decode f32": lambda: ops.attention_decode(q32, None, cache32, n_dev, H, D, scale, ws=ws),
+            "copy bf16": lambda: sink[:, :n].copy_(cache16[:, :n]),
+        }
+        with torch.no_grad():
+            err = float((arms["decode bf16"]().float() - arms["decode f32"]()).abs().max())
+        res = alternate(arms)
+        nbytes = B * n * 2 * H * D * 2
+        line = [f"n {n:5d} ({nbytes / 1e6:.1f} MB of bf16 read, max |bf16 - f32 kernel| {err:.1e}):"]
+        med = {}
+        for k in arms:
+            med[k], sp = med_spread(res[k])
+            line.append(f"{k} {med[k]:.1f} us (spread {sp:.1f})")
+        line.append(f"bf16 decode reads at {med['copy bf16'] / med['decode bf16']:.2f} of the copy's rate, "
+                    f"{med['decode f32'] / med['decode bf16']:.2f}x the f32 kernel")
+        print("  " + "; ".join(line))
+
+
+def gemm_part_bf16():
+    inner = int(DIM * 4 * 2 / 3)
+    hd = HEADS * D_HEAD
+    shapes = [("self q|kv", 3 * hd, DIM, False), ("W_o / cross q", DIM, hd, False), ("ffn 1", 2 * inner, DIM, False),
+              ("ffn 2", DIM, inner, False), ("head (f32 out, bias)", V, DIM, True)]
+    print(f"amk_gemm_rows_bf16 against F.linear on bf16, M = {B}; captured-replay us per call, {a.rounds} alternating "
+          f"rounds, spread = max - min")
+    for name, N, K, head in shapes:
+        x = torch.randn(B, K, device=dev).to(torch.bfloat16)
+        w = ops.empty_w16(N, K, dev)
+        w.copy_(torch.randn(N, K, device=dev) * K ** -0.5)
+        bias = torch.randn(N, device=dev) if head else None
+        if K % 8:
+            x = ops._rows_padded(x)   # rows at a stride of 8 elements, as the step hands them over
+        if head:
+            w32, b16 = w.float(), bias.to(torch.bfloat16)
+            arms = {"rows": lambda: ops.linear_rows_bf16(x, w, bias, torch.float32),
+                    "library bf16 + cast": lambda: torch.nn.functional.linear(x, w, b16).float(),
+                    "library f32 master": lambda: torch.nn.functional.linear(x.float(), w32, bias)}
+        else:
+            arms = {"rows": lambda: ops.linear_rows_bf16(x, w), "library bf16": lambda: torch.nn.functional.linear(x, w)}
+        res = alternate(arms)
+        line = [f"{name:>22} N {N:5d} K {K:5d} ({N * K * 2 / 1e6:.2f} MB of W):"]
+        med = {}
+        for k in arms:
+            med[k], sp = med_spread(res[k])
+            line.append(f"{k} {med[k]:.1f} us (spread {sp:.1f})")
+        best = min((v, k) for k, v in med.items() if k != "rows")
+        line.append(f"rows / best library = {med['rows'] / best[0]:.2f}")
+        print("  " + "; ".join(line))
+
+
+def model_part_bf16():
+    import copy
+
+    class StubVQ(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.codebook = types.SimpleNamespace(codebook_size=V)
+            self.num_patches = a.steps
+
+        def decode_indices(self, ids):
+            return ids
+
+    m32 = Parti(DIM, StubVQ(), None, None, L, HEADS, D_HEAD, DEPTH).to(dev).eval()
+    m16 = copy.deepcopy(m32)
+    text = torch.randn(B, L, DIM, device=dev)
+
+    def bf16(fn):
+        def run():
+            with torch.autocast("cuda", dtype=torch.bfloat16):
+                return fn()
+        return run
+
+    arms = {"graph f32": lambda: m32.sample(text, graph=True), "graph bf16": bf16(lambda: m16.sample(text, graph=True)),
+            "eager f32": lambda: m32.sample(text), "eager bf16": bf16(lambda: m16.sample(text))}
+    print(f"Parti sampling, f32 against bf16 autocast: batch {B}, {a.steps} tokens per sample, {V} codes, {a.rounds} "
+          f"alternating rounds after one warm-up round; spread = max - min of the rounds")
+    res = {k: [] for k in arms}
+    for r in range(a.rounds + 1):
+        for k, fn in arms.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            ids = fn()
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            assert tuple(ids.shape) == (B, a.steps)
+            if r:
+                res[k].append(dt)
+    for k in arms:
+        m, sp = med_spread(res[k])
+        print(f"  {k:>10}: median {m:.3f} s, spread {sp:.3f} s; {1e3 * m / a.steps:.3f} ms per token step, "
+              f"{B * a.steps / m:.0f} tokens/s")
+    print(f"  captures: f32 {m32.decode_graph_captures}, bf16 {m16.decode_graph_captures}")
+    ops.KERNEL_EVENTS = {}
+    with torch.autocast("cuda", dtype=torch.bfloat16):
+        state = m16.begin_decode(text)
+        m16.next_logits(state, None)
+        state.set_position(a.steps - 1)
+        m16.next_logits(state, torch.zeros(B, dtype=torch.long, device=dev))
+    torch.cuda.synchronize()
+    for name, (n, ms) in sorted(ops.kernel_event_summary(ops.KERNEL_EVENTS).items()):
+        print(f"  kernel events of the first and the last bf16 step: {name}: {n} launches, {1e3 * ms:.1f} us each")
+    ops.KERNEL_EVENTS = None
 
 
 def kernel_part():
@@ -158,7 +323,15 @@ def model_part():
         ops.KERNEL_EVENTS = None
 
 
-if a.part in ("all", "kernel"):
-    kernel_part()
-if a.part in ("all", "model"):
-    model_part()
+if a.autocast == "bf16":
+    if a.part in ("all", "kernel"):
+        kernel_part_bf16()
+    if a.part in ("all", "gemm"):
+        gemm_part_bf16()
+    if a.part in ("all", "model"):
+        model_part_bf16()
+else:
+    if a.part in ("all", "kernel"):
+        kernel_part()
+    if a.part in ("all", "model"):
+        model_part()

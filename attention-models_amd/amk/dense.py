@@ -193,6 +193,95 @@ def gemm_tn(y, x, *, y2=None, ln=None, want_bias=False, out=None, out2=None, bia
     return dw, dw2, db
 
 
+# ---------------------------------------------------------------------------- split-bf16 products on ready planes
+# (csrc/gemm_x6.hip; the planes are the ones amk.optim.FlatAdam keeps current: nothing is split per call)
+class X6Planes:
+    """The bf16 planes of one weight W (R, K): `w` = [3][NR][K padded to 32] (row order, or the gate order of
+    amk_gemm_x6_nt_swiglu when `gate`), `wt` = the planes of W^T, [3][K][R padded to 32] (None when not kept)."""
+    __slots__ = ("w", "wt", "gate", "R", "K")
+
+    def __init__(self, w, wt, gate, R, K):
+        self.w, self.wt, self.gate, self.R, self.K = w, wt, gate, R, K
+
+
+def _pad32(n):
+    return -(-n // 32) * 32
+
+
+def x6_split_plan(entries, transposed=True):
+    """The table of amk_gemm_x6_split_table for `entries` = [(src offset, R, K, gate)] of one flat f32 buffer:
+    returns (table int64 (n, 8) on the host, number of workgroups, bf16 elements of the plane buffer,
+    [(dst_w, w elements, dst_wt, wt elements)])."""
+    rows, spans, blk, off = [], [], 0, 0
+    for src, R, K, gate in entries:
+        if R % 4 or K % 4 or R <= 0 or K <= 0 or (gate and R % 2):
+            raise RuntimeError(f"x6 planes: a weight of shape {(R, K)} cannot be split (multiples of 4 required)")
+        H = R // 2 if gate else 0
+        NR = _lib.load().amk_gemm_x6_gate_rows(H) if gate else R
+        nw, nt = 3 * NR * _pad32(K), (3 * K * _pad32(R) if transposed else 0)
+        dst_w, dst_wt = off, -1
+        off += -(-nw // 128) * 128   # (every plane set starts on a 256-byte boundary)
+        if transposed:
+            dst_wt = off
+            off += -(-nt // 128) * 128
+        rows.append([src, R, K, H, blk, dst_w, dst_wt, NR])
+        spans.append((dst_w, nw, dst_wt, nt))
+        blk += (_pad32(R) // 32) * (_pad32(K) // 32)
+    return torch.tensor(rows, dtype=torch.int64).view(-1, 8), blk, off, spans
+
+
+def x6_split_table(flat, table_dev, n_blocks, planes):
+    """Run the table-driven split: `flat` the f32 buffer, `planes` the (zero-initialised) bf16 plane buffer."""
+    rc = _lib.load().amk_gemm_x6_split_table(_p(flat), flat.numel(), _p(table_dev), table_dev.shape[0], n_blocks,
+                                             _p(planes), planes.numel(), _stream())
+    _lib.check(rc, "amk_gemm_x6_split_table")
+
+
+def gemm_x6_nt(a, planes, N, bias=None, *, a2=None, planes2=None):
+    """a (M, K) W^T (+ bias) against the planes [3][N][K padded] of W (N, K); with a2 / planes2 the contraction goes on
+    over a second segment (a2 (M, K2) against [3][N][K2 padded]): dX = dq Wq + dkv Wkv in one launch."""
+    a, a2 = _mat(a, "a"), _mat(a2, "a2")
+    M, K = a.shape
+    c = torch.empty((M, N), device=a.device, dtype=torch.float32)
+    L = _lib.load()
+    if a2 is not None:
+        if bias is not None or a2.shape[0] != M:
+            raise RuntimeError("gemm_x6_nt: the two-segment form takes no bias and equal row counts")
+        rc = L.amk_gemm_x6_nt2(_p(a), a.stride(0), _p(planes), K, _p(a2), a2.stride(0), _p(planes2), a2.shape[1],
+                               _p(c), N, M, N, _stream())
+        _lib.check(rc, "amk_gemm_x6_nt2")
+        return c
+    rc = L.amk_gemm_x6_nt(_p(a), a.stride(0), _p(planes), _p(_vec(bias, N, "bias")), _p(c), N, M, N, K, _stream())
+    _lib.check(rc, "amk_gemm_x6_nt")
+    return c
+
+
+def gemm_x6_nt_swiglu(a, gate_planes, H, b12=None, *, keep_ab=True):
+    """(silu(a) * b, (a | b) or None) with (a | b) = a w12^T + b12, w12's planes in the gate order."""
+    a = _mat(a, "a")
+    M, K = a.shape
+    gate = torch.empty((M, H), device=a.device, dtype=torch.float32)
+    ab = torch.empty((M, 2 * H), device=a.device, dtype=torch.float32) if keep_ab else None
+    rc = _lib.load().amk_gemm_x6_nt_swiglu(_p(a), a.stride(0), _p(gate_planes), _p(_vec(b12, 2 * H, "b12")), _p(gate), H,
+                                           _p(ab), 2 * H, M, H, K, _stream())
+    _lib.check(rc, "amk_gemm_x6_nt_swiglu")
+    return gate, ab
+
+
+def gemm_x6_nt_swiglu_bwd(dy, w3t_planes, ab):
+    """(dA | dB) (M, 2H) from dGate = dy (M, K) W3 (K, H) against the planes of W3^T and the forward's (a | b)."""
+    dy, ab = _mat(dy, "dy"), _mat(ab, "ab")
+    M, K = dy.shape
+    H = ab.shape[1] // 2
+    if ab.shape != (M, 2 * H):
+        raise RuntimeError(f"gemm_x6_nt_swiglu_bwd: (a | b) {tuple(ab.shape)} against dy {tuple(dy.shape)}")
+    d_ab = torch.empty((M, 2 * H), device=dy.device, dtype=torch.float32)
+    rc = _lib.load().amk_gemm_x6_nt_swiglu_bwd(_p(dy), dy.stride(0), _p(w3t_planes), _p(ab), ab.stride(0), _p(d_ab), 2 * H,
+                                               M, H, K, _stream())
+    _lib.check(rc, "amk_gemm_x6_nt_swiglu_bwd")
+    return d_ab
+
+
 def _mat16(t, what):
     if not t.is_cuda:
         raise RuntimeError("amk ops run only on MI355X (HIP) tensors; got a CPU tensor. There is no CPU fallback.")

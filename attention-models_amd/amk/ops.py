@@ -1742,8 +1742,22 @@ class _BiasLinear(torch.autograd.Function):
 # Dense GEMMs of the nn.Linear layers: "f32" = the vendor library's exact-f32 kernels (rocBLAS / hipBLASLt, chosen
 # by TunableOp; 0.79 of the f32 MFMA peak) -- the parity mode and the headline; "bf16x6" = csrc/gemm_x6.hip for the
 # forward and the input gradient (split-bf16 products: f32-level error, bound = bf16 MFMA peak / 6); the weight
-# gradient stays with the library.
-GEMM_MODE = os.environ.get("AMK_GEMM", "f32")
+# gradient stays with the library.  "auto" (default) = "f32", except that a Linear, q / kv pair or SwiGLU FFN whose weights
+# carry CURRENT split-bf16 planes (amk.optim.FlatAdam.enable_planes: split once per optimizer step, not per call) runs its
+# forward and input gradient on the fused forms of csrc/gemm_x6.hip (_X6Linear, _X6Linear2, _X6SwiGLUFFN below); a module
+# called outside such a train step has no planes and takes exactly the "f32" paths.
+GEMM_MODE = os.environ.get("AMK_GEMM", "auto")
+if GEMM_MODE not in ("auto", "f32", "bf16x6"):
+    raise RuntimeError(f"AMK_GEMM must be auto, f32 or bf16x6 (got {GEMM_MODE!r})")
+# AMK_X6_LINEAR=0: no plane shadow, no x6 forms under "auto" (the A/B switch; read by VQGANTrainStep and at dispatch)
+X6_LINEAR = os.environ.get("AMK_X6_LINEAR", "1") != "0"
+# the layer kinds "auto" puts on the x6 forms (profiles/x6_linear_step_breakdown.log decides): linear, linear2, ffn
+X6_AUTO_KINDS = frozenset(k for k in os.environ.get("AMK_X6_KINDS", "linear,linear2,ffn").split(",") if k)
+# ... and the products of such a layer that run there: "fwd" = the forward products (always), "dx" = the input gradients
+# too (against the planes of W^T, which are only kept with it).  Default "fwd": back to back every product wins
+# (profiles/kbench_x6_linear.log), but in the step the input gradients' 1.2 ms came with 1.0 ms on the attention backward
+# that runs between them and 0.9 ms on the weight-gradient kernels (profiles/x6_linear_step_breakdown.log).
+X6_AUTO_FORMS = frozenset(k for k in os.environ.get("AMK_X6_FORMS", "fwd").split(",") if k)
 
 
 def gemm_x6_nt(a2, b2, bias=None):
@@ -1806,6 +1820,130 @@ class _LinearX6(torch.autograd.Function):
         if ctx.has_bias and ctx.needs_input_grad[2]:
             db = colsum(dy2)
         return dx, dw, db
+
+
+def _x6_planes(kind, x, *weights, gate=None):
+    """The current planes of every weight (a tuple), when "auto" puts this layer on the x6 forms; else None."""
+    if GEMM_MODE != "auto" or not X6_LINEAR or kind not in X6_AUTO_KINDS or torch.is_autocast_enabled():
+        return None
+    if not x.is_cuda or x.dtype != torch.float32 or x.numel() == 0 or x.shape[-1] % 4:
+        return None
+    if kind == "linear" and min(weights[0].shape) < 128:
+        # a lone Linear under 128 features either way (the quant layers, 256 <-> 32) stays where it was: its weight gradient
+        # would move from the library to dense.gemm_tn, whose tiles are 128 wide (+0.4 ms per step in the kernel trace,
+        # profiles/x6_linear_step_breakdown.log), for a forward of a few microseconds
+        return None
+    out = []
+    for w in weights:
+        pl = getattr(w, "_amk_x6", None)
+        if pl is None or w._version != w._amk_x6_version or pl.gate != (w is gate) or (pl.R, pl.K) != tuple(w.shape):
+            return None   # none kept, or the weight was written in place since (load_state_dict, manual init)
+        out.append(pl)
+    return tuple(out)
+
+
+class _X6Linear(torch.autograd.Function):
+    """_DenseLinear with the forward and dX = dY W on the split-bf16 GEMM against the weight's kept planes (those of W^T
+    for dX); dW and db stay on dense.gemm_tn, exact f32, written into the reducer's buckets."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, pl):
+        from . import dense
+
+        x2 = x.reshape(-1, x.shape[-1])
+        ctx.save_for_backward(x2, weight)
+        ctx.x_shape, ctx.has_bias, ctx.params, ctx.pl = x.shape, bias is not None, (weight, bias), pl
+        return dense.gemm_x6_nt(x2, pl.w, pl.R, bias).view(*x.shape[:-1], pl.R)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        from . import dense
+
+        x2, weight = ctx.saved_tensors
+        dy2 = dy.reshape(-1, dy.shape[-1])
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = (dense.gemm_x6_nt(dy2, ctx.pl.wt, ctx.pl.K) if ctx.pl.wt is not None else _nn_plain(dy2, weight)).view(ctx.x_shape)
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            want_b = ctx.has_bias and ctx.needs_input_grad[2]
+            dw, db = _tn_into(dense.gemm_tn, dy2, x2, ctx.params[0], ctx.params[1] if want_b else None)
+        return dx, dw, db, None
+
+
+class _X6Linear2(torch.autograd.Function):
+    """_DenseLinear2 on the kept planes: (x Wa^T, x Wb^T); dX = dA Wa + dB Wb as one launch over two contraction
+    segments; (dWa, dWb) from dense.gemm_tn as there."""
+
+    @staticmethod
+    def forward(ctx, x, wa, wb, pa, pb):
+        from . import dense
+
+        x2 = x.reshape(-1, x.shape[-1])
+        ctx.save_for_backward(x2, wa, wb)
+        ctx.x_shape, ctx.params, ctx.pl = x.shape, (wa, wb), (pa, pb)
+        a, b = dense.gemm_x6_nt(x2, pa.w, pa.R), dense.gemm_x6_nt(x2, pb.w, pb.R)
+        return a.view(*x.shape[:-1], pa.R), b.view(*x.shape[:-1], pb.R)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, da, db_):
+        from . import dense
+
+        x2, wa, wb = ctx.saved_tensors
+        pa, pb = ctx.pl
+        da2 = da.reshape(-1, da.shape[-1])
+        db2 = db_.reshape(-1, db_.shape[-1])
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = (dense.gemm_x6_nt(da2, pa.wt, pa.K, a2=db2, planes2=pb.wt) if pa.wt is not None and pb.wt is not None
+                  else dense.gemm_nn(da2, wa, a2=db2, w2=wb)).view(ctx.x_shape)
+        dwa = dwb = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            (ar, av), (br, bv) = _claim(ctx.params[0]), _claim(ctx.params[1])
+            dwa, dwb, _ = dense.gemm_tn(da2, x2, y2=db2, out=av, out2=bv)
+            if av is not None:
+                ar.wrote(ctx.params[0])
+                dwa = None
+            if bv is not None:
+                br.wrote(ctx.params[1])
+                dwb = None
+        return dx, dwa, dwb, None, None
+
+
+class _X6SwiGLUFFN(torch.autograd.Function):
+    """_SwiGLUFFN on the kept planes: the gate in the epilogue of the w12 product (w12's planes in the gate order; (a | b)
+    written only when a backward will read it), w3, dGate = dOut W3 with the gate's derivative in its epilogue and
+    dX = d(a | b) W12 on the split-bf16 GEMM; the four weight / bias gradients on dense.gemm_tn as there."""
+
+    @staticmethod
+    def forward(ctx, x, w12, b12, w3, b3, p12, p3):
+        from . import dense
+
+        x2 = x.reshape(-1, x.shape[-1])
+        need = any(ctx.needs_input_grad)
+        gate, ab = dense.gemm_x6_nt_swiglu(x2, p12.w, p12.R // 2, b12, keep_ab=need)
+        out = dense.gemm_x6_nt(gate, p3.w, p3.R, b3)
+        if need:
+            ctx.save_for_backward(x2, w12, w3, ab, gate)
+        ctx.x_shape, ctx.has_bias, ctx.params, ctx.pl = x.shape, (b12 is not None, b3 is not None), (w12, b12, w3, b3), (p12, p3)
+        return out.view(*x.shape[:-1], p3.R)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        from . import dense
+
+        x2, w12, w3, ab, gate = ctx.saved_tensors
+        p12, p3 = ctx.pl
+        d2 = dout.reshape(-1, dout.shape[-1])
+        d_ab = dense.gemm_x6_nt_swiglu_bwd(d2, p3.wt, ab) if p3.wt is not None else dense.gemm_nn(d2, w3, swiglu_ab=ab)
+        dw3, db3 = _tn_into(dense.gemm_tn, d2, gate, ctx.params[2], ctx.params[3] if ctx.has_bias[1] else None)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = (dense.gemm_x6_nt(d_ab, p12.wt, p12.K) if p12.wt is not None else _nn_plain(d_ab, w12)).view(ctx.x_shape)
+        dw12, db12 = _tn_into(dense.gemm_tn, d_ab, x2, ctx.params[0], ctx.params[1] if ctx.has_bias[0] else None)
+        return dx, dw12, db12, dw3, db3, None, None
 
 
 # Dense GEMMs of the nn.Linear layers, default path: csrc/gemm_f32.hip (amk_gemm_f32) -- the forward with the bias in
@@ -2035,6 +2173,9 @@ def linear(x, weight, bias=None):
         return torch.nn.functional.linear(x, weight, bias)
     if GEMM_MODE == "bf16x6" and _x6_ok(x, weight):
         return _LinearX6.apply(x, weight, bias)
+    pl = _x6_planes("linear", x, weight)
+    if pl is not None:
+        return _X6Linear.apply(x, weight, bias, pl[0])
     if _dense_ok(x, weight):
         return _DenseLinear.apply(x, weight, bias)
     if bias is None:
@@ -2044,6 +2185,9 @@ def linear(x, weight, bias=None):
 
 def linear2(x, wa, wb):
     """(F.linear(x, wa), F.linear(x, wb)) -- one launch when the shapes allow (wa.shape[0] a multiple of 128)."""
+    pl = _x6_planes("linear2", x, wa, wb) if wa.shape[0] % 128 == 0 else None
+    if pl is not None:
+        return _X6Linear2.apply(x, wa, wb, *pl)
     if GEMM_MODE != "bf16x6" and _dense_ok(x, wa, wb) and wa.shape[0] % 128 == 0:
         return _DenseLinear2.apply(x, wa, wb)
     return linear(x, wa), linear(x, wb)
@@ -2096,6 +2240,9 @@ def swiglu_ffn(x, w12, b12, w3, b3):
 
             g, _ = dense.gemm_nt_swiglu_bf16(x.to(torch.bfloat16).reshape(-1, x.shape[-1]), _w16(w12), b12, keep_ab=False)
             return torch.nn.functional.linear(g, _w16(w3), _w16(b3)).view(*x.shape[:-1], w3.shape[0])
+    pl = _x6_planes("ffn", x, w12, w3, gate=w12) if not torch.is_autocast_enabled() else None
+    if pl is not None:
+        return _X6SwiGLUFFN.apply(x, w12, b12, w3, b3, *pl)
     if GEMM_MODE != "bf16x6" and _dense_ok(x, w12) and w3.shape[1] % 4 == 0 and w3.shape[0] % 4 == 0 and w3.is_contiguous():
         return _SwiGLUFFN.apply(x, w12, b12, w3, b3)
     ab = linear(x, w12, b12)

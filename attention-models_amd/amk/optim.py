@@ -42,7 +42,9 @@ class FlatAdam:
         bf16_shadow=True: a bf16 copy of every parameter (``p._amk_bf16``, a view of one flat buffer per bucket) is kept
         current by the update kernel itself; the mixed-precision ops (amk.ops.linear / swiglu_ffn under bf16 autocast)
         read it instead of casting the fp32 weight on every call.  Code that writes parameters behind the optimizer's
-        back (load_state_dict, manual init) must call ``refresh_shadow()``."""
+        back (load_state_dict, manual init) must call ``refresh_shadow()``.
+
+        The split-bf16 plane shadow (``enable_planes``) is the same idea for the f32 step: see there."""
         if not reducer.on_gpu:
             raise RuntimeError("FlatAdam runs on MI355X (HIP) parameters only; use torch.optim on CPU")
         self.red = reducer
@@ -57,6 +59,7 @@ class FlatAdam:
         skip = {id(p) for p in no_decay}
         self.wd = np.array([0.0 if id(p) in skip else float(weight_decay) for p in self.params], dtype=np.float64)
         self.flat_p, self.m, self.v, self.seg, self.flat_p16 = [], [], [], [], []
+        self.planes = []   # per bucket (plane buffer, device table, workgroups) or None: see enable_planes
         pid = 0
         for b in reducer.buckets:
             fp = torch.zeros_like(b.flat)
@@ -76,6 +79,7 @@ class FlatAdam:
             self.enable_shadow()
         else:
             self.disable_shadow()   # (copies a deepcopy of a model may have carried over from another optimizer: stale)
+        self.disable_planes()
         self.partials = torch.zeros(len(reducer.buckets) * self.npart, device=dev, dtype=torch.float32)
         self.norm = torch.zeros(1, device=dev, dtype=torch.float32)
         # per-step table {active, lr / bc1, sqrt(bc2), 0} per parameter: pinned host staging, async copy
@@ -107,8 +111,58 @@ class FlatAdam:
             p.__dict__.pop("_amk_bf16_version", None)
         self.flat_p16 = []
 
+    def enable_planes(self, gate=(), transposed=True):
+        """Start keeping the split-bf16 planes of every 2-D parameter (both dimensions multiples of 4) current: the three
+        bf16 planes of W as csrc/gemm_x6.hip reads them (``p._amk_x6.w``; for the parameters in `gate` -- the w12 of a
+        SwiGLU FFN -- in the gate order of amk_gemm_x6_nt_swiglu) and, with `transposed`, those of W^T for the input gradient
+        (``p._amk_x6.wt``, else None), in one flat buffer per bucket allocated here, so the addresses are stable and ``step`` stays
+        capturable.  ``step`` re-splits them with one table-driven launch per bucket after the update; whatever else writes
+        the parameters must call ``refresh_shadow()`` -- until then ``p._version`` differs from ``p._amk_x6_version`` and
+        amk.ops does not use the planes.  Costs 6 bytes per element next to the parameter's 4, 12 with `transposed` (``planes_bytes``)."""
+        from . import dense
+
+        if self.planes and self._planes_t == bool(transposed):
+            return self._split_planes()
+        self.disable_planes()
+        self._planes_t = bool(transposed)
+        gate = {id(p) for p in gate}
+        for b, fp in zip(self.red.buckets, self.flat_p):
+            ent = [(off, p.shape[0], p.shape[1], id(p) in gate, p) for p, off in zip(b.params, b.offsets)
+                   if p.dim() == 2 and p.shape[0] % 4 == 0 and p.shape[1] % 4 == 0]
+            if not ent:
+                self.planes.append(None)
+                continue
+            table, nblk, elems, spans = dense.x6_split_plan([e[:4] for e in ent], transposed=self._planes_t)
+            buf = torch.zeros(elems, device=fp.device, dtype=torch.bfloat16)
+            for (_, R, K, g, p), (dw, nw, dt, nt) in zip(ent, spans):
+                p._amk_x6 = dense.X6Planes(buf[dw:dw + nw], buf[dt:dt + nt] if self._planes_t else None, g, R, K)
+            self.planes.append((buf, table.to(fp.device), nblk, [e[4] for e in ent]))
+        self._split_planes()
+
+    def disable_planes(self):
+        for p in self.params:
+            p.__dict__.pop("_amk_x6", None)
+            p.__dict__.pop("_amk_x6_version", None)
+        self.planes = []
+
+    @property
+    def planes_bytes(self):
+        return sum(pl[0].numel() * 2 for pl in self.planes if pl is not None)
+
+    def _split_planes(self, stamp=True):
+        from . import dense
+
+        for fp, pl in zip(self.flat_p, self.planes):
+            if pl is not None:
+                dense.x6_split_table(fp, pl[1], pl[2], pl[0])
+                if stamp:
+                    for p in pl[3]:
+                        p._amk_x6_version = p._version
+
     def refresh_shadow(self):
-        """Re-derive the bf16 copies from the fp32 parameters (after anything but ``step`` wrote them)."""
+        """Re-derive the bf16 copies and the split-bf16 planes from the fp32 parameters (after anything but ``step``
+        wrote them)."""
+        self._split_planes()
         for fp, f16 in zip(self.flat_p, self.flat_p16):
             f16.copy_(fp)
         if self.flat_p16:
@@ -182,6 +236,7 @@ class FlatAdam:
                 (2 if self.TABLE_WD else 0) | (1 if self.decoupled else 0), _ptr(self.norm) if k == 0 else _ptr(None),
                 _ptr(self.flat_p16[k]) if self.flat_p16 else _ptr(None), stream)
             _lib.check(rc, "amk_adam_flat_step")
+        self._split_planes(stamp=False)   # (the update wrote behind torch's back: the versions stand)
         red.mark_zeroed()
         return self.norm
 

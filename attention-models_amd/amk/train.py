@@ -342,6 +342,7 @@ class VQGANTrainStep:
             self.g_optim = FlatAdam(self.g_red, lr=lr, betas=betas, weight_decay=weight_decay, capturable=capturable,
                                     bf16_shadow=autocast == torch.bfloat16)
             self.d_optim = FlatAdam(self.d_red, lr=lr, betas=betas, weight_decay=weight_decay, capturable=capturable)
+            self._sync_planes()
         elif capturable:
             dev = next(model.parameters()).device
             okw.update(capturable=True)
@@ -364,6 +365,19 @@ class VQGANTrainStep:
         # reference call for call.
         self.share_forward = bool(share_forward)
 
+    def _sync_planes(self):
+        """The f32 step under ops.GEMM_MODE == "auto": the generator's optimizer keeps the split-bf16 planes of its
+        weights current (amk.optim.FlatAdam.enable_planes), and its Linear layers run on them (amk.ops._X6Linear, ...).
+        Any other precision or mode (and AMK_X6_LINEAR=0): no planes, the f32 kernels."""
+        from . import ops
+        from .models.vitvqgan import SwiGLU
+
+        if self._autocast is None and ops.GEMM_MODE == "auto" and ops.X6_LINEAR:
+            self.g_optim.enable_planes(gate=[m.w12.weight for m in self.model.modules() if isinstance(m, SwiGLU)],
+                                       transposed="dx" in ops.X6_AUTO_FORMS)
+        else:
+            self.g_optim.disable_planes()
+
     @property
     def autocast(self):
         return self._autocast
@@ -377,6 +391,7 @@ class VQGANTrainStep:
                 self.g_optim.enable_shadow()
             else:
                 self.g_optim.disable_shadow()
+            self._sync_planes()
 
     def _amp(self):
         import contextlib

@@ -70,54 +70,90 @@ __global__ __launch_bounds__(256) void split_planes_kernel(const float* __restri
   for (int p = 0; p < 3; ++p) *reinterpret_cast<bf16x4*>(planes + ((int64_t)p * R + r) * Kp + k) = pl[p];
 }
 
+enum { X6_PLAIN = 0, X6_GATE = 1, X6_GATE_BWD = 2 };
+
 struct Args {
-  const float *A, *bias;
-  const __bf16* Bp;   // [3][N][Kp]
-  float* C;
-  int M, N, K, Kp;
-  int64_t lda, ldc;
+  const float *A, *A2, *bias, *AB;
+  const __bf16 *Bp, *Bp2;   // [3][NR][Kp] (and [3][NR][Kp2] against A2)
+  float *C, *G;
+  int M, N, K, Kp, K2, Kp2, NR;
+  int64_t lda, lda2, ldc, ldg, ldab;
 };
 
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
+
+// EPI: X6_PLAIN     C = A B^T (+ bias)
+//      X6_GATE      B = w12 in the gate order (plane rows 128 t + j: column 64 t + j of a for j < 64, of b for j >= 64,
+//                   zero rows past H); a tile is 128 rows x 64 gate columns, 8 waves as 4 (m) x 2 (n), and a wave's two
+//                   MFMA tiles are the a and the b columns of the SAME 32 gate columns: the pair meets in one lane.
+//                   G = silu(a) b with the bias added; (a | b) goes to C only when C is given.
+//      X6_GATE_BWD  N = H, the product is dGate; reads (a | b) from AB, writes (dA | dB) to C.
+// TWO: the contraction runs over (A, Bp) and then (A2, Bp2): dX = dq Wq + dkv Wkv in one launch.
+template <int EPI, bool TWO>
 __global__ __launch_bounds__(NTHR, 4) void gemm_x6_nt_kernel(Args g) {
+  constexpr bool GATE = EPI == X6_GATE;
+  constexpr int TN = GATE ? 64 : BN;   // output columns of a tile (its plane rows are always 128)
   __shared__ __attribute__((aligned(16))) __bf16 Ap[3 * PLANE];
   __shared__ __attribute__((aligned(16))) __bf16 Bs[3 * PLANE];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5;
-  const int wm = wave >> 2, wn = wave & 3;  // 2 x 4 waves: rows 64 wm .., columns 32 wn ..
+  // PLAIN: 2 x 4 waves, rows 64 wm .., columns 32 wn ..; GATE: 4 x 2 waves, rows 32 wm .., gate columns 32 wn ..
+  const int wm = GATE ? wave >> 1 : wave >> 2, wn = GATE ? wave & 1 : wave & 3;
   // tiles: consecutive logical ids walk the N tiles of one M tile (they share the A rows): one XCD
-  const int ntn = (g.N + BN - 1) / BN;
+  const int ntn = (g.N + TN - 1) / TN;
   const int wg = xcd_remap(blockIdx.x, gridDim.x);
-  const int m0 = (wg / ntn) * BM, n0 = (wg % ntn) * BN;
+  const int m0 = (wg / ntn) * BM, n0 = (wg % ntn) * TN, p0 = (wg % ntn) * BN;
 
   // A staging: thread -> rows ar + 64 j (j < 2), 4 floats at column ac
   const int ar = tid >> 3, ac = (tid & 7) * 4;
   const __amdgpu_buffer_rsrc_t a_rsrc =
       __builtin_amdgcn_make_buffer_rsrc((void*)g.A, 0, (int)(((int64_t)(g.M - 1) * g.lda + g.K) * 4), 0x00020000);
-  int aoff[2];
+  const __amdgpu_buffer_rsrc_t a2_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)(TWO ? g.A2 : g.A), 0, TWO ? (int)(((int64_t)(g.M - 1) * g.lda2 + g.K2) * 4) : 0, 0x00020000);
+  int aoff[2], aoff2[2];
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int ra = m0 + ar + 64 * j;
     aoff[j] = ra < g.M ? (int)(((int64_t)ra * g.lda + ac) * 4) : 0x7ffffff0;  // past the buffer: zeros
+    aoff2[j] = TWO && ra < g.M ? (int)(((int64_t)ra * g.lda2 + ac) * 4) : 0x7ffffff0;
   }
   // B staging: 3 planes x 128 rows x 4 pieces of 16 B: plane p, row tid / 4, piece tid % 4
   const int br = tid >> 2, bc = (tid & 3) * 8;
   const __amdgpu_buffer_rsrc_t b_rsrc =
-      __builtin_amdgcn_make_buffer_rsrc((void*)g.Bp, 0, (int)((int64_t)3 * g.N * g.Kp * 2), 0x00020000);
-  int boff[3];
+      __builtin_amdgcn_make_buffer_rsrc((void*)g.Bp, 0, (int)((int64_t)3 * g.NR * g.Kp * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t b2_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)(TWO ? g.Bp2 : g.Bp), 0, TWO ? (int)((int64_t)3 * g.NR * g.Kp2 * 2) : 0, 0x00020000);
+  int boff[3], boff2[3];
 #pragma unroll
-  for (int p = 0; p < 3; ++p)
-    boff[p] = n0 + br < g.N ? (int)((((int64_t)p * g.N + n0 + br) * g.Kp + bc) * 2) : 0x7ffffff0;
+  for (int p = 0; p < 3; ++p) {
+    boff[p] = p0 + br < g.NR ? (int)((((int64_t)p * g.NR + p0 + br) * g.Kp + bc) * 2) : 0x7ffffff0;
+    boff2[p] = TWO && p0 + br < g.NR ? (int)((((int64_t)p * g.NR + p0 + br) * g.Kp2 + bc) * 2) : 0x7ffffff0;
+  }
 
+  const int nk1 = (g.K + BK - 1) / BK;
+  const int nk = nk1 + (TWO ? (g.K2 + BK - 1) / BK : 0);
   float4 ast[2];
   uint4 bst[3];
-  auto prefetch = [&](int k0) {
-    const bool kin = k0 + ac < g.K;  // columns past K (the last, partial step) must read zeros, not the next row
+  auto prefetch = [&](int kt) {
+    if (TWO && kt >= nk1) {
+      const int k0 = (kt - nk1) * BK;
+      const bool kin = k0 + ac < g.K2;
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
-      ast[j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, kin ? aoff[j] + k0 * 4 : 0x7ffffff0, 0, 0));
+      for (int j = 0; j < 2; ++j)
+        ast[j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(a2_rsrc, kin ? aoff2[j] + k0 * 4 : 0x7ffffff0, 0, 0));
 #pragma unroll
-    for (int p = 0; p < 3; ++p)
-      bst[p] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(b_rsrc, boff[p] + k0 * 2, 0, 0));  // Kp is padded
+      for (int p = 0; p < 3; ++p)
+        bst[p] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(b2_rsrc, boff2[p] + k0 * 2, 0, 0));
+    } else {
+      const int k0 = kt * BK;
+      const bool kin = k0 + ac < g.K;  // columns past K (the last, partial step) must read zeros, not the next row
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+        ast[j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, kin ? aoff[j] + k0 * 4 : 0x7ffffff0, 0, 0));
+#pragma unroll
+      for (int p = 0; p < 3; ++p)
+        bst[p] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(b_rsrc, boff[p] + k0 * 2, 0, 0));  // Kp is padded
+    }
   };
   auto commit = [&]() {
     __builtin_amdgcn_sched_barrier(0);
@@ -138,45 +174,137 @@ __global__ __launch_bounds__(NTHR, 4) void gemm_x6_nt_kernel(Args g) {
 #pragma unroll
     for (int t = 0; t < 16; ++t) acc[i][t] = 0.f;
 
-  const int nk = (g.K + BK - 1) / BK;
   prefetch(0);
   for (int kt = 0; kt < nk; ++kt) {
     __syncthreads();  // every wave is done with the previous tile's fragments
     commit();
     __syncthreads();
-    prefetch(min(kt + 1, nk - 1) * BK);  // unconditional (the last step re-reads its own tile, unused)
-    __builtin_amdgcn_sched_barrier(0);   // issued HERE, under the MFMAs below (the compiler sinks them otherwise)
+    prefetch(min(kt + 1, nk - 1));      // unconditional (the last step re-reads its own tile, unused)
+    __builtin_amdgcn_sched_barrier(0);  // issued HERE, under the MFMAs below (the compiler sinks them otherwise)
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      bf16x8 a[2][3], b[3];
-#pragma unroll
-      for (int p = 0; p < 3; ++p) {
-        b[p] = *reinterpret_cast<const bf16x8*>(&Bs[p * PLANE + (32 * wn + r) * RS + 16 * s + 8 * h]);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-          a[i][p] = *reinterpret_cast<const bf16x8*>(&Ap[p * PLANE + (64 * wm + 32 * i + r) * RS + 16 * s + 8 * h]);
-      }
       // six partial products per output tile, smallest first; the two tiles' chains interleave
+      constexpr int PA[6] = {1, 2, 0, 1, 0, 0};
+      constexpr int PB[6] = {1, 0, 2, 0, 1, 0};
+      if constexpr (GATE) {
+        bf16x8 a[3], b[2][3];
 #pragma unroll
-      for (int q = 0; q < 6; ++q) {
-        constexpr int PA[6] = {1, 2, 0, 1, 0, 0};
-        constexpr int PB[6] = {1, 0, 2, 0, 1, 0};
+        for (int p = 0; p < 3; ++p) {
+          a[p] = *reinterpret_cast<const bf16x8*>(&Ap[p * PLANE + (32 * wm + r) * RS + 16 * s + 8 * h]);
 #pragma unroll
-        for (int i = 0; i < 2; ++i) acc[i] = mfmab(a[i][PA[q]], b[PB[q]], acc[i]);
+          for (int i = 0; i < 2; ++i)
+            b[i][p] = *reinterpret_cast<const bf16x8*>(&Bs[p * PLANE + (64 * i + 32 * wn + r) * RS + 16 * s + 8 * h]);
+        }
+#pragma unroll
+        for (int q = 0; q < 6; ++q)
+#pragma unroll
+          for (int i = 0; i < 2; ++i) acc[i] = mfmab(a[PA[q]], b[i][PB[q]], acc[i]);
+      } else {
+        bf16x8 a[2][3], b[3];
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+          b[p] = *reinterpret_cast<const bf16x8*>(&Bs[p * PLANE + (32 * wn + r) * RS + 16 * s + 8 * h]);
+#pragma unroll
+          for (int i = 0; i < 2; ++i)
+            a[i][p] = *reinterpret_cast<const bf16x8*>(&Ap[p * PLANE + (64 * wm + 32 * i + r) * RS + 16 * s + 8 * h]);
+        }
+#pragma unroll
+        for (int q = 0; q < 6; ++q)
+#pragma unroll
+          for (int i = 0; i < 2; ++i) acc[i] = mfmab(a[i][PA[q]], b[PB[q]], acc[i]);
       }
     }
   }
-  // epilogue: register t of lane (r, h) is C[m0 + 64 wm + 32 i + acc_row(t, h)][n0 + 32 wn + r]
   const int n = n0 + 32 * wn + r;
-  if (n < g.N) {
-    const float bv = g.bias ? g.bias[n] : 0.f;
+  if (n >= g.N) return;
+  if constexpr (GATE) {
+    // register t of lane (r, h): a (acc[0]) and b (acc[1]) of row m0 + 32 wm + acc_row(t, h), gate column n
+    const float ba = g.bias ? g.bias[n] : 0.f, bb = g.bias ? g.bias[g.N + n] : 0.f;
+#pragma unroll
+    for (int t = 0; t < 16; ++t) {
+      const int m = m0 + 32 * wm + acc_row(t, h);
+      if (m < g.M) {
+        const float av = acc[0][t] + ba, bv = acc[1][t] + bb;
+        g.G[(int64_t)m * g.ldg + n] = av * sigmoidf_(av) * bv;
+        if (g.C) { g.C[(int64_t)m * g.ldc + n] = av; g.C[(int64_t)m * g.ldc + g.N + n] = bv; }
+      }
+    }
+  } else {
+    // register t of lane (r, h) is C[m0 + 64 wm + 32 i + acc_row(t, h)][n0 + 32 wn + r]
+    const float bv = (EPI == X6_PLAIN && g.bias) ? g.bias[n] : 0.f;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int t = 0; t < 16; ++t) {
         const int m = m0 + 64 * wm + 32 * i + acc_row(t, h);
-        if (m < g.M) g.C[(int64_t)m * g.ldc + n] = acc[i][t] + bv;
+        if (m < g.M) {
+          if constexpr (EPI == X6_GATE_BWD) {
+            const float dg = acc[i][t], a_ = g.AB[(int64_t)m * g.ldab + n], b_ = g.AB[(int64_t)m * g.ldab + g.N + n];
+            const float sg = sigmoidf_(a_);
+            g.C[(int64_t)m * g.ldc + n] = dg * b_ * (sg * (1.f + a_ * (1.f - sg)));
+            g.C[(int64_t)m * g.ldc + g.N + n] = dg * (a_ * sg);
+          } else {
+            g.C[(int64_t)m * g.ldc + n] = acc[i][t] + bv;
+          }
+        }
       }
+  }
+}
+
+// ---- the plane shadow: every weight of a flat parameter buffer split in ONE launch, driven by a table.
+// Entry e (SPLIT_ENT int64 each): {src, R, K, H, blk0, dst_w, dst_wt, NR}: W = flat + src is (R, K) row-major;
+// its planes go to planes + dst_w as [3][NR][K padded to 32] -- row r of W at plane row r (H == 0), or in the gate
+// order of X6_GATE (H > 0, R == 2 H) -- and the planes of W^T to planes + dst_wt as [3][K][R padded to 32] (dst_wt
+// < 0: none).  Workgroups blk0 .. of the grid own the 32 x 32 tiles of W, row tiles outermost; the transposed planes
+// go through an LDS tile.  Rows and columns of padding inside a tile are written as zeros; plane rows no tile owns
+// (the gate order's rows past H) are never written: the buffer is allocated zeroed.
+constexpr int SPLIT_ENT = 8;
+
+__global__ __launch_bounds__(256) void split_table_kernel(const float* __restrict__ flat, int64_t flat_elems,
+                                                          const int64_t* __restrict__ table, int n_ent,
+                                                          __bf16* __restrict__ planes, int64_t planes_elems) {
+  __shared__ __bf16 T[3][32][36];
+  const int tid = threadIdx.x;
+  int e = 0;
+  while (e + 1 < n_ent && (int64_t)blockIdx.x >= table[(e + 1) * SPLIT_ENT + 4]) ++e;
+  const int64_t* t = table + e * SPLIT_ENT;
+  const int64_t src = t[0], dst_w = t[5], dst_wt = t[6];
+  const int R = (int)t[1], K = (int)t[2], H = (int)t[3], NR = (int)t[7];
+  const int Kp = (K + 31) / 32 * 32, Rp = (R + 31) / 32 * 32, tk_n = Kp / 32;
+  const int tile = (int)((int64_t)blockIdx.x - t[4]);
+  const int tr = tile / tk_n, tk = tile - tr * tk_n;
+  // a table that does not fit its buffers writes nothing (uniform per workgroup)
+  if (tile < 0 || tr >= Rp / 32 || src < 0 || src + (int64_t)R * K > flat_elems || dst_w < 0 ||
+      dst_w + (int64_t)3 * NR * Kp > planes_elems || (dst_wt >= 0 && dst_wt + (int64_t)3 * K * Rp > planes_elems) ||
+      (H > 0 ? (R != 2 * H || NR < (H + 63) / 64 * 128) : NR < R))
+    return;
+  const int lr = tid >> 3, lc = (tid & 7) * 4;
+  const int rr = 32 * tr + lr, k = 32 * tk + lc;
+  float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (rr < R && k < K) x = *reinterpret_cast<const float4*>(flat + src + (int64_t)rr * K + k);  // K % 4 == 0
+  bf16x4 pl[3];
+  split4(x, pl);
+  if (rr < R) {
+    int pr = rr;
+    if (H > 0) { const int j = rr < H ? rr : rr - H; pr = 128 * (j >> 6) + (j & 63) + (rr < H ? 0 : 64); }
+#pragma unroll
+    for (int p = 0; p < 3; ++p) *reinterpret_cast<bf16x4*>(planes + dst_w + ((int64_t)p * NR + pr) * Kp + k) = pl[p];
+  }
+  if (dst_wt < 0) return;
+#pragma unroll
+  for (int p = 0; p < 3; ++p)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) T[p][lc + j][lr] = pl[p][j];
+  __syncthreads();
+  const int kk = 32 * tk + lr, rc = 32 * tr + lc;   // row kk of W^T, columns rc .. rc + 3
+  if (kk < K) {
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+      bf16x4 v;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = T[p][lr][lc + j];
+      *reinterpret_cast<bf16x4*>(planes + dst_wt + ((int64_t)p * K + kk) * Rp + rc) = v;
+    }
   }
 }
 
@@ -205,21 +333,77 @@ extern "C" int amk_gemm_x6_split(const float* W, int64_t ldw, int N, int K, void
   return AMK_OK;
 }
 
+// One driver for every form: checks as amk_gemm_x6_nt always made them (sizes, 16-byte rows, operands < 2 GiB).
+static int x6_launch(const char* who, int epi, const float* A, int64_t lda, const void* planes, int K, const float* A2,
+                     int64_t lda2, const void* planes2, int K2, const float* bias, const float* AB, int64_t ldab, float* C,
+                     int64_t ldc, float* G, int64_t ldg, int M, int N, void* stream) {
+  const bool two = A2 != nullptr;
+  AMK_CHECK_ARG(A && planes, "%s: null pointer", who);
+  AMK_CHECK_ARG(M > 0 && N > 0 && K > 0 && (!two || (K2 > 0 && planes2)), "%s: non-positive size M=%d N=%d K=%d", who, M, N, K);
+  AMK_CHECK_SUPPORTED(K % 4 == 0 && lda % 4 == 0 && ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(planes)) & 15) == 0,
+                      "%s: K, lda must be multiples of 4 and A, the planes 16-byte aligned", who);
+  const int NR = epi == X6_GATE ? (N + 63) / 64 * 128 : N;
+  AMK_CHECK_SUPPORTED(((int64_t)(M - 1) * lda + K) * 4 < 0x7ffffff0ll && (int64_t)3 * NR * padded_k(K) * 2 < 0x7ffffff0ll,
+                      "%s: an operand must span < 2 GiB", who);
+  if (two) {
+    AMK_CHECK_SUPPORTED(K2 % 4 == 0 && lda2 % 4 == 0 && ((reinterpret_cast<uintptr_t>(A2) | reinterpret_cast<uintptr_t>(planes2)) & 15) == 0,
+                        "%s: K2, lda2 must be multiples of 4 and A2, its planes 16-byte aligned", who);
+    AMK_CHECK_SUPPORTED(((int64_t)(M - 1) * lda2 + K2) * 4 < 0x7ffffff0ll && (int64_t)3 * NR * padded_k(K2) * 2 < 0x7ffffff0ll,
+                        "%s: an operand must span < 2 GiB", who);
+  }
+  Args g;
+  g.A = A; g.A2 = A2; g.bias = bias; g.AB = AB; g.C = C; g.G = G;
+  g.Bp = static_cast<const __bf16*>(planes); g.Bp2 = static_cast<const __bf16*>(planes2);
+  g.M = M; g.N = N; g.K = K; g.Kp = padded_k(K); g.K2 = two ? K2 : 0; g.Kp2 = two ? padded_k(K2) : 0; g.NR = NR;
+  g.lda = lda; g.lda2 = lda2; g.ldc = ldc; g.ldg = ldg; g.ldab = ldab;
+  const int tn = epi == X6_GATE ? 64 : BN;
+  const int64_t nwg = (int64_t)((M + BM - 1) / BM) * ((N + tn - 1) / tn);
+  AMK_CHECK_SUPPORTED(nwg < (1ll << 31), "%s: grid too large", who);
+  const dim3 grid((unsigned)nwg), blk(NTHR);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (epi == X6_GATE) hipLaunchKernelGGL((gemm_x6_nt_kernel<X6_GATE, false>), grid, blk, 0, st, g);
+  else if (epi == X6_GATE_BWD) hipLaunchKernelGGL((gemm_x6_nt_kernel<X6_GATE_BWD, false>), grid, blk, 0, st, g);
+  else if (two) hipLaunchKernelGGL((gemm_x6_nt_kernel<X6_PLAIN, true>), grid, blk, 0, st, g);
+  else hipLaunchKernelGGL((gemm_x6_nt_kernel<X6_PLAIN, false>), grid, blk, 0, st, g);
+  AMK_CHECK_LAUNCH(who);
+  return AMK_OK;
+}
+
 extern "C" int amk_gemm_x6_nt(const float* A, int64_t lda, const void* b_planes, const float* bias,
                               float* C, int64_t ldc, int M, int N, int K, void* stream) {
-  AMK_CHECK_ARG(A && b_planes && C, "amk_gemm_x6_nt: null pointer");
-  AMK_CHECK_ARG(M > 0 && N > 0 && K > 0, "amk_gemm_x6_nt: non-positive size M=%d N=%d K=%d", M, N, K);
-  AMK_CHECK_SUPPORTED(K % 4 == 0 && lda % 4 == 0 &&
-                          ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(b_planes)) & 15) == 0,
-                      "amk_gemm_x6_nt: K, lda must be multiples of 4 and A, the planes 16-byte aligned");
-  AMK_CHECK_SUPPORTED(((int64_t)(M - 1) * lda + K) * 4 < 0x7ffffff0ll && amk_gemm_x6_planes_bytes(N, K) < 0x7ffffff0ll,
-                      "amk_gemm_x6_nt: an operand must span < 2 GiB");
-  Args g;
-  g.A = A; g.Bp = static_cast<const __bf16*>(b_planes); g.bias = bias; g.C = C;
-  g.M = M; g.N = N; g.K = K; g.Kp = padded_k(K); g.lda = lda; g.ldc = ldc;
-  const int64_t nwg = (int64_t)((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-  AMK_CHECK_SUPPORTED(nwg < (1ll << 31), "amk_gemm_x6_nt: grid too large");
-  hipLaunchKernelGGL(gemm_x6_nt_kernel, dim3((unsigned)nwg), dim3(NTHR), 0, static_cast<hipStream_t>(stream), g);
-  AMK_CHECK_LAUNCH("amk_gemm_x6_nt");
+  AMK_CHECK_ARG(C, "amk_gemm_x6_nt: null pointer");
+  return x6_launch("amk_gemm_x6_nt", X6_PLAIN, A, lda, b_planes, K, nullptr, 0, nullptr, 0, bias, nullptr, 0, C, ldc, nullptr, 0, M, N, stream);
+}
+
+extern "C" int amk_gemm_x6_nt2(const float* A, int64_t lda, const void* planes, int K, const float* A2, int64_t lda2,
+                               const void* planes2, int K2, float* C, int64_t ldc, int M, int N, void* stream) {
+  AMK_CHECK_ARG(C && A2 && planes2, "amk_gemm_x6_nt2: null pointer");
+  return x6_launch("amk_gemm_x6_nt2", X6_PLAIN, A, lda, planes, K, A2, lda2, planes2, K2, nullptr, nullptr, 0, C, ldc, nullptr, 0, M, N, stream);
+}
+
+extern "C" int amk_gemm_x6_gate_rows(int H) { return H > 0 ? (H + 63) / 64 * 128 : 0; }
+
+extern "C" int amk_gemm_x6_nt_swiglu(const float* A, int64_t lda, const void* gate_planes, const float* bias, float* gate,
+                                     int64_t ldg, float* ab, int64_t ldab, int M, int H, int K, void* stream) {
+  AMK_CHECK_ARG(gate, "amk_gemm_x6_nt_swiglu: null pointer");
+  return x6_launch("amk_gemm_x6_nt_swiglu", X6_GATE, A, lda, gate_planes, K, nullptr, 0, nullptr, 0, bias, nullptr, 0, ab, ldab, gate, ldg, M, H, stream);
+}
+
+extern "C" int amk_gemm_x6_nt_swiglu_bwd(const float* dY, int64_t ldy, const void* w3t_planes, const float* ab, int64_t ldab,
+                                         float* d_ab, int64_t ldd, int M, int H, int K, void* stream) {
+  AMK_CHECK_ARG(ab && d_ab, "amk_gemm_x6_nt_swiglu_bwd: null pointer");
+  return x6_launch("amk_gemm_x6_nt_swiglu_bwd", X6_GATE_BWD, dY, ldy, w3t_planes, K, nullptr, 0, nullptr, 0, nullptr, ab, ldab, d_ab, ldd, nullptr, 0, M, H, stream);
+}
+
+extern "C" int amk_gemm_x6_split_table(const float* flat, int64_t flat_elems, const void* table, int n_entries, int64_t n_blocks,
+                                       void* planes, int64_t planes_elems, void* stream) {
+  AMK_CHECK_ARG(flat && table && planes, "amk_gemm_x6_split_table: null pointer");
+  AMK_CHECK_ARG(n_entries > 0 && n_blocks > 0 && flat_elems > 0 && planes_elems > 0, "amk_gemm_x6_split_table: non-positive size");
+  AMK_CHECK_SUPPORTED(((reinterpret_cast<uintptr_t>(flat) | reinterpret_cast<uintptr_t>(planes) | reinterpret_cast<uintptr_t>(table)) & 15) == 0,
+                      "amk_gemm_x6_split_table: 16-byte aligned pointers");
+  AMK_CHECK_SUPPORTED(n_blocks < (1ll << 31), "amk_gemm_x6_split_table: grid too large");
+  hipLaunchKernelGGL(split_table_kernel, dim3((unsigned)n_blocks), dim3(256), 0, static_cast<hipStream_t>(stream), flat, flat_elems,
+                     static_cast<const int64_t*>(table), n_entries, static_cast<__bf16*>(planes), planes_elems);
+  AMK_CHECK_LAUNCH("amk_gemm_x6_split_table");
   return AMK_OK;
 }

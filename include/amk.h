@@ -581,6 +581,32 @@ int64_t amk_gemm_x6_planes_bytes(int N, int K);
 int amk_gemm_x6_split(const float* W, int64_t ldw, int N, int K, void* planes, void* stream);
 int amk_gemm_x6_nt(const float* A, int64_t lda, const void* w_planes, const float* bias,
                    float* C, int64_t ldc, int M, int N, int K, void* stream);
+/* The same product on planes that are already there (the plane shadow of amk.optim.FlatAdam), with what the exact-f32
+ * path fuses on the train step's shapes:
+ *   amk_gemm_x6_nt2            C = A W^T + A2 W2^T, one contraction in two segments (dX = dq Wq + dkv Wkv against the planes
+ *                              of Wq^T and Wkv^T, each [3][N][K* padded to 32]).
+ *   amk_gemm_x6_nt_swiglu      (a | b) = A w12^T + bias (w12 (2H, K)); gate = silu(a) * b (M, H); (a | b) (M, 2H) is written
+ *                              only when `ab` is given.  `gate_planes` hold w12 in the GATE ORDER: amk_gemm_x6_gate_rows(H)
+ *                              = 128 ceil(H / 64) rows per plane, plane row 128 t + j = row 64 t + j of w12 for j < 64, row
+ *                              H + 64 t + j - 64 for j >= 64, zero rows where that column is past H.
+ *   amk_gemm_x6_nt_swiglu_bwd  dGate = dY W3 against the planes of W3^T ([3][H][K padded]); reads (a | b), writes (dA | dB).
+ *   amk_gemm_x6_split_table    the split of every weight of one flat parameter buffer in one launch.  `table` (device,
+ *                              n_entries x 8 int64): {src, R, K, H, blk0, dst_w, dst_wt, NR} -- W = flat + src is (R, K)
+ *                              row-major (R, K multiples of 4), its planes go to planes + dst_w (bf16 elements) as
+ *                              [3][NR][K padded] in row order (H = 0, NR >= R) or in the gate order (H > 0, R = 2H), the
+ *                              planes of W^T to planes + dst_wt as [3][K][R padded] (dst_wt < 0: none); the entry owns
+ *                              workgroups blk0 .. blk0 + ceil(R / 32) ceil(K / 32) - 1 of the n_blocks.  `planes` must have
+ *                              been zeroed once (gate-order rows past H are never written); an entry that does not fit
+ *                              flat_elems / planes_elems writes nothing. */
+int amk_gemm_x6_nt2(const float* A, int64_t lda, const void* planes, int K, const float* A2, int64_t lda2,
+                    const void* planes2, int K2, float* C, int64_t ldc, int M, int N, void* stream);
+int amk_gemm_x6_gate_rows(int H);
+int amk_gemm_x6_nt_swiglu(const float* A, int64_t lda, const void* gate_planes, const float* bias, float* gate,
+                          int64_t ldg, float* ab, int64_t ldab, int M, int H, int K, void* stream);
+int amk_gemm_x6_nt_swiglu_bwd(const float* dY, int64_t ldy, const void* w3t_planes, const float* ab, int64_t ldab,
+                              float* d_ab, int64_t ldd, int M, int H, int K, void* stream);
+int amk_gemm_x6_split_table(const float* flat, int64_t flat_elems, const void* table, int n_entries, int64_t n_blocks,
+                            void* planes, int64_t planes_elems, void* stream);
 
 /* --------------------------------------------------------------------------
  * Dense exact-f32 GEMMs with the surrounding element-wise passes folded in.

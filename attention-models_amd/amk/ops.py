@@ -1412,7 +1412,81 @@ class _AgentAttn(torch.autograd.Function):
         return dqkv2, dconv_w, dconv_b, None, None, None, None
 
 
+# Mixed precision: under bf16 autocast the qkv projection hands over bf16 and W_o takes bf16, so the f32 core above sits
+# between an upcast of qkv, a downcast of o and the two casts of their gradients.  csrc/agent.hip instantiates the same
+# kernels on bf16 elements (f32 arithmetic in the f32 path's order, o / dq / dk / dv rounded once on the store; agents,
+# vagent, stats1, the workspaces and the convolution's parameters and gradients stay f32): the same bits as the cast
+# path at half the bytes through the eight tensors, without the four cast kernels.  AMK_AGENT_BF16=0 keeps the cast
+# path.  Read once per process.  Measured by tools/kbench_agent.py --autocast bf16 (profiles/kbench_agent_bf16.log).
+AGENT_BF16 = os.environ.get("AMK_AGENT_BF16", "1") == "1"
+
+
+class _AgentAttnBF16(torch.autograd.Function):
+    """_AgentAttn on bf16 elements: qkv (B,T,3*h*d) bf16 -> o (B,T,h*d) bf16; conv_w / conv_b and their gradients f32."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda")
+    def forward(ctx, qkv2, conv_w, conv_b, H, D, P, scale):
+        B, T, _ = qkv2.shape
+        qkv2 = qkv2.contiguous()
+        qkv = qkv2.view(B, T, 3, H, D)
+        q, k, v = (qkv[:, :, j].permute(0, 2, 1, 3) for j in range(3))
+        dev = qkv2.device
+        o = torch.empty((B, T, H, D), device=dev, dtype=torch.bfloat16).permute(0, 2, 1, 3)
+        agents = torch.empty((B, H, P, D), device=dev, dtype=torch.float32)
+        vagent = torch.empty_like(agents)
+        stats1 = torch.empty((B, H, P, 2), device=dev, dtype=torch.float32)
+        cw, cb = conv_w.contiguous(), conv_b.contiguous()
+        L = _lib.load()
+        ws = torch.empty((max(L.amk_agent_bf16_ws_floats(B, H, T, P, D, 0), 1),), device=dev, dtype=torch.float32)
+        rc = L.amk_agent_attn_bf16_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(cw), _ptr(cb), _ptr(o), _ptr(agents), _ptr(vagent),
+                                       _ptr(stats1), _ptr(ws), B, H, T, D, P, *_strides4(q), *_strides4(k), *_strides4(v),
+                                       *_strides4(o), float(scale), _stream())
+        _lib.check(rc, "amk_agent_attn_bf16_fwd")
+        ctx.save_for_backward(qkv2, cw, agents, vagent, stats1)
+        ctx.cfg = (H, D, P, scale)
+        return o.permute(0, 2, 1, 3).reshape(B, T, H * D)
+
+    @staticmethod
+    @once_differentiable
+    @_amp_bwd
+    def backward(ctx, d_o2):
+        qkv2, cw, agents, vagent, stats1 = ctx.saved_tensors
+        H, D, P, scale = ctx.cfg
+        B, T, _ = qkv2.shape
+        dev = qkv2.device
+        qkv = qkv2.view(B, T, 3, H, D)
+        q, k, v = (qkv[:, :, j].permute(0, 2, 1, 3) for j in range(3))
+        d_o = d_o2.to(torch.bfloat16).contiguous().view(B, T, H, D).permute(0, 2, 1, 3)
+        dqkv2 = torch.empty_like(qkv2)
+        dqkv = dqkv2.view(B, T, 3, H, D)
+        dq, dk, dv = (dqkv[:, :, j].permute(0, 2, 1, 3) for j in range(3))
+        L = _lib.load()
+        cells = B * H * L.amk_agent_num_chunks_dh(T, D)
+        ws = torch.empty((max(L.amk_agent_bf16_ws_floats(B, H, T, P, D, 1), 1),), device=dev, dtype=torch.float32)
+        dw_part = torch.empty((cells, 9, D), device=dev, dtype=torch.float32)
+        db_part = torch.empty((cells, D), device=dev, dtype=torch.float32)
+        rc = L.amk_agent_attn_bf16_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(cw), _ptr(d_o), _ptr(agents), _ptr(vagent), _ptr(stats1),
+                                       _ptr(dq), _ptr(dk), _ptr(dv), _ptr(ws), _ptr(dw_part), _ptr(db_part),
+                                       B, H, T, D, P, *_strides4(q), *_strides4(k), *_strides4(v), *_strides4(d_o),
+                                       *_strides4(dq), *_strides4(dk), *_strides4(dv), float(scale), _stream())
+        _lib.check(rc, "amk_agent_attn_bf16_bwd")
+        dconv_w = torch.empty((D, 1, 3, 3), device=dev, dtype=torch.float32)
+        dconv_b = torch.empty((D,), device=dev, dtype=torch.float32)
+        _lib.check(L.amk_agent_conv_grad_reduce(_ptr(dw_part), _ptr(db_part), cells, D, _ptr(dconv_w), _ptr(dconv_b), _stream()),
+                   "amk_agent_conv_grad_reduce")
+        return dqkv2, dconv_w, dconv_b, None, None, None, None
+
+
+def _agent_bf16_ok(qkv2, conv_w, conv_b, dim_head, pool):
+    return (AGENT_BF16 and _bf16_autocast() and qkv2.is_cuda and qkv2.dtype == torch.bfloat16
+            and conv_w.is_cuda and conv_b.is_cuda and conv_w.dtype == torch.float32 and conv_b.dtype == torch.float32
+            and dim_head in (32, 64, 128) and pool <= 16)
+
+
 def agent_attention(qkv2, conv_w, conv_b, num_heads, dim_head, pool, scale):
+    if _agent_bf16_ok(qkv2, conv_w, conv_b, dim_head, pool):
+        return _AgentAttnBF16.apply(qkv2, conv_w, conv_b, num_heads, dim_head, pool, scale)
     return _AgentAttn.apply(qkv2, conv_w, conv_b, num_heads, dim_head, pool, scale)
 
 

@@ -32,6 +32,14 @@
 // D = 128 halves the chunk so that the staged tile (64 x 132 floats) and a thread's share of a token (32 channels)
 // stay what they are at D = 64: same registers, static LDS under 64 KB, no scratch.  The streaming backward (below)
 // exists for D = 64 only.
+//
+// Two element types.  The kernels that touch q, k, v, o, dO, dq, dk, dv live in agent_kernels.h, which this file includes
+// once with E = float (agent_*_kernel, amk_agent_attn_fwd / _bwd) and once with E = __bf16 (agent_*_bf16_kernel,
+// amk_agent_attn_bf16_fwd / _bwd, for torch.autocast(bfloat16)): there a lane's 4 channels are one 8-byte access, widened
+// exactly on the load and rounded to nearest even once on the store, and everything between is the f32 arithmetic above
+// in the same order, so the bf16 outputs are the f32 outputs rounded once.  dq is written by two kernels (stage-2 part,
+// then the pooled dA / len): its first part crosses in f32 through the workspace (BwdParams::dqf).  The kernels that see
+// only f32 workspaces (agent_s1_combine_kernel, agent_mid_kernel, agent_conv_reduce_kernel) are here and serve both.
 #include "amk_common.h"
 #include <stdlib.h>
 
@@ -60,10 +68,12 @@ struct Cfg {
 
 struct Strides { int64_t sb, st, sh; };
 
+// q, k, v, o, d_o, dq, dk, dv are views of the kernel's element type E (float, or __bf16 under bf16 autocast); strides
+// count elements.  Everything else is f32 on both paths.
 struct Params {
-  const float *q, *k, *v;          // (B,h,T,d) views
+  const void *q, *k, *v;           // (B,h,T,d) views of E
   const float *convw, *convb;      // (d,1,3,3), (d)
-  float* o;                        // (B,h,T,d) view
+  void* o;                         // (B,h,T,d) view of E
   float *agents, *vagent, *stats1; // (B,h,p,d), (B,h,p,d), (B,h,p,2) saved for backward
   float* part;                     // (B,h,NC,p,PSTR) stage-1 partials
   int B, H, T, P, NC;
@@ -72,15 +82,18 @@ struct Params {
 };
 
 struct BwdParams {
-  const float *q, *k, *v, *d_o, *convw;
+  const void *q, *k, *v, *d_o;     // views of E
+  const float *convw;
   const float *agents, *vagent, *stats1;
-  float *dq, *dk, *dv;             // (B,h,T,d) views, fully overwritten
+  void *dq, *dk, *dv;              // (B,h,T,d) views of E, fully overwritten
   float *pva, *pa2, *pa1;          // (B,h,NC,p,d) per-chunk partials: dV_agent, dA (stage 2), dA (stage 1)
   float *dva, *da2, *delta1;       // (B,h,p,d), (B,h,p,d), (B,h,p) folded by the mid kernel
   float *dconvw_part, *dconvb_part;// (B*h*NC, 9, d), (B*h*NC, d) partial sums
   int B, H, T, P, NC;
   Strides qs, ks, vs, dos, dqs, dks, dvs;
   float scale;
+  float* dqf;                      // E = __bf16: contiguous (B,h,T,d) floats, the stage-2 part of dq on its way to the pool
+                                   // backward, which adds the pooled term in f32 and rounds dq once
 };
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
@@ -92,18 +105,51 @@ __device__ __forceinline__ float4 f4(float x) { return make_float4(x, x, x, x); 
 // became eight serial round trips (5.5 us to stage 32 KB; tools/scratch/stamps_agent.py).
 constexpr unsigned PAST = 0x80000000u;
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t slab(const float* base) {
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t slab(const void* base) {
   return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, 0x7ffffffe, 0x00020000);
 }
-__device__ __forceinline__ float4 bld4(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0));
+// The element type E of q, k, v, o, dO, dq, dk, dv: a lane's 4 channels are one b128 (float) or one b64 (__bf16) access.
+// bf16 widens exactly on the load and is rounded to nearest even once, on the store; everything in between is the
+// f32 arithmetic of the float build, in the same order.
+__device__ __forceinline__ float4 widen4(u32x2 w) {
+  return make_float4(__builtin_bit_cast(float, w.x << 16), __builtin_bit_cast(float, w.x & 0xffff0000u),
+                     __builtin_bit_cast(float, w.y << 16), __builtin_bit_cast(float, w.y & 0xffff0000u));
 }
+__device__ __forceinline__ unsigned rne16(float x) {   // the bf16 bits of x, round to nearest even (integer arithmetic:
+  const unsigned u = __builtin_bit_cast(unsigned, x);  // independent of the denormal mode); NaN -> the quiet NaN 0x7fc0
+  return (u & 0x7fffffffu) > 0x7f800000u ? 0x7fc0u : (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
+__device__ __forceinline__ u32x2 narrow4(float4 v) {
+  u32x2 w;
+  w.x = rne16(v.x) | (rne16(v.y) << 16); w.y = rne16(v.z) | (rne16(v.w) << 16);
+  return w;
+}
+template <class E>
+__device__ __forceinline__ float4 bld4(__amdgpu_buffer_rsrc_t r, unsigned off) {
+  if constexpr (sizeof(E) == 4) return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0));
+  else return widen4(__builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(r, (int)off, 0, 0)));
+}
+template <class E>
 __device__ __forceinline__ void bst4(__amdgpu_buffer_rsrc_t r, unsigned off, float4 v) {
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (int)off, 0, 0);
+  if constexpr (sizeof(E) == 4) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (int)off, 0, 0);
+  else __builtin_amdgcn_raw_buffer_store_b64(narrow4(v), r, (int)off, 0, 0);
+}
+// 4 channels through a plain pointer (the pooling kernels)
+template <class E>
+__device__ __forceinline__ float4 gld4(const E* p) {
+  if constexpr (sizeof(E) == 4) return *reinterpret_cast<const float4*>(p);
+  else return widen4(*reinterpret_cast<const u32x2*>(p));
+}
+template <class E>
+__device__ __forceinline__ void gst4(E* p, float4 v) {
+  if constexpr (sizeof(E) == 4) *reinterpret_cast<float4*>(p) = v;
+  else *reinterpret_cast<u32x2*>(p) = narrow4(v);
 }
 // byte offset of row t (channels c4..) in a (T, D) view with row stride st, or PAST
+template <class E>
 __device__ __forceinline__ unsigned row_off(int t, int T, int64_t st, int c4) {
-  return (t >= 0 && t < T) ? (unsigned)(((int64_t)t * st + c4) * 4) : PAST;
+  return (t >= 0 && t < T) ? (unsigned)(((int64_t)t * st + c4) * (int)sizeof(E)) : PAST;
 }
 __device__ __forceinline__ void fma4(float4& a, float s, const float4& x) {
   a.x += s * x.x; a.y += s * x.y; a.z += s * x.z; a.w += s * x.w;
@@ -122,26 +168,26 @@ __host__ __device__ __forceinline__ int bin_hi(int i, int T, int P) { return (in
 
 // Workgroup-cooperative: rows [t0, t0+CH) of a (T, D) view -> tile[CH][TS]; rows >= T are zero.
 // D / 4 lanes per row (16 per 256-byte row at D = 64), RPP rows per pass: coalesced b128 loads, conflict-free LDS writes.
-template <int D>
-__device__ __forceinline__ void stage_rows(float* tile, const float* base, int64_t st, int t0, int T, int tid) {
+template <int D, class E>
+__device__ __forceinline__ void stage_rows(float* tile, const E* base, int64_t st, int t0, int T, int tid) {
   using C = Cfg<D>;
   const int c4 = (tid & (C::LPR - 1)) * 4;
   const __amdgpu_buffer_rsrc_t rs = slab(base);
   float4 pc[C::NPIECE];
 #pragma unroll
-  for (int j = 0; j < C::NPIECE; ++j) pc[j] = bld4(rs, row_off(t0 + C::RPP * j + (tid >> C::LPR_LOG), T, st, c4));   // all in flight
+  for (int j = 0; j < C::NPIECE; ++j) pc[j] = bld4<E>(rs, row_off<E>(t0 + C::RPP * j + (tid >> C::LPR_LOG), T, st, c4));   // all in flight
 #pragma unroll
   for (int j = 0; j < C::NPIECE; ++j) st4(tile + (C::RPP * j + (tid >> C::LPR_LOG)) * C::TS + c4, pc[j]);
 }
 // the same in two halves: request the pieces (registers), put them into the tile later -- the second tile of a kernel
 // is in flight while the first one is worked on
-template <int D>
-__device__ __forceinline__ void fetch_rows(float4 (&pc)[Cfg<D>::NPIECE], const float* base, int64_t st, int t0, int T, int tid) {
+template <int D, class E>
+__device__ __forceinline__ void fetch_rows(float4 (&pc)[Cfg<D>::NPIECE], const E* base, int64_t st, int t0, int T, int tid) {
   using C = Cfg<D>;
   const int c4 = (tid & (C::LPR - 1)) * 4;
   const __amdgpu_buffer_rsrc_t rs = slab(base);
 #pragma unroll
-  for (int j = 0; j < C::NPIECE; ++j) pc[j] = bld4(rs, row_off(t0 + C::RPP * j + (tid >> C::LPR_LOG), T, st, c4));
+  for (int j = 0; j < C::NPIECE; ++j) pc[j] = bld4<E>(rs, row_off<E>(t0 + C::RPP * j + (tid >> C::LPR_LOG), T, st, c4));
 }
 template <int D>
 __device__ __forceinline__ void put_rows(float* tile, const float4 (&pc)[Cfg<D>::NPIECE], int tid) {
@@ -151,15 +197,15 @@ __device__ __forceinline__ void put_rows(float* tile, const float4 (&pc)[Cfg<D>:
   for (int j = 0; j < C::NPIECE; ++j) st4(tile + (C::RPP * j + (tid >> C::LPR_LOG)) * C::TS + c4, pc[j]);
 }
 // tile[CH][TS] -> rows [t0, min(t0+CH, T)) of a (T, D) view
-template <int D>
-__device__ __forceinline__ void unstage_rows(const float* tile, float* base, int64_t st, int t0, int T, int tid) {
+template <int D, class E>
+__device__ __forceinline__ void unstage_rows(const float* tile, E* base, int64_t st, int t0, int T, int tid) {
   using C = Cfg<D>;
   const int c4 = (tid & (C::LPR - 1)) * 4;
   const __amdgpu_buffer_rsrc_t rs = slab(base);
 #pragma unroll
   for (int r0 = 0; r0 < C::CH; r0 += C::RPP) {
     const int r = r0 + (tid >> C::LPR_LOG);
-    bst4(rs, row_off(t0 + r, T, st, c4), ld4(tile + r * C::TS + c4));
+    bst4<E>(rs, row_off<E>(t0 + r, T, st, c4), ld4(tile + r * C::TS + c4));
   }
 }
 // a value moved inside a row of 16 lanes by a DPP pattern (one VALU modifier; __shfl_xor compiles to ds_bpermute_b32, an
@@ -231,123 +277,7 @@ __device__ __forceinline__ Where where(int H, int NC) {
   return w;
 }
 
-// ---------------------------------------------------------------------------------------
-// forward 0: agent tokens = mean of q over the adaptive bin (AdaptiveAvgPool2d over (t, h), h == p).
-// One workgroup per (b, h, agent); RPP rows per pass.
-template <int D>
-__global__ __launch_bounds__(NT) void agent_pool_kernel(Params p) {
-  using C = Cfg<D>;
-  __shared__ __attribute__((aligned(16))) float red[4 * D];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c4 = (tid & (C::LPR - 1)) * 4;
-  const int i = blockIdx.x % p.P;
-  const int bh = blockIdx.x / p.P;
-  const int h = bh % p.H, b = bh / p.H;
-  const float* qb = p.q + (int64_t)b * p.qs.sb + (int64_t)h * p.qs.sh;
-  const int lo = bin_lo(i, p.T, p.P), hi = bin_hi(i, p.T, p.P);
-  float4 s = f4(0.f);
-  for (int t = lo + (tid >> C::LPR_LOG); t < hi; t += C::RPP) {
-    const float4 x = ld4(qb + (int64_t)t * p.qs.st + c4);
-    s.x += x.x; s.y += x.y; s.z += x.z; s.w += x.w;
-  }
-  s = fold_subs<D>(s);
-  if (lane < C::LPR) st4(&red[wave * D + c4], s);
-  __syncthreads();
-  if (wave == 0)
-    for (int k = 0; k < (D + 63) / 64; ++k) if (const int c = lane + 64 * k; D >= 64 || c < D)
-      p.agents[((int64_t)bh * p.P + i) * D + c] =
-          (red[c] + red[D + c] + red[2 * D + c] + red[3 * D + c]) / (float)(hi - lo);
-}
-
-// forward 1: per-chunk partial of V_agent = softmax((A*scale) K^T) V: chunk max, chunk row sum and
-// the un-normalised sum over the chunk's keys.
-template <int D, int PM>
-__global__ __launch_bounds__(NT) void agent_s1_partial_kernel(Params p) {
-  using C = Cfg<D>;
-  constexpr int CH = C::CH, TS = C::TS, PSTR = C::PSTR;
-  __shared__ __attribute__((aligned(16))) float As[PM * D];
-  __shared__ __attribute__((aligned(16))) float tile[CH * TS];   // k rows, then the cross-wave reduction
-  __shared__ float S[PM * CH];
-  __shared__ float mloc[PM], lloc[PM];
-  float* red = tile;
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const Where w = where<CH>(p.H, p.NC);
-  const int P = p.P, T = p.T, t0 = w.t0;
-  const float* kb = p.k + (int64_t)w.b * p.ks.sb + (int64_t)w.h * p.ks.sh;
-  const float* vb = p.v + (int64_t)w.b * p.vs.sb + (int64_t)w.h * p.vs.sh;
-
-  for (int i = wave; i < P; i += 4)
-    for (int k = 0; k < (D + 63) / 64; ++k) if (const int c = lane + 64 * k; D >= 64 || c < D) As[i * D + c] = p.agents[(w.bh * P + i) * D + c] * p.scale;
-  stage_rows<D>(tile, kb, p.ks.st, t0, T, tid);
-  // the value rows of phase B (D / 4 lanes per row, RPP rows per pass) are requested NOW and arrive under phase A: the
-  // barriers in between order LDS only
-  const int sub = (tid >> C::LPR_LOG), c4 = (tid & (C::LPR - 1)) * 4;
-  float4 vrow[C::NPIECE];
-  {
-    const __amdgpu_buffer_rsrc_t vrs = slab(vb);
-#pragma unroll
-    for (int j = 0; j < C::NPIECE; ++j) vrow[j] = bld4(vrs, row_off(t0 + C::RPP * j + sub, T, p.vs.st, c4));
-  }
-  lds_barrier();
-  {  // phase A: TPT threads per key
-    const int tok = tid >> C::TPT_LOG, half = tid & (C::TPT - 1);
-    float kr[C::TCH];
-    load_half<D>(tile, tok, half, kr);
-#pragma unroll
-    for (int i = 0; i < PM; ++i) {
-      if (i < P) {
-        const float s = dot_half<D>(kr, &As[i * D], half);
-        if (half == 0) S[i * CH + tok] = (t0 + tok < T) ? s : -INFINITY;
-      }
-    }
-  }
-  lds_barrier();
-  for (int i = wave; i < P; i += 4) {  // chunk max per agent: one wave per agent
-    float m = S[i * CH + lane];
-#pragma unroll
-    for (int r = 64; r < CH; r += 64) m = fmaxf(m, S[i * CH + r + lane]);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    if (lane == 0) mloc[i] = m;  // finite: every chunk holds at least one key
-  }
-  lds_barrier();
-  for (int e = tid; e < P * CH; e += NT) S[e] = expf(S[e] - mloc[e / CH]);   // (rows past T: exp(-inf) = 0)
-  lds_barrier();
-  {  // phase B: D / 4 lanes per value row, RPP rows of the chunk per pass
-    float4 acc[PM];
-#pragma unroll
-    for (int i = 0; i < PM; ++i) acc[i] = f4(0.f);
-#pragma unroll
-    for (int j = 0; j < C::NPIECE; ++j) {
-      const int r = C::RPP * j + sub;
-#pragma unroll
-      for (int i = 0; i < PM; ++i)
-        if (i < P) fma4(acc[i], S[i * CH + r], vrow[j]);
-    }
-#pragma unroll
-    for (int i = 0; i < PM; ++i) {
-      if (i < P) {
-        const float4 a = fold_subs<D>(acc[i]);
-        if (lane < C::LPR) st4(&red[(wave * MAXP + i) * D + c4], a);
-      }
-    }
-    for (int i = wave; i < P; i += 4) {  // row sums of this chunk, one wave per agent
-      float s = S[i * CH + lane];
-#pragma unroll
-      for (int r = 64; r < CH; r += 64) s = s + S[i * CH + r + lane];
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
-      if (lane == 0) lloc[i] = s;
-    }
-  }
-  __syncthreads();
-  for (int i = wave; i < P; i += 4) {
-    float* rec = p.part + ((w.bh * p.NC + w.ch) * P + i) * PSTR;
-    for (int k = 0; k < (D + 63) / 64; ++k) if (const int c = lane + 64 * k; D >= 64 || c < D) rec[c] = fold4<D>(red, i, c);
-    if (lane == 0) { rec[D] = mloc[i]; rec[D + 1] = lloc[i]; }
-  }
-}
-
+// (forward 0, 1 and 3 -- pool, s1_partial, s2 -- are in agent_kernels.h; so are backward 0, 2, 3 and the streaming forms)
 // forward 2: fold the chunk partials (fixed chunk order): V_agent and the (max, sum) stats.
 // One workgroup per (b, h), one wave per agent.  The chunk stats sit one per lane (64 chunks per
 // pass) so their loads and exponentials are independent instead of a serial chain.
@@ -415,275 +345,23 @@ __device__ __forceinline__ void load_taps(const float* convw, int c4, float4 (&w
     wq[j] = make_float4(convw[(c4 + 0) * 9 + j], convw[(c4 + 1) * 9 + j], convw[(c4 + 2) * 9 + j], convw[(c4 + 3) * 9 + j]);
 }
 
-// forward 3: O = softmax((q*scale) A^T) V_agent + dwc(v) for one chunk of tokens.
-template <int D, int PM>
-__global__ __launch_bounds__(NT) void agent_s2_kernel(Params p) {
-  using C = Cfg<D>;
-  constexpr int CH = C::CH, TS = C::TS;
-  __shared__ __attribute__((aligned(16))) float As[PM * D];
-  __shared__ __attribute__((aligned(16))) float tile[CH * TS];   // q rows
-  __shared__ float S[PM * CH];
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const Where w = where<CH>(p.H, p.NC);
-  const int P = p.P, T = p.T, t0 = w.t0;
-  const float* qb = p.q + (int64_t)w.b * p.qs.sb + (int64_t)w.h * p.qs.sh;
-
-  for (int i = wave; i < P; i += 4)
-    for (int k = 0; k < (D + 63) / 64; ++k) if (const int c = lane + 64 * k; D >= 64 || c < D) As[i * D + c] = p.agents[(w.bh * P + i) * D + c] * p.scale;
-  stage_rows<D>(tile, qb, p.qs.st, t0, T, tid);
-  // phase B mapping: D / 4 lanes per output row, and a lane group takes CH / RPP CONSECUTIVE rows, so that the 3x3
-  // window of the depthwise convolution slides: three new value rows (heads h-1, h, h+1) per output row instead of
-  // nine.  The first rows of the window are requested now and arrive under phase A (LDS-only barriers in between).
-  constexpr int RPG = C::NPIECE;   // rows per group
-  const int grp = (tid >> C::LPR_LOG), c4 = (tid & (C::LPR - 1)) * 4;
-  const __amdgpu_buffer_rsrc_t vrs = slab(p.v + (int64_t)w.b * p.vs.sb);
-  auto ldv = [&](int a, int t) {   // value row of head h + a - 1 at token t, channels c4..c4+3; zero padding
-    const int h2 = w.h + a - 1;
-    return bld4(vrs, (h2 >= 0 && h2 < p.H && t >= 0 && t < T) ? (unsigned)(((int64_t)h2 * p.vs.sh + (int64_t)t * p.vs.st + c4) * 4) : PAST);
-  };
-  const int tfirst = t0 + RPG * grp;
-  float4 win[3][4];   // [head offset][token slot]: tokens t-1, t, t+1 and the prefetched t+2
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    win[a][0] = ldv(a, tfirst - 1); win[a][1] = ldv(a, tfirst); win[a][2] = ldv(a, tfirst + 1); win[a][3] = ldv(a, tfirst + 2);
-  }
-  lds_barrier();
-  {  // phase A: TPT threads per token: p scores, softmax over the agents
-    const int tok = tid >> C::TPT_LOG, half = tid & (C::TPT - 1);
-    float qr[C::TCH];
-    load_half<D>(tile, tok, half, qr);
-    float sc[PM];
-    float m = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < PM; ++i)
-      if (i < P) { sc[i] = dot_half<D>(qr, &As[i * D], half); m = fmaxf(m, sc[i]); }
-    float l = 0.f;
-#pragma unroll
-    for (int i = 0; i < PM; ++i)
-      if (i < P) { sc[i] = expf(sc[i] - m); l += sc[i]; }
-    if (half == 0) {
-#pragma unroll
-      for (int i = 0; i < PM; ++i)
-        if (i < P) S[i * CH + tok] = sc[i] / l;
-    }
-  }
-  lds_barrier();
-  {  // phase B
-    float4 wq[9], var[PM];
-    load_taps(p.convw, c4, wq);
-    const float4 cb = ld4(p.convb + c4);
-#pragma unroll
-    for (int i = 0; i < PM; ++i) var[i] = (i < P) ? ld4(p.vagent + (w.bh * P + i) * D + c4) : f4(0.f);
-    const __amdgpu_buffer_rsrc_t ors = slab(p.o + (int64_t)w.b * p.os.sb + (int64_t)w.h * p.os.sh);
-#pragma unroll
-    for (int j = 0; j < RPG; ++j) {
-      const int r = RPG * grp + j, t = t0 + r;
-      float4 o = cb;
-#pragma unroll
-      for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) mad4(o, wq[a * 3 + b], win[a][b]);
-#pragma unroll
-      for (int i = 0; i < PM; ++i)
-        if (i < P) fma4(o, S[i * CH + r], var[i]);
-      bst4(ors, row_off(t, T, p.os.st, c4), o);
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        win[a][0] = win[a][1]; win[a][1] = win[a][2]; win[a][2] = win[a][3];
-        win[a][3] = ldv(a, (j + 3 <= RPG) ? t + 3 : -1);   // (row t+3 is the last one the group's window needs)
-      }
-    }
-  }
+// The stage-2 part of dq goes to the float tensor dq itself, or (E = __bf16) in f32 to the contiguous workspace dqf.
+// dq_part: the (T, D) float view of this (b, h); dq_part_st: its row stride.
+template <int D, class E>
+__device__ __forceinline__ float* dq_part(const BwdParams& p, const Where& w) {
+  if constexpr (sizeof(E) == 4) return static_cast<float*>(p.dq) + (int64_t)w.b * p.dqs.sb + (int64_t)w.h * p.dqs.sh;
+  else return p.dqf + w.bh * p.T * D;
 }
-
-// ---------------------------------------------------------------------------------------
-// backward 0: stage-2 backward of one chunk: dq (broadcast part), partials of dV_agent, of dA
-// (broadcast part) and of the conv weight / bias gradients.
-template <int D, int PM>
-__global__ __launch_bounds__(NT) void agent_s2_bwd_kernel(BwdParams p) {
-  using C = Cfg<D>;
-  constexpr int CH = C::CH, TS = C::TS, HALF = C::TCH;
-  __shared__ __attribute__((aligned(16))) float As[PM * D];
-  __shared__ __attribute__((aligned(16))) float Vas[PM * D];
-  __shared__ __attribute__((aligned(16))) float tile[CH * TS];   // q rows, dO rows, dq rows out, reductions
-  __shared__ float S[PM * CH];    // P2 of the chunk
-  __shared__ float DS[PM * CH];   // dS2 of the chunk
-  float* red = tile;
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const Where w = where<CH>(p.H, p.NC);
-  const int P = p.P, T = p.T, t0 = w.t0, h = w.h;
-  const float* qb = p.q + (int64_t)w.b * p.qs.sb + (int64_t)h * p.qs.sh;
-  const float* gb = p.d_o + (int64_t)w.b * p.dos.sb + (int64_t)h * p.dos.sh;
-  float* dqb = p.dq + (int64_t)w.b * p.dqs.sb + (int64_t)h * p.dqs.sh;
-  const float* vbatch = p.v + (int64_t)w.b * p.vs.sb;
-
-  AG_STAMP(0);
-  for (int i = wave; i < P; i += 4) {
-    for (int k = 0; k < (D + 63) / 64; ++k) if (const int c = lane + 64 * k; D >= 64 || c < D) {
-      As[i * D + c] = p.agents[(w.bh * P + i) * D + c];
-      Vas[i * D + c] = p.vagent[(w.bh * P + i) * D + c];
-    }
-  }
-  stage_rows<D>(tile, qb, p.qs.st, t0, T, tid);
-  float4 gpc[C::NPIECE];
-  fetch_rows<D>(gpc, gb, p.dos.st, t0, T, tid);   // the dO tile: in flight while the q tile is worked on
-  // phase B (below): D / 4 lanes per row, a lane group takes CH / RPP CONSECUTIVE rows: the 3x3 window of value rows behind
-  // the convolution's weight gradient slides (three new rows per token instead of nine), rows two tokens ahead in
-  // flight; its first rows are requested here, a whole phase early
-  constexpr int RPG = C::NPIECE;
-  const int grp = (tid >> C::LPR_LOG), c4 = (tid & (C::LPR - 1)) * 4;
-  const __amdgpu_buffer_rsrc_t vrs = slab(vbatch), grs = slab(gb), qrs = slab(qb);
-  auto ldv = [&](int a, int t) {
-    const int h2 = h + a - 1;
-    return bld4(vrs, (h2 >= 0 && h2 < p.H && t >= 0 && t < T) ? (unsigned)(((int64_t)h2 * p.vs.sh + (int64_t)t * p.vs.st + c4) * 4) : PAST);
-  };
-  const int tfirst = t0 + RPG * grp;
-  float4 win[3][4], gq[2][3];   // value window [head offset][t-1, t, t+1, t+2]; dO / q rows [t, t+1, t+2]
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    win[a][0] = ldv(a, tfirst - 1); win[a][1] = ldv(a, tfirst); win[a][2] = ldv(a, tfirst + 1); win[a][3] = ldv(a, tfirst + 2);
-  }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) { gq[0][k] = bld4(grs, row_off(tfirst + k, T, p.dos.st, c4)); gq[1][k] = bld4(qrs, row_off(tfirst + k, T, p.qs.st, c4)); }
-  lds_barrier();
-  AG_STAMP(1);
-  {  // phase A: TPT threads per token
-    const int tok = tid >> C::TPT_LOG, half = tid & (C::TPT - 1);
-    const bool ok = t0 + tok < T;
-    float sc[PM], dp[PM];
-    {
-      float qr[HALF];
-      load_half<D>(tile, tok, half, qr);
-#pragma unroll
-      for (int i = 0; i < PM; ++i)
-        if (i < P) sc[i] = dot_half<D>(qr, &As[i * D], half) * p.scale;
-    }
-    lds_barrier();
-    put_rows<D>(tile, gpc, tid);
-    lds_barrier();
-    AG_STAMP(2);
-    {
-      float gr[HALF];
-      load_half<D>(tile, tok, half, gr);
-#pragma unroll
-      for (int i = 0; i < PM; ++i)
-        if (i < P) dp[i] = dot_half<D>(gr, &Vas[i * D], half);
-    }
-    float m = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < PM; ++i)
-      if (i < P) m = fmaxf(m, sc[i]);
-    float l = 0.f;
-#pragma unroll
-    for (int i = 0; i < PM; ++i)
-      if (i < P) { sc[i] = expf(sc[i] - m); l += sc[i]; }
-    float dl = 0.f;
-#pragma unroll
-    for (int i = 0; i < PM; ++i)
-      if (i < P) { sc[i] /= l; dl += sc[i] * dp[i]; }
-#pragma unroll
-    for (int i = 0; i < PM; ++i) {
-      if (i < P) {
-        const float ds = sc[i] * (dp[i] - dl);
-        if (half == 0) {
-          S[i * CH + tok] = ok ? sc[i] : 0.f;
-          DS[i * CH + tok] = ok ? ds : 0.f;
-        }
-        dp[i] = ds * p.scale;
-      }
-    }
-    // dq_t = scale * sum_i dS2[t,i] A_i: this thread's 32 channels into its own half row of the tile
-    float* dst = tile + tok * TS + HALF * half;
-#pragma unroll
-    for (int j = 0; j < HALF / 4; ++j) {
-      float4 o = f4(0.f);
-#pragma unroll
-      for (int i = 0; i < PM; ++i)
-        if (i < P) fma4(o, dp[i], ld4(&As[i * D + HALF * half + 4 * j]));
-      st4(dst + 4 * j, o);
-    }
-  }
-  __syncthreads();
-  AG_STAMP(3);
-  unstage_rows<D>(tile, dqb, p.dqs.st, t0, T, tid);
-  float4 accva[PM], acca[PM], dw9[9], dbs = f4(0.f);
-#pragma unroll
-  for (int i = 0; i < PM; ++i) { accva[i] = f4(0.f); acca[i] = f4(0.f); }
-#pragma unroll
-  for (int j = 0; j < 9; ++j) dw9[j] = f4(0.f);
-  {
-#pragma unroll 1
-    for (int j = 0; j < RPG; ++j) {
-      const int r = RPG * grp + j, t = t0 + r;
-      const float4 g = gq[0][0], qv = gq[1][0];   // (rows past T: zeros, and S / DS are zero there)
-#pragma unroll
-      for (int i = 0; i < PM; ++i) {
-        if (i < P) {
-          fma4(accva[i], S[i * CH + r], g);
-          fma4(acca[i], DS[i * CH + r], qv);
-        }
-      }
-      dbs.x += g.x; dbs.y += g.y; dbs.z += g.z; dbs.w += g.w;
-#pragma unroll
-      for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int bb = 0; bb < 3; ++bb) mad4(dw9[a * 3 + bb], g, win[a][bb]);
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        win[a][0] = win[a][1]; win[a][1] = win[a][2]; win[a][2] = win[a][3];
-        win[a][3] = ldv(a, (j + 3 <= RPG) ? t + 3 : -1);
-      }
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        gq[k][0] = gq[k][1]; gq[k][1] = gq[k][2];
-        gq[k][2] = bld4(k == 0 ? grs : qrs, (j + 3 < RPG) ? row_off(t + 3, T, k == 0 ? p.dos.st : p.qs.st, c4) : PAST);
-      }
-    }
-  }
-  const int64_t cell = w.bh * p.NC + w.ch;
-  AG_STAMP(4);
-  __syncthreads();  // the dq rows have left the tile
-#pragma unroll
-  for (int i = 0; i < PM; ++i) {
-    if (i < P) {
-      const float4 a = fold_subs<D>(accva[i]);
-      if (lane < C::LPR) st4(&red[(wave * MAXP + i) * D + c4], a);
-    }
-  }
-  __syncthreads();
-  for (int i = wave; i < P; i += 4)
-    for (int k = 0; k < (D + 63) / 64; ++k) if (const int c = lane + 64 * k; D >= 64 || c < D) p.pva[(cell * P + i) * D + c] = fold4<D>(red, i, c);
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < PM; ++i) {
-    if (i < P) {
-      const float4 a = fold_subs<D>(acca[i]);
-      if (lane < C::LPR) st4(&red[(wave * MAXP + i) * D + c4], a);
-    }
-  }
-  __syncthreads();
-  for (int i = wave; i < P; i += 4)
-    for (int k = 0; k < (D + 63) / 64; ++k) if (const int c = lane + 64 * k; D >= 64 || c < D) p.pa2[(cell * P + i) * D + c] = p.scale * fold4<D>(red, i, c);
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < 9; ++j) {
-    const float4 a = fold_subs<D>(dw9[j]);
-    if (lane < C::LPR) st4(&red[(wave * MAXP + j) * D + c4], a);
-  }
-  {
-    const float4 a = fold_subs<D>(dbs);
-    if (lane < C::LPR) st4(&red[(wave * MAXP + 9) * D + c4], a);
-  }
-  __syncthreads();
-  if (wave == 0) {
-    for (int k = 0; k < (D + 63) / 64; ++k) if (const int c = lane + 64 * k; D >= 64 || c < D) {
-      for (int j = 0; j < 9; ++j) p.dconvw_part[(cell * 9 + j) * D + c] = fold4<D>(red, j, c);
-      p.dconvb_part[cell * D + c] = fold4<D>(red, 9, c);
-    }
-  }
-  AG_STAMP(5);
+template <int D, class E>
+__device__ __forceinline__ int64_t dq_part_st(const BwdParams& p) {
+  if constexpr (sizeof(E) == 4) return p.dqs.st;
+  else return D;
+}
+// where the pool backward reads that part of row `row` = (b h) T + t back: from dq itself (dst), or from dqf
+template <int D, class E>
+__device__ __forceinline__ const float* dq_part_row(const BwdParams& p, const E* dst, int64_t row, int c4) {
+  if constexpr (sizeof(E) == 4) return dst;
+  else return p.dqf + row * D + c4;
 }
 
 // backward 1: fold the stage-2 partials in chunk order: dV_agent, dA (stage 2), delta1 = <dV_agent, V_agent>.
@@ -725,148 +403,6 @@ __global__ __launch_bounds__(256) void agent_mid_kernel(BwdParams p) {
   }
 }
 
-// backward 2: stage-1 backward of one chunk: dk, dv (aggregation + transposed conv of dO), partial
-// of dA (aggregation part).
-template <int D, int PM>
-__global__ __launch_bounds__(NT) void agent_s1_bwd_kernel(BwdParams p) {
-  using C = Cfg<D>;
-  constexpr int CH = C::CH, TS = C::TS, HALF = C::TCH;
-  __shared__ __attribute__((aligned(16))) float As[PM * D];
-  __shared__ __attribute__((aligned(16))) float dVas[PM * D];
-  __shared__ __attribute__((aligned(16))) float tile[CH * TS];   // k rows, v rows, dk rows out, reduction
-  __shared__ float S[PM * CH];    // P1 of the chunk
-  __shared__ float DS[PM * CH];   // dS1 of the chunk
-  __shared__ float m1[PM], l1[PM], delta1[PM];
-  float* red = tile;
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const Where w = where<CH>(p.H, p.NC);
-  const int P = p.P, T = p.T, t0 = w.t0, h = w.h;
-  const float* kb = p.k + (int64_t)w.b * p.ks.sb + (int64_t)h * p.ks.sh;
-  const float* vb = p.v + (int64_t)w.b * p.vs.sb + (int64_t)h * p.vs.sh;
-  float* dkb = p.dk + (int64_t)w.b * p.dks.sb + (int64_t)h * p.dks.sh;
-  float* dvb = p.dv + (int64_t)w.b * p.dvs.sb + (int64_t)h * p.dvs.sh;
-  const float* gbatch = p.d_o + (int64_t)w.b * p.dos.sb;
-
-  for (int i = wave; i < P; i += 4) {
-    const int64_t row = w.bh * P + i;
-    for (int k = 0; k < (D + 63) / 64; ++k) if (const int c = lane + 64 * k; D >= 64 || c < D) {
-      As[i * D + c] = p.agents[row * D + c];
-      dVas[i * D + c] = p.dva[row * D + c];
-    }
-    if (lane == 0) { m1[i] = p.stats1[row * 2]; l1[i] = p.stats1[row * 2 + 1]; delta1[i] = p.delta1[row]; }
-  }
-  stage_rows<D>(tile, kb, p.ks.st, t0, T, tid);
-  float4 vpc[C::NPIECE];
-  fetch_rows<D>(vpc, vb, p.vs.st, t0, T, tid);   // the v tile: in flight while the k tile is worked on
-  lds_barrier();
-  {  // phase A: TPT threads per key
-    const int tok = tid >> C::TPT_LOG, half = tid & (C::TPT - 1);
-    const bool ok = t0 + tok < T;
-    float pr[PM], ds[PM];
-    {
-      float kr[HALF];
-      load_half<D>(tile, tok, half, kr);
-#pragma unroll
-      for (int i = 0; i < PM; ++i)
-        if (i < P) pr[i] = expf(dot_half<D>(kr, &As[i * D], half) * p.scale - m1[i]) / l1[i];
-    }
-    lds_barrier();
-    put_rows<D>(tile, vpc, tid);
-    lds_barrier();
-    {
-      float vr[HALF];
-      load_half<D>(tile, tok, half, vr);
-#pragma unroll
-      for (int i = 0; i < PM; ++i) {
-        if (i < P) {
-          const float dp = dot_half<D>(vr, &dVas[i * D], half);
-          const float d = pr[i] * (dp - delta1[i]);
-          if (half == 0) {
-            S[i * CH + tok] = ok ? pr[i] : 0.f;
-            DS[i * CH + tok] = ok ? d : 0.f;
-          }
-          ds[i] = d * p.scale;
-        }
-      }
-    }
-    // dk_t = scale * sum_i dS1[i,t] A_i
-    float* dst = tile + tok * TS + HALF * half;
-#pragma unroll
-    for (int j = 0; j < HALF / 4; ++j) {
-      float4 o = f4(0.f);
-#pragma unroll
-      for (int i = 0; i < PM; ++i)
-        if (i < P) fma4(o, ds[i], ld4(&As[i * D + HALF * half + 4 * j]));
-      st4(dst + 4 * j, o);
-    }
-  }
-  __syncthreads();
-  unstage_rows<D>(tile, dkb, p.dks.st, t0, T, tid);
-  // phase B: D / 4 lanes per row, CH / RPP consecutive rows per lane group: the 3x3 window of dO rows behind the
-  // transposed depthwise convolution slides (three new rows per token instead of nine)
-  constexpr int RPG = C::NPIECE;
-  const int grp = (tid >> C::LPR_LOG), c4 = (tid & (C::LPR - 1)) * 4;
-  float4 acca[PM];
-  {
-    float4 wq[9], dva[PM];
-    load_taps(p.convw, c4, wq);
-#pragma unroll
-    for (int i = 0; i < PM; ++i) { acca[i] = f4(0.f); dva[i] = (i < P) ? ld4(&dVas[i * D + c4]) : f4(0.f); }
-    // dv[h, t] += sum_{a, b} w[a][b] dO[h - (a - 1), t - (b - 1)]: window slot s holds dO[., t - 1 + s] of head h + 1 - a
-    const __amdgpu_buffer_rsrc_t grs = slab(gbatch), krs = slab(kb), dvrs = slab(dvb);
-    auto ldg = [&](int a, int t) {
-      const int h2 = h - (a - 1);
-      return bld4(grs, (h2 >= 0 && h2 < p.H && t >= 0 && t < T) ? (unsigned)(((int64_t)h2 * p.dos.sh + (int64_t)t * p.dos.st + c4) * 4) : PAST);
-    };
-    const int tfirst = t0 + RPG * grp;
-    float4 win[3][4], krow[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      win[a][0] = ldg(a, tfirst - 1); win[a][1] = ldg(a, tfirst); win[a][2] = ldg(a, tfirst + 1); win[a][3] = ldg(a, tfirst + 2);
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) krow[k] = bld4(krs, row_off(tfirst + k, T, p.ks.st, c4));
-#pragma unroll 1
-    for (int j = 0; j < RPG; ++j) {
-      const int r = RPG * grp + j, t = t0 + r;
-      const float4 kv = krow[0];
-      float4 dvv = f4(0.f);
-#pragma unroll
-      for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int bb = 0; bb < 3; ++bb) mad4(dvv, wq[a * 3 + bb], win[a][2 - bb]);   // token t - (bb - 1) = slot 2 - bb
-#pragma unroll
-      for (int i = 0; i < PM; ++i) {
-        if (i < P) {
-          fma4(acca[i], DS[i * CH + r], kv);
-          fma4(dvv, S[i * CH + r], dva[i]);
-        }
-      }
-      bst4(dvrs, row_off(t, T, p.dvs.st, c4), dvv);
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        win[a][0] = win[a][1]; win[a][1] = win[a][2]; win[a][2] = win[a][3];
-        win[a][3] = ldg(a, (j + 3 <= RPG) ? t + 3 : -1);
-      }
-      krow[0] = krow[1]; krow[1] = krow[2];
-      krow[2] = bld4(krs, (j + 3 < RPG) ? row_off(t + 3, T, p.ks.st, c4) : PAST);
-    }
-  }
-  __syncthreads();  // the dk rows have left the tile
-#pragma unroll
-  for (int i = 0; i < PM; ++i) {
-    if (i < P) {
-      const float4 a = fold_subs<D>(acca[i]);
-      if (lane < C::LPR) st4(&red[(wave * MAXP + i) * D + c4], a);
-    }
-  }
-  __syncthreads();
-  const int64_t cell = w.bh * p.NC + w.ch;
-  for (int i = wave; i < P; i += 4)
-    for (int k = 0; k < (D + 63) / 64; ++k) if (const int c = lane + 64 * k; D >= 64 || c < D) p.pa1[(cell * P + i) * D + c] = p.scale * fold4<D>(red, i, c);
-}
-
 // ---------------------------------------------------------------------------------------
 // Streaming forms of the two chunk kernels of the backward (P <= 8 agents per head).  The kernels above stage a
 // chunk's rows in LDS and run two thread mappings over them (2 threads <-> token for the p-wide arithmetic, 16 lanes <->
@@ -889,255 +425,30 @@ __device__ __forceinline__ float fold16(float x) {
   return x;
 }
 
-template <int PM>
-__global__ __launch_bounds__(NT) void agent_s2_bwd_stream_kernel(BwdParams p) {
-  constexpr int D = 64, CH = Cfg<D>::CH;   // streaming forms: head dim 64 only
-  __shared__ __attribute__((aligned(16))) float red[4 * 2 * PM * D];   // [wave][dV_agent | dA][agent][channel]
-  constexpr int RPG = CH / (NT / 16);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, grp = tid >> 4, c4 = (tid & 15) * 4;
-  const Where w = where<CH>(p.H, p.NC);
-  const int P = p.P, T = p.T, h = w.h;
-  const __amdgpu_buffer_rsrc_t qrs = slab(p.q + (int64_t)w.b * p.qs.sb + (int64_t)h * p.qs.sh);
-  const __amdgpu_buffer_rsrc_t grs = slab(p.d_o + (int64_t)w.b * p.dos.sb + (int64_t)h * p.dos.sh);
-  const __amdgpu_buffer_rsrc_t dqrs = slab(p.dq + (int64_t)w.b * p.dqs.sb + (int64_t)h * p.dqs.sh);
-  const int tfirst = w.t0 + RPG * grp;
-  float4 qg[2][4];   // q / dO rows [t, t+1, t+2, t+3]: three rows of requests in flight ahead of the one being worked on
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    qg[0][k] = bld4(qrs, row_off(tfirst + k, T, p.qs.st, c4));
-    qg[1][k] = bld4(grs, row_off(tfirst + k, T, p.dos.st, c4));
-  }
-  float4 A[PM], Va[PM], accva[PM], acca[PM];
-#pragma unroll
-  for (int i = 0; i < PM; ++i) {
-    A[i] = i < P ? ld4(p.agents + (w.bh * P + i) * D + c4) : f4(0.f);
-    Va[i] = i < P ? ld4(p.vagent + (w.bh * P + i) * D + c4) : f4(0.f);
-    accva[i] = f4(0.f); acca[i] = f4(0.f);
-  }
-#pragma unroll 1
-  for (int j = 0; j < RPG; ++j) {
-    const float4 qv = qg[0][0], g = qg[1][0];
-    const bool ok = tfirst + j < T;
-    float sc[PM], dp[PM];
-    float m = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < PM; ++i) {
-      sc[i] = fold16(dot4(qv, A[i])) * p.scale;
-      dp[i] = fold16(dot4(g, Va[i]));
-      if (i < P) m = fmaxf(m, sc[i]);
-    }
-    float l = 0.f;
-#pragma unroll
-    for (int i = 0; i < PM; ++i) { sc[i] = i < P ? expf(sc[i] - m) : 0.f; l += sc[i]; }
-    const float il = ok ? 1.f / l : 0.f;   // (rows past the sequence: P2 = 0, dS2 = 0)
-    float dl = 0.f;
-#pragma unroll
-    for (int i = 0; i < PM; ++i) { sc[i] *= il; dl += sc[i] * dp[i]; }
-    float4 dq = f4(0.f);
-#pragma unroll
-    for (int i = 0; i < PM; ++i) {
-      const float ds = sc[i] * (dp[i] - dl);
-      fma4(dq, ds * p.scale, A[i]);
-      fma4(accva[i], sc[i], g);
-      fma4(acca[i], ds, qv);
-    }
-    bst4(dqrs, row_off(tfirst + j, T, p.dqs.st, c4), dq);
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      qg[k][0] = qg[k][1]; qg[k][1] = qg[k][2]; qg[k][2] = qg[k][3];
-      qg[k][3] = bld4(k == 0 ? qrs : grs, (j + 4 < RPG) ? row_off(tfirst + j + 4, T, k == 0 ? p.qs.st : p.dos.st, c4) : PAST);
-    }
-  }
-  // fold the 16 groups: 4 per wave by DPP, the 4 waves through LDS
-#pragma unroll
-  for (int i = 0; i < PM; ++i) {
-    if (i < P) {
-      const float4 a = fold_subs<D>(accva[i]), b = fold_subs<D>(acca[i]);
-      if (lane < 16) { st4(&red[((wave * 2 + 0) * PM + i) * D + c4], a); st4(&red[((wave * 2 + 1) * PM + i) * D + c4], b); }
-    }
-  }
-  __syncthreads();
-  const int64_t cell = w.bh * p.NC + w.ch;
-  for (int i = wave; i < P; i += 4) {
-    float sva = 0.f, sa = 0.f;
-#pragma unroll
-    for (int ww = 0; ww < 4; ++ww) { sva += red[((ww * 2 + 0) * PM + i) * D + lane]; sa += red[((ww * 2 + 1) * PM + i) * D + lane]; }
-    p.pva[(cell * P + i) * D + lane] = sva;
-    p.pa2[(cell * P + i) * D + lane] = p.scale * sa;
-  }
-}
+constexpr int PB = 64;   // tokens per workgroup of the pool backward
 
-template <int PM>
-__global__ __launch_bounds__(NT) void agent_s1_bwd_stream_kernel(BwdParams p) {
-  constexpr int D = 64, CH = Cfg<D>::CH;
-  __shared__ __attribute__((aligned(16))) float red[4 * (PM + 10) * D];   // [wave][dA (PM) | dconv_w (9) | dconv_b][channel]
-  __shared__ __attribute__((aligned(16))) float wqs[9 * D];                // the convolution's taps [tap][channel]
-  __shared__ __attribute__((aligned(16))) float As[PM * D], dVas[PM * D];  // agents and dV_agent: 48 registers too many next
-                                                                           // to the 36 of the convolution's gradient
-  __shared__ float m1[PM], il1[PM], delta1[PM];
-  constexpr int RPG = CH / (NT / 16);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, grp = tid >> 4, c4 = (tid & 15) * 4;
-  const Where w = where<CH>(p.H, p.NC);
-  const int P = p.P, T = p.T, h = w.h;
-  const __amdgpu_buffer_rsrc_t krs = slab(p.k + (int64_t)w.b * p.ks.sb + (int64_t)h * p.ks.sh);
-  const __amdgpu_buffer_rsrc_t vrs = slab(p.v + (int64_t)w.b * p.vs.sb + (int64_t)h * p.vs.sh);
-  const __amdgpu_buffer_rsrc_t grs = slab(p.d_o + (int64_t)w.b * p.dos.sb);
-  const __amdgpu_buffer_rsrc_t dkrs = slab(p.dk + (int64_t)w.b * p.dks.sb + (int64_t)h * p.dks.sh);
-  const __amdgpu_buffer_rsrc_t dvrs = slab(p.dv + (int64_t)w.b * p.dvs.sb + (int64_t)h * p.dvs.sh);
-  const int tfirst = w.t0 + RPG * grp;
-  // dO rows of head h - (a - 1) at token t (zero padding): the window of the transposed depthwise convolution
-  auto ldg = [&](int a, int t) {
-    const int h2 = h - (a - 1);
-    return bld4(grs, (h2 >= 0 && h2 < p.H && t >= 0 && t < T) ? (unsigned)(((int64_t)h2 * p.dos.sh + (int64_t)t * p.dos.st + c4) * 4) : PAST);
-  };
-  float4 win[3][4], kv[2][3];   // dO window [head offset][t-1, t, t+1, t+2]; k / v rows [t, t+1, t+2]
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    win[a][0] = ldg(a, tfirst - 1); win[a][1] = ldg(a, tfirst); win[a][2] = ldg(a, tfirst + 1); win[a][3] = ldg(a, tfirst + 2);
-  }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) { kv[0][k] = bld4(krs, row_off(tfirst + k, T, p.ks.st, c4)); kv[1][k] = bld4(vrs, row_off(tfirst + k, T, p.vs.st, c4)); }
-  if (tid < 9 * 16) {   // taps: wqs[j][c] = convw[c][j]
-    const int j = tid / 16, cc = (tid & 15) * 4;
-    st4(&wqs[j * D + cc], make_float4(p.convw[(cc + 0) * 9 + j], p.convw[(cc + 1) * 9 + j], p.convw[(cc + 2) * 9 + j], p.convw[(cc + 3) * 9 + j]));
-  }
-  if (tid < P) {
-    const int64_t row = w.bh * P + tid;
-    m1[tid] = p.stats1[row * 2]; il1[tid] = 1.f / p.stats1[row * 2 + 1]; delta1[tid] = p.delta1[row];
-  }
-  for (int i = wave; i < P; i += 4) {
-    As[i * D + lane] = p.agents[(w.bh * P + i) * D + lane];
-    dVas[i * D + lane] = p.dva[(w.bh * P + i) * D + lane];
-  }
-  float4 acca[PM], dw9[9], dbs = f4(0.f);
-#pragma unroll
-  for (int i = 0; i < PM; ++i) acca[i] = f4(0.f);
-#pragma unroll
-  for (int j = 0; j < 9; ++j) dw9[j] = f4(0.f);
-  __syncthreads();
-#pragma unroll 1
-  for (int j = 0; j < RPG; ++j) {
-    const int t = tfirst + j;
-    const float4 kr = kv[0][0], vr = kv[1][0];
-    const bool ok = t < T;
-    float4 dk = f4(0.f), dvv = f4(0.f);
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-      for (int bb = 0; bb < 3; ++bb) {
-        mad4(dvv, ld4(&wqs[(a * 3 + bb) * D + c4]), win[a][2 - bb]);   // dv[h, t] += w[a][b] dO[h - (a-1), t - (b-1)]
-        mad4(dw9[a * 3 + bb], vr, win[a][2 - bb]);                      // (v is zero past the sequence)
-      }
-    dbs.x += win[1][1].x; dbs.y += win[1][1].y; dbs.z += win[1][1].z; dbs.w += win[1][1].w;   // dO[h, t]
-#pragma unroll
-    for (int i = 0; i < PM; ++i) {
-      if (i < P) {
-        const float4 Ai = ld4(&As[i * D + c4]), dVi = ld4(&dVas[i * D + c4]);
-        const float s = fold16(dot4(kr, Ai)), dp = fold16(dot4(vr, dVi));
-        const float pr = ok ? expf(s * p.scale - m1[i]) * il1[i] : 0.f;
-        const float ds = pr * (dp - delta1[i]);
-        fma4(dk, ds * p.scale, Ai);
-        fma4(dvv, pr, dVi);
-        fma4(acca[i], ds, kr);
-      }
-    }
-    bst4(dkrs, row_off(t, T, p.dks.st, c4), dk);
-    bst4(dvrs, row_off(t, T, p.dvs.st, c4), dvv);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      win[a][0] = win[a][1]; win[a][1] = win[a][2]; win[a][2] = win[a][3];
-      win[a][3] = ldg(a, (j + 3 <= RPG) ? t + 3 : -1);
-    }
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      kv[k][0] = kv[k][1]; kv[k][1] = kv[k][2];
-      kv[k][2] = bld4(k == 0 ? krs : vrs, (j + 3 < RPG) ? row_off(t + 3, T, k == 0 ? p.ks.st : p.vs.st, c4) : PAST);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < PM; ++i) {
-    if (i < P) {
-      const float4 a = fold_subs<D>(acca[i]);
-      if (lane < 16) st4(&red[(wave * (PM + 10) + i) * D + c4], a);
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 9; ++j) {
-    const float4 a = fold_subs<D>(dw9[j]);
-    if (lane < 16) st4(&red[(wave * (PM + 10) + PM + j) * D + c4], a);
-  }
-  {
-    const float4 a = fold_subs<D>(dbs);
-    if (lane < 16) st4(&red[(wave * (PM + 10) + PM + 9) * D + c4], a);
-  }
-  __syncthreads();
-  const int64_t cell = w.bh * p.NC + w.ch;
-  auto fold = [&](int slot) {
-    float x = 0.f;
-#pragma unroll
-    for (int ww = 0; ww < 4; ++ww) x += red[(ww * (PM + 10) + slot) * D + lane];
-    return x;
-  };
-  for (int i = wave; i < P; i += 4) p.pa1[(cell * P + i) * D + lane] = p.scale * fold(i);
-  for (int j = wave; j < 10; j += 4) {
-    if (j < 9) p.dconvw_part[(cell * 9 + j) * D + lane] = fold(PM + j);
-    else p.dconvb_part[cell * D + lane] = fold(PM + 9);
-  }
-}
-
-// backward 3: dq[b,h,t,:] += sum over the bins i containing t of dA[b,h,i,:] / len(bin i), with
-// dA = dA(stage 2) + the chunk partials of dA(stage 1) folded in chunk order.  One workgroup per
-// (b, h, 64-token block): dA / len of the bins that meet the block is rebuilt in LDS first.
-constexpr int PB = 64;
-template <int D>
-__global__ __launch_bounds__(NT) void agent_pool_bwd_kernel(BwdParams p) {
-  using C = Cfg<D>;
-  __shared__ __attribute__((aligned(16))) float dA[MAXP * D];
-  __shared__ int lo_s[MAXP], hi_s[MAXP];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int T = p.T, P = p.P;
-  const int nblk = (T + PB - 1) / PB;
-  const int blk = blockIdx.x % nblk;
-  const int64_t bh = blockIdx.x / nblk;
-  const int h = (int)(bh % p.H), b = (int)(bh / p.H);
-  const int t0 = blk * PB, t1 = min(T, t0 + PB);
-  for (int i = wave; i < P; i += 4) {
-    const int lo = bin_lo(i, T, P), hi = bin_hi(i, T, P);
-    if (lane == 0) { lo_s[i] = lo; hi_s[i] = hi; }
-    if (lo < t1 && hi > t0) {
-      for (int k = 0; k < (D + 63) / 64; ++k) if (const int c = lane + 64 * k; D >= 64 || c < D) {
-        float da = p.da2[(bh * P + i) * D + c];
-        for (int ch = 0; ch < p.NC; ++ch) da += p.pa1[(((bh * p.NC + ch) * P) + i) * D + c];
-        dA[i * D + c] = da / (float)(hi - lo);
-      }
-    }
-  }
-  __syncthreads();
-  const int c4 = (tid & (C::LPR - 1)) * 4;
-  float* dqb = p.dq + (int64_t)b * p.dqs.sb + (int64_t)h * p.dqs.sh;
-#pragma unroll
-  for (int r0 = 0; r0 < PB; r0 += C::RPP) {
-    const int t = t0 + r0 + (tid >> C::LPR_LOG);
-    if (t < T) {
-      float4 add = f4(0.f);
-      for (int i = 0; i < P; ++i)
-        if (t >= lo_s[i] && t < hi_s[i]) fma4(add, 1.f, ld4(&dA[i * D + c4]));
-      float* dst = dqb + (int64_t)t * p.dqs.st + c4;
-      const float4 cur = ld4(dst);
-      st4(dst, make_float4(cur.x + add.x, cur.y + add.y, cur.z + add.z, cur.w + add.w));
-    }
-  }
-}
+// every kernel that touches a tensor of E, once per element type (agent_kernels.h)
+#define AGENT_E float
+#define AGENT_KERNEL(n) agent_##n##_kernel
+#include "agent_kernels.h"
+#undef AGENT_E
+#undef AGENT_KERNEL
+#define AGENT_E __bf16
+#define AGENT_KERNEL(n) agent_##n##_bf16_kernel
+#include "agent_kernels.h"
+#undef AGENT_E
+#undef AGENT_KERNEL
 
 }  // namespace amk_agent
 
 using namespace amk_agent;
 
 static bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static bool sok(const Strides& s) { return s.sb % 4 == 0 && s.st % 4 == 0 && s.sh % 4 == 0; }
+// strides count elements: a row of a lane's 4 channels starts on a 16-byte boundary (4 floats, 8 bf16)
+static bool sok(const Strides& s, int64_t m) { return s.sb % m == 0 && s.st % m == 0 && s.sh % m == 0; }
 // the kernels address one batch entry's (h, T, d) slab through a 32-bit byte offset (offsets from 2^31 on mean "past the end")
-static bool span_ok(const Strides& s, int H, int T, int D) {
-  return s.st >= 0 && s.sh >= 0 && ((int64_t)(H - 1) * s.sh + (int64_t)(T - 1) * s.st + D) * 4 < 0x7ffffffell;
+static bool span_ok(const Strides& s, int H, int T, int D, int esz) {
+  return s.st >= 0 && s.sh >= 0 && ((int64_t)(H - 1) * s.sh + (int64_t)(T - 1) * s.st + D) * esz < 0x7ffffffell;
 }
 static bool dh_ok(int Dh) { return Dh == 32 || Dh == 64 || Dh == 128; }
 static int chunk_len(int Dh) { return Dh == 128 ? Cfg<128>::CH : Dh == 32 ? Cfg<32>::CH : Cfg<64>::CH; }
@@ -1149,6 +460,12 @@ static int nchunks(int T, int Dh) { return (T + chunk_len(Dh) - 1) / chunk_len(D
     if ((P_) <= 8) hipLaunchKernelGGL((KERNEL<D, 8>), __VA_ARGS__);          \
     else hipLaunchKernelGGL((KERNEL<D, 16>), __VA_ARGS__);                   \
   } while (0)
+// BF: the __bf16 wrappers (agent_<NAME>_bf16_kernel) instead of the float ones (agent_<NAME>_kernel)
+#define AMK_AGENT_LAUNCH_E(NAME, P_, ...)                                                \
+  do {                                                                                   \
+    if constexpr (BF) AMK_AGENT_LAUNCH(agent_##NAME##_bf16_kernel, P_, __VA_ARGS__);     \
+    else AMK_AGENT_LAUNCH(agent_##NAME##_kernel, P_, __VA_ARGS__);                       \
+  } while (0)
 
 extern "C" int amk_agent_num_chunks(int T) { return T > 0 ? nchunks(T, 64) : 0; }
 extern "C" int amk_agent_num_chunks_dh(int T, int Dh) { return T > 0 && dh_ok(Dh) ? nchunks(T, Dh) : 0; }
@@ -1159,14 +476,52 @@ extern "C" int64_t amk_agent_ws_floats_dh(int B, int H, int T, int P, int Dh, in
   return backward ? 3 * cells * Dh + 2 * rows * Dh + rows : cells * (Dh + 2);
 }
 extern "C" int64_t amk_agent_ws_floats(int B, int H, int T, int P, int backward) { return amk_agent_ws_floats_dh(B, H, T, P, 64, backward); }
+// the bf16 backward keeps the stage-2 part of dq in f32 behind the f32 path's workspace: (B, h, T, d) floats more
+extern "C" int64_t amk_agent_bf16_ws_floats(int B, int H, int T, int P, int Dh, int backward) {
+  const int64_t n = amk_agent_ws_floats_dh(B, H, T, P, Dh, backward);
+  return n && backward ? n + (int64_t)B * H * T * Dh : n;
+}
 
-template <int D>
+template <int D, bool BF>
 static void agent_fwd_launch(const Params& p, hipStream_t st) {
   const unsigned cells = (unsigned)((int64_t)p.B * p.H * p.NC);
-  hipLaunchKernelGGL(agent_pool_kernel<D>, dim3((unsigned)(p.B * p.H * p.P)), dim3(NT), 0, st, p);
-  AMK_AGENT_LAUNCH(agent_s1_partial_kernel, p.P, dim3(cells), dim3(NT), 0, st, p);
+  if constexpr (BF) hipLaunchKernelGGL(agent_pool_bf16_kernel<D>, dim3((unsigned)(p.B * p.H * p.P)), dim3(NT), 0, st, p);
+  else hipLaunchKernelGGL(agent_pool_kernel<D>, dim3((unsigned)(p.B * p.H * p.P)), dim3(NT), 0, st, p);
+  AMK_AGENT_LAUNCH_E(s1_partial, p.P, dim3(cells), dim3(NT), 0, st, p);
   hipLaunchKernelGGL(agent_s1_combine_kernel<D>, dim3((unsigned)(p.B * p.H)), dim3(256), 0, st, p);
-  AMK_AGENT_LAUNCH(agent_s2_kernel, p.P, dim3(cells), dim3(NT), 0, st, p);
+  AMK_AGENT_LAUNCH_E(s2, p.P, dim3(cells), dim3(NT), 0, st, p);
+}
+
+// both element types: BF = false is amk_agent_attn_fwd (float, strides multiples of 4), BF = true amk_agent_attn_bf16_fwd
+// (__bf16, strides multiples of 8)
+template <bool BF>
+static int agent_fwd_host(const char* name, const void* q, const void* k, const void* v, const float* conv_w, const float* conv_b,
+                          void* o, float* agents, float* vagent, float* stats1, float* ws, int B, int H, int T, int Dh, int P,
+                          const Strides& qs, const Strides& ks, const Strides& vs, const Strides& os, float scale, void* stream) {
+  constexpr int ESZ = BF ? 2 : 4, SM = 16 / ESZ;
+  AMK_CHECK_ARG(q && k && v && conv_w && conv_b && o && agents && vagent && stats1 && ws, "%s: null pointer", name);
+  AMK_CHECK_ARG(B > 0 && H > 0 && T > 0 && P > 0, "%s: non-positive size", name);
+  AMK_CHECK_SUPPORTED(dh_ok(Dh), "%s: head dim %d not supported (32, 64 or 128)", name, Dh);
+  AMK_CHECK_SUPPORTED(P <= MAXP && P <= T, "%s: agents per head %d > %d or > T", name, P, MAXP);
+  Params p;
+  p.q = q; p.k = k; p.v = v; p.convw = conv_w; p.convb = conv_b; p.o = o;
+  p.agents = agents; p.vagent = vagent; p.stats1 = stats1; p.part = ws;
+  p.B = B; p.H = H; p.T = T; p.P = P; p.NC = nchunks(T, Dh);
+  p.qs = qs; p.ks = ks; p.vs = vs; p.os = os;
+  p.scale = scale;
+  AMK_CHECK_ARG(a16(q) && a16(k) && a16(v) && a16(o) && sok(p.qs, SM) && sok(p.ks, SM) && sok(p.vs, SM) && sok(p.os, SM),
+                "%s: pointers must be 16-byte aligned and strides multiples of %d", name, SM);
+  const int64_t cells = (int64_t)B * H * p.NC;
+  AMK_CHECK_SUPPORTED(cells * P < (1ll << 31), "%s: B*h*chunks*p exceeds the grid limit", name);
+  AMK_CHECK_SUPPORTED(span_ok(p.qs, H, T, Dh, ESZ) && span_ok(p.ks, H, T, Dh, ESZ) && span_ok(p.vs, H, T, Dh, ESZ) &&
+                          span_ok(p.os, H, T, Dh, ESZ),
+                      "%s: one batch entry of a tensor must span less than 2 GiB with non-negative strides", name);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (Dh == 32) agent_fwd_launch<32, BF>(p, st);
+  else if (Dh == 128) agent_fwd_launch<128, BF>(p, st);
+  else agent_fwd_launch<64, BF>(p, st);
+  AMK_CHECK_LAUNCH(name);
+  return AMK_OK;
 }
 
 extern "C" int amk_agent_attn_fwd(const float* q, const float* k, const float* v, const float* conv_w, const float* conv_b,
@@ -1175,49 +530,89 @@ extern "C" int amk_agent_attn_fwd(const float* q, const float* k, const float* v
                                   int64_t q_sb, int64_t q_st, int64_t q_sh, int64_t k_sb, int64_t k_st, int64_t k_sh,
                                   int64_t v_sb, int64_t v_st, int64_t v_sh, int64_t o_sb, int64_t o_st, int64_t o_sh,
                                   float scale, void* stream) {
-  AMK_CHECK_ARG(q && k && v && conv_w && conv_b && o && agents && vagent && stats1 && ws, "amk_agent_attn_fwd: null pointer");
-  AMK_CHECK_ARG(B > 0 && H > 0 && T > 0 && P > 0, "amk_agent_attn_fwd: non-positive size");
-  AMK_CHECK_SUPPORTED(dh_ok(Dh), "amk_agent_attn_fwd: head dim %d not supported (32, 64 or 128)", Dh);
-  AMK_CHECK_SUPPORTED(P <= MAXP && P <= T, "amk_agent_attn_fwd: agents per head %d > %d or > T", P, MAXP);
-  Params p;
-  p.q = q; p.k = k; p.v = v; p.convw = conv_w; p.convb = conv_b; p.o = o;
-  p.agents = agents; p.vagent = vagent; p.stats1 = stats1; p.part = ws;
-  p.B = B; p.H = H; p.T = T; p.P = P; p.NC = nchunks(T, Dh);
-  p.qs = {q_sb, q_st, q_sh}; p.ks = {k_sb, k_st, k_sh}; p.vs = {v_sb, v_st, v_sh}; p.os = {o_sb, o_st, o_sh};
-  p.scale = scale;
-  AMK_CHECK_ARG(a16(q) && a16(k) && a16(v) && a16(o) && sok(p.qs) && sok(p.ks) && sok(p.vs) && sok(p.os),
-                "amk_agent_attn_fwd: pointers must be 16-byte aligned and strides multiples of 4");
-  const int64_t cells = (int64_t)B * H * p.NC;
-  AMK_CHECK_SUPPORTED(cells * P < (1ll << 31), "amk_agent_attn_fwd: B*h*chunks*p exceeds the grid limit");
-  AMK_CHECK_SUPPORTED(span_ok(p.qs, H, T, Dh) && span_ok(p.ks, H, T, Dh) && span_ok(p.vs, H, T, Dh) && span_ok(p.os, H, T, Dh),
-                      "amk_agent_attn_fwd: one batch entry of a tensor must span less than 2 GiB with non-negative strides");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (Dh == 32) agent_fwd_launch<32>(p, st);
-  else if (Dh == 128) agent_fwd_launch<128>(p, st);
-  else agent_fwd_launch<64>(p, st);
-  AMK_CHECK_LAUNCH("amk_agent_attn_fwd");
-  return AMK_OK;
+  return agent_fwd_host<false>("amk_agent_attn_fwd", q, k, v, conv_w, conv_b, o, agents, vagent, stats1, ws, B, H, T, Dh, P,
+                               {q_sb, q_st, q_sh}, {k_sb, k_st, k_sh}, {v_sb, v_st, v_sh}, {o_sb, o_st, o_sh}, scale, stream);
+}
+extern "C" int amk_agent_attn_bf16_fwd(const void* q, const void* k, const void* v, const float* conv_w, const float* conv_b,
+                                       void* o, float* agents, float* vagent, float* stats1, float* ws,
+                                       int B, int H, int T, int Dh, int P,
+                                       int64_t q_sb, int64_t q_st, int64_t q_sh, int64_t k_sb, int64_t k_st, int64_t k_sh,
+                                       int64_t v_sb, int64_t v_st, int64_t v_sh, int64_t o_sb, int64_t o_st, int64_t o_sh,
+                                       float scale, void* stream) {
+  return agent_fwd_host<true>("amk_agent_attn_bf16_fwd", q, k, v, conv_w, conv_b, o, agents, vagent, stats1, ws, B, H, T, Dh, P,
+                              {q_sb, q_st, q_sh}, {k_sb, k_st, k_sh}, {v_sb, v_st, v_sh}, {o_sb, o_st, o_sh}, scale, stream);
 }
 
 // the LDS-staged chunk kernels for every head dim; the streaming forms (head dim 64, P <= 8) unless AMK_AGENT_STREAM=0
-template <int D>
+template <int D, bool BF>
 static void agent_bwd_launch(const BwdParams& p, hipStream_t st, bool streaming) {
   const unsigned cells = (unsigned)((int64_t)p.B * p.H * p.NC);
   const int P = p.P;
-#define AMK_AGENT_STREAM_LAUNCH(KERNEL)                                                                \
+#define AMK_AGENT_STREAM_LAUNCH_(KERNEL)                                                               \
   do {                                                                                                  \
     if (P <= 4) hipLaunchKernelGGL(KERNEL<4>, dim3(cells), dim3(NT), 0, st, p);                        \
     else if (P <= 6) hipLaunchKernelGGL(KERNEL<6>, dim3(cells), dim3(NT), 0, st, p);                   \
     else hipLaunchKernelGGL(KERNEL<8>, dim3(cells), dim3(NT), 0, st, p);                               \
   } while (0)
-  if (D == 64 && streaming) AMK_AGENT_STREAM_LAUNCH(agent_s2_bwd_stream_kernel);
-  else AMK_AGENT_LAUNCH(agent_s2_bwd_kernel, P, dim3(cells), dim3(NT), 0, st, p);
+#define AMK_AGENT_STREAM_LAUNCH(NAME)                                                    \
+  do {                                                                                   \
+    if constexpr (BF) AMK_AGENT_STREAM_LAUNCH_(agent_##NAME##_stream_bf16_kernel);       \
+    else AMK_AGENT_STREAM_LAUNCH_(agent_##NAME##_stream_kernel);                         \
+  } while (0)
+  if (D == 64 && streaming) AMK_AGENT_STREAM_LAUNCH(s2_bwd);
+  else AMK_AGENT_LAUNCH_E(s2_bwd, P, dim3(cells), dim3(NT), 0, st, p);
   hipLaunchKernelGGL(agent_mid_kernel<D>, dim3((unsigned)(p.B * p.H)), dim3(256), 0, st, p);
-  if (D == 64 && streaming) AMK_AGENT_STREAM_LAUNCH(agent_s1_bwd_stream_kernel);
-  else AMK_AGENT_LAUNCH(agent_s1_bwd_kernel, P, dim3(cells), dim3(NT), 0, st, p);
+  if (D == 64 && streaming) AMK_AGENT_STREAM_LAUNCH(s1_bwd);
+  else AMK_AGENT_LAUNCH_E(s1_bwd, P, dim3(cells), dim3(NT), 0, st, p);
 #undef AMK_AGENT_STREAM_LAUNCH
+#undef AMK_AGENT_STREAM_LAUNCH_
   const int64_t pblk = (int64_t)p.B * p.H * ((p.T + PB - 1) / PB);
-  hipLaunchKernelGGL(agent_pool_bwd_kernel<D>, dim3((unsigned)pblk), dim3(NT), 0, st, p);
+  if constexpr (BF) hipLaunchKernelGGL(agent_pool_bwd_bf16_kernel<D>, dim3((unsigned)pblk), dim3(NT), 0, st, p);
+  else hipLaunchKernelGGL(agent_pool_bwd_kernel<D>, dim3((unsigned)pblk), dim3(NT), 0, st, p);
+}
+
+struct BwdStrides { Strides q, k, v, d_o, dq, dk, dv; };
+
+template <bool BF>
+static int agent_bwd_host(const char* name, const void* q, const void* k, const void* v, const float* conv_w, const void* d_o,
+                          const float* agents, const float* vagent, const float* stats1, void* dq, void* dk, void* dv,
+                          float* ws, float* dconvw_part, float* dconvb_part, int B, int H, int T, int Dh, int P,
+                          const BwdStrides& s, float scale, void* stream) {
+  constexpr int ESZ = BF ? 2 : 4, SM = 16 / ESZ;
+  AMK_CHECK_ARG(q && k && v && conv_w && d_o && agents && vagent && stats1 && dq && dk && dv && ws && dconvw_part &&
+                    dconvb_part, "%s: null pointer", name);
+  AMK_CHECK_ARG(B > 0 && H > 0 && T > 0 && P > 0, "%s: non-positive size", name);
+  AMK_CHECK_SUPPORTED(dh_ok(Dh) && P <= MAXP && P <= T, "%s: unsupported d=%d (32, 64 or 128) / p=%d", name, Dh, P);
+  BwdParams p;
+  p.q = q; p.k = k; p.v = v; p.d_o = d_o; p.convw = conv_w; p.agents = agents; p.vagent = vagent; p.stats1 = stats1;
+  p.dq = dq; p.dk = dk; p.dv = dv; p.dconvw_part = dconvw_part; p.dconvb_part = dconvb_part;
+  p.B = B; p.H = H; p.T = T; p.P = P; p.NC = nchunks(T, Dh);
+  const int64_t cells = (int64_t)B * H * p.NC, rows = (int64_t)B * H * P;
+  // bf16: the f32 stage-2 part of dq comes first (its rows move as float4s: 16-byte aligned when ws is)
+  p.dqf = BF ? ws : nullptr;
+  p.pva = BF ? ws + (int64_t)B * H * T * Dh : ws; p.pa2 = p.pva + cells * P * Dh; p.pa1 = p.pa2 + cells * P * Dh;
+  p.dva = p.pa1 + cells * P * Dh; p.da2 = p.dva + rows * Dh; p.delta1 = p.da2 + rows * Dh;
+  p.qs = s.q; p.ks = s.k; p.vs = s.v; p.dos = s.d_o; p.dqs = s.dq; p.dks = s.dk; p.dvs = s.dv;
+  p.scale = scale;
+  AMK_CHECK_ARG(a16(q) && a16(k) && a16(v) && a16(d_o) && a16(dq) && a16(dk) && a16(dv) && (!BF || a16(ws)) && sok(p.qs, SM) && sok(p.ks, SM) &&
+                    sok(p.vs, SM) && sok(p.dos, SM) && sok(p.dqs, SM) && sok(p.dks, SM) && sok(p.dvs, SM),
+                "%s: pointers must be 16-byte aligned and strides multiples of %d", name, SM);
+  const int64_t pblk = (int64_t)B * H * ((T + PB - 1) / PB);
+  AMK_CHECK_SUPPORTED(pblk < (1ll << 31), "%s: B*h*T exceeds the grid limit", name);
+  AMK_CHECK_SUPPORTED(span_ok(p.qs, H, T, Dh, ESZ) && span_ok(p.ks, H, T, Dh, ESZ) && span_ok(p.vs, H, T, Dh, ESZ) &&
+                          span_ok(p.dos, H, T, Dh, ESZ) && span_ok(p.dqs, H, T, Dh, ESZ) && span_ok(p.dks, H, T, Dh, ESZ) &&
+                          span_ok(p.dvs, H, T, Dh, ESZ),
+                      "%s: one batch entry of a tensor must span less than 2 GiB with non-negative strides", name);
+  AMK_CHECK_SUPPORTED(!BF || (int64_t)T * Dh * 4 < 0x7ffffffell, "%s: one head of the f32 dq workspace must span less than 2 GiB", name);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // AMK_AGENT_STREAM=0: the LDS-staged chunk kernels also for P <= 8 (head dim 64); read per call, like AMK_MOE_NARROW
+  const char* e = getenv("AMK_AGENT_STREAM");
+  const bool streaming = (e ? atoi(e) : 1) && P <= 8;
+  if (Dh == 32) agent_bwd_launch<32, BF>(p, st, streaming);
+  else if (Dh == 128) agent_bwd_launch<128, BF>(p, st, streaming);
+  else agent_bwd_launch<64, BF>(p, st, streaming);
+  AMK_CHECK_LAUNCH(name);
+  return AMK_OK;
 }
 
 extern "C" int amk_agent_attn_bwd(const float* q, const float* k, const float* v, const float* conv_w, const float* d_o,
@@ -1228,37 +623,23 @@ extern "C" int amk_agent_attn_bwd(const float* q, const float* k, const float* v
                                   int64_t v_sb, int64_t v_st, int64_t v_sh, int64_t do_sb, int64_t do_st, int64_t do_sh,
                                   int64_t dq_sb, int64_t dq_st, int64_t dq_sh, int64_t dk_sb, int64_t dk_st, int64_t dk_sh,
                                   int64_t dv_sb, int64_t dv_st, int64_t dv_sh, float scale, void* stream) {
-  AMK_CHECK_ARG(q && k && v && conv_w && d_o && agents && vagent && stats1 && dq && dk && dv && ws && dconvw_part &&
-                    dconvb_part, "amk_agent_attn_bwd: null pointer");
-  AMK_CHECK_ARG(B > 0 && H > 0 && T > 0 && P > 0, "amk_agent_attn_bwd: non-positive size");
-  AMK_CHECK_SUPPORTED(dh_ok(Dh) && P <= MAXP && P <= T, "amk_agent_attn_bwd: unsupported d=%d (32, 64 or 128) / p=%d", Dh, P);
-  BwdParams p;
-  p.q = q; p.k = k; p.v = v; p.d_o = d_o; p.convw = conv_w; p.agents = agents; p.vagent = vagent; p.stats1 = stats1;
-  p.dq = dq; p.dk = dk; p.dv = dv; p.dconvw_part = dconvw_part; p.dconvb_part = dconvb_part;
-  p.B = B; p.H = H; p.T = T; p.P = P; p.NC = nchunks(T, Dh);
-  const int64_t cells = (int64_t)B * H * p.NC, rows = (int64_t)B * H * P;
-  p.pva = ws; p.pa2 = p.pva + cells * P * Dh; p.pa1 = p.pa2 + cells * P * Dh;
-  p.dva = p.pa1 + cells * P * Dh; p.da2 = p.dva + rows * Dh; p.delta1 = p.da2 + rows * Dh;
-  p.qs = {q_sb, q_st, q_sh}; p.ks = {k_sb, k_st, k_sh}; p.vs = {v_sb, v_st, v_sh}; p.dos = {do_sb, do_st, do_sh};
-  p.dqs = {dq_sb, dq_st, dq_sh}; p.dks = {dk_sb, dk_st, dk_sh}; p.dvs = {dv_sb, dv_st, dv_sh};
-  p.scale = scale;
-  AMK_CHECK_ARG(a16(q) && a16(k) && a16(v) && a16(d_o) && a16(dq) && a16(dk) && a16(dv) && sok(p.qs) && sok(p.ks) &&
-                    sok(p.vs) && sok(p.dos) && sok(p.dqs) && sok(p.dks) && sok(p.dvs),
-                "amk_agent_attn_bwd: pointers must be 16-byte aligned and strides multiples of 4");
-  const int64_t pblk = (int64_t)B * H * ((T + PB - 1) / PB);
-  AMK_CHECK_SUPPORTED(pblk < (1ll << 31), "amk_agent_attn_bwd: B*h*T exceeds the grid limit");
-  AMK_CHECK_SUPPORTED(span_ok(p.qs, H, T, Dh) && span_ok(p.ks, H, T, Dh) && span_ok(p.vs, H, T, Dh) && span_ok(p.dos, H, T, Dh) &&
-                          span_ok(p.dqs, H, T, Dh) && span_ok(p.dks, H, T, Dh) && span_ok(p.dvs, H, T, Dh),
-                      "amk_agent_attn_bwd: one batch entry of a tensor must span less than 2 GiB with non-negative strides");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  // AMK_AGENT_STREAM=0: the LDS-staged chunk kernels also for P <= 8 (head dim 64); read per call, like AMK_MOE_NARROW
-  const char* e = getenv("AMK_AGENT_STREAM");
-  const bool streaming = (e ? atoi(e) : 1) && P <= 8;
-  if (Dh == 32) agent_bwd_launch<32>(p, st, streaming);
-  else if (Dh == 128) agent_bwd_launch<128>(p, st, streaming);
-  else agent_bwd_launch<64>(p, st, streaming);
-  AMK_CHECK_LAUNCH("amk_agent_attn_bwd");
-  return AMK_OK;
+  return agent_bwd_host<false>("amk_agent_attn_bwd", q, k, v, conv_w, d_o, agents, vagent, stats1, dq, dk, dv, ws, dconvw_part,
+                               dconvb_part, B, H, T, Dh, P,
+                               {{q_sb, q_st, q_sh}, {k_sb, k_st, k_sh}, {v_sb, v_st, v_sh}, {do_sb, do_st, do_sh},
+                                {dq_sb, dq_st, dq_sh}, {dk_sb, dk_st, dk_sh}, {dv_sb, dv_st, dv_sh}}, scale, stream);
+}
+extern "C" int amk_agent_attn_bf16_bwd(const void* q, const void* k, const void* v, const float* conv_w, const void* d_o,
+                                       const float* agents, const float* vagent, const float* stats1,
+                                       void* dq, void* dk, void* dv, float* ws, float* dconvw_part, float* dconvb_part,
+                                       int B, int H, int T, int Dh, int P,
+                                       int64_t q_sb, int64_t q_st, int64_t q_sh, int64_t k_sb, int64_t k_st, int64_t k_sh,
+                                       int64_t v_sb, int64_t v_st, int64_t v_sh, int64_t do_sb, int64_t do_st, int64_t do_sh,
+                                       int64_t dq_sb, int64_t dq_st, int64_t dq_sh, int64_t dk_sb, int64_t dk_st, int64_t dk_sh,
+                                       int64_t dv_sb, int64_t dv_st, int64_t dv_sh, float scale, void* stream) {
+  return agent_bwd_host<true>("amk_agent_attn_bf16_bwd", q, k, v, conv_w, d_o, agents, vagent, stats1, dq, dk, dv, ws, dconvw_part,
+                              dconvb_part, B, H, T, Dh, P,
+                              {{q_sb, q_st, q_sh}, {k_sb, k_st, k_sh}, {v_sb, v_st, v_sh}, {do_sb, do_st, do_sh},
+                               {dq_sb, dq_st, dq_sh}, {dk_sb, dk_st, dk_sh}, {dv_sb, dv_st, dv_sh}}, scale, stream);
 }
 
 // dconvw[c][a*3+b] = sum over the rows of dconvw_part[row][a*3+b][c]; dconvb[c] = sum of dconvb_part[row][c]: one launch,

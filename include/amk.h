@@ -476,6 +476,38 @@ int amk_agent_attn_bwd(const float* q, const float* k, const float* v, const flo
 int amk_agent_conv_grad_reduce(const float* dconvw_part, const float* dconvb_part, int64_t rows, int D,
                                float* dconvw, float* dconvb, void* stream);
 
+/* The AgentAttention core (models/agent_attention.py:55-73) on bf16 elements, for torch.autocast(bfloat16): q, k, v, o
+ * (and d_o, dq, dk, dv in the backward) are bf16 views, strides in elements; agents, vagent, stats1, the workspaces,
+ * the convolution's parameters and its gradient partials stay f32 and amk_agent_conv_grad_reduce is shared.  The same
+ * kernels as the f32 entry points above, instantiated on another element type: a lane's 4 channels are one 8-byte
+ * access, widened exactly on the load; all arithmetic is the f32 arithmetic of amk_agent_attn_fwd / _bwd in the same
+ * order; o, dq, dk, dv are rounded to nearest even once, on the store.  So the f32 outputs equal bit for bit those of
+ * the f32 entry points on the upcast tensors, and the bf16 outputs are their f32 outputs rounded once.  dq is the sum
+ * of a stage-2 part and a pooled part written by two kernels: the first part crosses in f32 through the workspace,
+ * which is why the backward's workspace is (B,H,T,D) floats larger:
+ *   amk_agent_bf16_ws_floats(.., 0) = amk_agent_ws_floats_dh(.., 0),  (.., 1) = amk_agent_ws_floats_dh(.., 1) + B*H*T*D.
+ * Refused before any device work: null pointers, non-positive sizes, a bf16 tensor (or the backward's ws) that is not
+ * 16-byte aligned, a stride that is no multiple of 8 elements (AMK_EINVAL); D outside {32, 64, 128}, P > 16 or P > T,
+ * a batch entry of 2 GiB or more (2-byte elements) or negative strides, a grid beyond 2^31 (AMK_EUNSUPPORTED).
+ * AMK_AGENT_STREAM is read on every call of amk_agent_attn_bf16_bwd, as in amk_agent_attn_bwd. */
+int64_t amk_agent_bf16_ws_floats(int B, int H, int T, int P, int D, int backward);
+
+int amk_agent_attn_bf16_fwd(const void* q, const void* k, const void* v, const float* conv_w, const float* conv_b,
+                            void* o, float* agents, float* vagent, float* stats1, float* ws,
+                            int B, int H, int T, int D, int P,
+                            int64_t q_sb, int64_t q_st, int64_t q_sh, int64_t k_sb, int64_t k_st, int64_t k_sh,
+                            int64_t v_sb, int64_t v_st, int64_t v_sh, int64_t o_sb, int64_t o_st, int64_t o_sh,
+                            float scale, void* stream);
+
+int amk_agent_attn_bf16_bwd(const void* q, const void* k, const void* v, const float* conv_w, const void* d_o,
+                            const float* agents, const float* vagent, const float* stats1,
+                            void* dq, void* dk, void* dv, float* ws, float* dconvw_part, float* dconvb_part,
+                            int B, int H, int T, int D, int P,
+                            int64_t q_sb, int64_t q_st, int64_t q_sh, int64_t k_sb, int64_t k_st, int64_t k_sh,
+                            int64_t v_sb, int64_t v_st, int64_t v_sh, int64_t do_sb, int64_t do_st, int64_t do_sh,
+                            int64_t dq_sb, int64_t dq_st, int64_t dq_sh, int64_t dk_sb, int64_t dk_st, int64_t dk_sh,
+                            int64_t dv_sb, int64_t dv_st, int64_t dv_sh, float scale, void* stream);
+
 /* --------------------------------------------------------------------------
  * Residual-add + LayerNorm and the bias-gradient column sum (the
  * pre-LN / residual epilogues around the attention and FFN of models/vitvqgan.py:44-61 and

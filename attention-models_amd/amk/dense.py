@@ -282,6 +282,45 @@ def gemm_x6_nt_swiglu_bwd(dy, w3t_planes, ab):
     return d_ab
 
 
+def x6_tn_chunks(M, N, K):
+    """Chunks of the M rows amk_gemm_x6_tn sums its partial tiles over (1: no workspace), from its workspace size."""
+    nbytes = _lib.load().amk_gemm_x6_tn_ws_bytes(M, N, K)
+    return nbytes // ((N * K + N) * 4) if nbytes else 1
+
+
+def gemm_x6_tn(y, x, *, y2=None, want_bias=False, out=None, out2=None, bias_out=None):
+    """dense.gemm_tn (without ln) on split-bf16 products (csrc/gemm_x6_tn.hip): y^T @ x, with y2 a second gradient against
+    the same x (y.shape[1] a multiple of 128).  Returns (dw, dw2 or None, colsum(y | y2) or None); out / out2 / bias_out:
+    write the results there (OVERWRITING) instead of into fresh tensors."""
+    y, x, y2 = _mat(y, "y"), _mat(x, "x"), _mat(y2, "y2")
+    M, N1 = y.shape
+    K = x.shape[1]
+    N2 = y2.shape[1] if y2 is not None else 0
+    if x.shape[0] != M or (y2 is not None and y2.shape[0] != M):
+        raise RuntimeError(f"gemm_x6_tn: y {tuple(y.shape)} against x {tuple(x.shape)}")
+    dw = _out(out, (N1, K), "gemm_x6_tn out")
+    if dw is None:
+        dw = torch.empty((N1, K), device=y.device, dtype=torch.float32)
+    dw2 = None
+    if y2 is not None:
+        dw2 = _out(out2, (N2, K), "gemm_x6_tn out2")
+        if dw2 is None:
+            dw2 = torch.empty((N2, K), device=y.device, dtype=torch.float32)
+    db = None
+    if want_bias:
+        db = _out(bias_out, (N1 + N2,), "gemm_x6_tn bias_out")
+        if db is None:
+            db = torch.empty((N1 + N2,), device=y.device, dtype=torch.float32)
+    L = _lib.load()
+    N = N1 + N2
+    nbytes = L.amk_gemm_x6_tn_ws_bytes(M, N, K)
+    ws = torch.empty((nbytes // 4,), device=y.device, dtype=torch.float32) if nbytes else None
+    rc = L.amk_gemm_x6_tn(_p(y), y.stride(0), _p(y2), y2.stride(0) if y2 is not None else 0, N1 if y2 is not None else 0,
+                          _p(x), x.stride(0), _p(dw), K, _p(dw2), K, _p(db), M, N, K, _p(ws), nbytes, _stream())
+    _lib.check(rc, "amk_gemm_x6_tn")
+    return dw, dw2, db
+
+
 def _mat16(t, what):
     if not t.is_cuda:
         raise RuntimeError("amk ops run only on MI355X (HIP) tensors; got a CPU tensor. There is no CPU fallback.")

@@ -90,6 +90,8 @@ SIGNATURES = {
     "amk_gemm_x6_nt_swiglu": (_I, [_P, _L, _P, _P, _P, _L, _P, _L, _I, _I, _I, _P]),
     "amk_gemm_x6_nt_swiglu_bwd": (_I, [_P, _L, _P, _P, _L, _P, _L, _I, _I, _I, _P]),
     "amk_gemm_x6_split_table": (_I, [_P, _L, _P, _I, _L, _P, _L, _P]),
+    "amk_gemm_x6_tn_ws_bytes": (_L, [_L, _I, _I]),
+    "amk_gemm_x6_tn": (_I, [_P, _L, _P, _L, _I, _P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _P, _L, _P]),
     "amk_gemm_f32_ws_bytes": (_L, [_c.POINTER(GemmDesc)]),
     "amk_gemm_f32": (_I, [_c.POINTER(GemmDesc), _P, _L, _P]),
     "amk_row_stats": (_I, [_P, _L, _I, _F, _P, _P, _P]),

@@ -1828,10 +1828,37 @@ X6_LINEAR = os.environ.get("AMK_X6_LINEAR", "1") != "0"
 # the layer kinds "auto" puts on the x6 forms (profiles/x6_linear_step_breakdown.log decides): linear, linear2, ffn
 X6_AUTO_KINDS = frozenset(k for k in os.environ.get("AMK_X6_KINDS", "linear,linear2,ffn").split(",") if k)
 # ... and the products of such a layer that run there: "fwd" = the forward products (always), "dx" = the input gradients
-# too (against the planes of W^T, which are only kept with it).  Default "fwd": back to back every product wins
+# too (against the planes of W^T, which are only kept with it).  "dx" is off by default: back to back every product wins
 # (profiles/kbench_x6_linear.log), but in the step the input gradients' 1.2 ms came with 1.0 ms on the attention backward
 # that runs between them and 0.9 ms on the weight-gradient kernels (profiles/x6_linear_step_breakdown.log).
-X6_AUTO_FORMS = frozenset(k for k in os.environ.get("AMK_X6_FORMS", "fwd").split(",") if k)
+# "dw" = the weight (and bias) gradients of such a layer on csrc/gemm_x6_tn.hip (both operands are activations and are
+# split inside the kernel: no planes involved).  Default "fwd,dw": the weight gradients fall from 11.5 to 7.8 ms of device
+# time per step and, unlike "dx", cost the kernels around them nothing measurable -- the headline gains 3.3 ms against a
+# parent spread of 0.31 (profiles/x6_tn_step_breakdown.log).  All five gradient shapes of the step are on it: every one wins
+# back to back (x1.40 - x1.47, profiles/kbench_x6_tn.log) and the step with all of them cleared the A/B at the first attempt,
+# so no shape is held back on the f32 kernel.
+X6_AUTO_FORMS = frozenset(k for k in os.environ.get("AMK_X6_FORMS", "fwd,dw").split(",") if k)
+
+
+def _x6_tn_ok(M, N, K, *lds):
+    """The preconditions of amk_gemm_x6_tn for a gradient (N, K) over M rows with operand row strides `lds`, so that other
+    shapes take dense.gemm_tn instead of an error from the C side: multiples of 4, and every operand (with the three
+    steps its prefetch runs past a chunk) under 1 GiB."""
+    if M < 1 or N % 4 or K % 4 or any(ld % 4 for ld in lds):
+        return False
+    return all((M + 96) * ld * 4 < (1 << 30) for ld in lds) and N * K * 4 < (1 << 30)
+
+
+def _x6_tn(y, x, **kw):
+    """dense.gemm_tn's product for the backward of the x6 Functions: on dense.gemm_x6_tn when the "dw" form is on and the
+    shapes are that kernel's, else on dense.gemm_tn (exact f32)."""
+    from . import dense
+
+    y2 = kw.get("y2")
+    if "dw" in X6_AUTO_FORMS and _x6_tn_ok(y.shape[0], y.shape[1] + (y2.shape[1] if y2 is not None else 0), x.shape[1],
+                                           *(t.stride(0) for t in (y, x, y2) if t is not None and t.stride(1) == 1)):
+        return dense.gemm_x6_tn(y, x, **kw)
+    return dense.gemm_tn(y, x, **kw)
 
 
 def gemm_x6_nt(a2, b2, bias=None):
@@ -1918,7 +1945,8 @@ def _x6_planes(kind, x, *weights, gate=None):
 
 class _X6Linear(torch.autograd.Function):
     """_DenseLinear with the forward and dX = dY W on the split-bf16 GEMM against the weight's kept planes (those of W^T
-    for dX); dW and db stay on dense.gemm_tn, exact f32, written into the reducer's buckets."""
+    for dX); dW and db from _x6_tn (dense.gemm_x6_tn with the "dw" form, else dense.gemm_tn, exact f32), written into the
+    reducer's buckets."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, pl):
@@ -1941,13 +1969,13 @@ class _X6Linear(torch.autograd.Function):
             dx = (dense.gemm_x6_nt(dy2, ctx.pl.wt, ctx.pl.K) if ctx.pl.wt is not None else _nn_plain(dy2, weight)).view(ctx.x_shape)
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
             want_b = ctx.has_bias and ctx.needs_input_grad[2]
-            dw, db = _tn_into(dense.gemm_tn, dy2, x2, ctx.params[0], ctx.params[1] if want_b else None)
+            dw, db = _tn_into(_x6_tn, dy2, x2, ctx.params[0], ctx.params[1] if want_b else None)
         return dx, dw, db, None
 
 
 class _X6Linear2(torch.autograd.Function):
     """_DenseLinear2 on the kept planes: (x Wa^T, x Wb^T); dX = dA Wa + dB Wb as one launch over two contraction
-    segments; (dWa, dWb) from dense.gemm_tn as there."""
+    segments; (dWa, dWb) from one launch of _x6_tn, as there from dense.gemm_tn."""
 
     @staticmethod
     def forward(ctx, x, wa, wb, pa, pb):
@@ -1975,7 +2003,7 @@ class _X6Linear2(torch.autograd.Function):
         dwa = dwb = None
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
             (ar, av), (br, bv) = _claim(ctx.params[0]), _claim(ctx.params[1])
-            dwa, dwb, _ = dense.gemm_tn(da2, x2, y2=db2, out=av, out2=bv)
+            dwa, dwb, _ = _x6_tn(da2, x2, y2=db2, out=av, out2=bv)
             if av is not None:
                 ar.wrote(ctx.params[0])
                 dwa = None
@@ -1988,7 +2016,7 @@ class _X6Linear2(torch.autograd.Function):
 class _X6SwiGLUFFN(torch.autograd.Function):
     """_SwiGLUFFN on the kept planes: the gate in the epilogue of the w12 product (w12's planes in the gate order; (a | b)
     written only when a backward will read it), w3, dGate = dOut W3 with the gate's derivative in its epilogue and
-    dX = d(a | b) W12 on the split-bf16 GEMM; the four weight / bias gradients on dense.gemm_tn as there."""
+    dX = d(a | b) W12 on the split-bf16 GEMM; the four weight / bias gradients from _x6_tn."""
 
     @staticmethod
     def forward(ctx, x, w12, b12, w3, b3, p12, p3):
@@ -2012,11 +2040,11 @@ class _X6SwiGLUFFN(torch.autograd.Function):
         p12, p3 = ctx.pl
         d2 = dout.reshape(-1, dout.shape[-1])
         d_ab = dense.gemm_x6_nt_swiglu_bwd(d2, p3.wt, ab) if p3.wt is not None else dense.gemm_nn(d2, w3, swiglu_ab=ab)
-        dw3, db3 = _tn_into(dense.gemm_tn, d2, gate, ctx.params[2], ctx.params[3] if ctx.has_bias[1] else None)
+        dw3, db3 = _tn_into(_x6_tn, d2, gate, ctx.params[2], ctx.params[3] if ctx.has_bias[1] else None)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = (dense.gemm_x6_nt(d_ab, p12.wt, p12.K) if p12.wt is not None else _nn_plain(d_ab, w12)).view(ctx.x_shape)
-        dw12, db12 = _tn_into(dense.gemm_tn, d_ab, x2, ctx.params[0], ctx.params[1] if ctx.has_bias[0] else None)
+        dw12, db12 = _tn_into(_x6_tn, d_ab, x2, ctx.params[0], ctx.params[1] if ctx.has_bias[0] else None)
         return dx, dw12, db12, dw3, db3, None, None
 
 

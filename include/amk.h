@@ -639,6 +639,18 @@ int amk_gemm_x6_nt_swiglu_bwd(const float* dY, int64_t ldy, const void* w3t_plan
                               float* d_ab, int64_t ldd, int M, int H, int K, void* stream);
 int amk_gemm_x6_split_table(const float* flat, int64_t flat_elems, const void* table, int n_entries, int64_t n_blocks,
                             void* planes, int64_t planes_elems, void* stream);
+/* The weight (and bias) gradient of the same layers on split-bf16 products (csrc/gemm_x6_tn.hip):
+ * c[n, k] = sum_m y[m, n] x[m, k] with y (M, N) and x (M, K) f32 row-major (the contraction index is the row), both split
+ * into three bf16 parts inside the kernel, six products per 16 rows accumulated in f32; dbias (N, optional) = the column
+ * sums of y in f32.  split > 0 (a multiple of 128, < N): rows [0, split) of the result come from y and go to c, rows
+ * [split, N) come from y2 (M, N - split) and go to c2, against the same x (dWq | dWkv in one launch); split = 0: y2, c2
+ * unused.  The M rows are summed in chunks, in a fixed order (bitwise reproducible); workspace: the _ws_bytes() call
+ * below (0 when one chunk suffices), 16-byte aligned.  AMK_EUNSUPPORTED: N, K or a leading dimension not a multiple of 4, a
+ * pointer off 16-byte alignment, an operand of 2 GiB or more, an output or one chunk's operand rows of 1 GiB or more. */
+int64_t amk_gemm_x6_tn_ws_bytes(int64_t M, int N, int K);
+int amk_gemm_x6_tn(const float* y, int64_t ldy, const float* y2, int64_t ldy2, int split, const float* x, int64_t ldx,
+                   float* c, int64_t ldc, float* c2, int64_t ldc2, float* dbias, int64_t M, int N, int K,
+                   void* workspace, int64_t ws_bytes, void* stream);
 
 /* --------------------------------------------------------------------------
  * Dense exact-f32 GEMMs with the surrounding element-wise passes folded in.

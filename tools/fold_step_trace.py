@@ -18,6 +18,7 @@ FAMILIES = [
     ("f32 NT (gemm_nt_dkernel / gemm_nt_kernel)", r"amk_dense.*gemm_nt_"),
     ("f32 NN (gemm_nn_kernel)", r"amk_dense.*gemm_nn_"),
     ("f32 TN + reduce (weight gradients)", r"amk_dense.*(gemm_tn_|tn_reduce)"),
+    ("x6 TN + reduce (weight gradients)", r"gemm_x6_tn_kernel|x6_tn_reduce_kernel"),
     ("library GEMMs (Cijk_*)", r"^Cijk_"),
     ("attention (attn_*)", r"attn_"),
 ]

@@ -3,8 +3,10 @@ it today against the split-bf16 forms on cached planes (csrc/gemm_x6.hip; planes
 table-driven split the optimizer runs once per step), fused forms included.  The two sides are interleaved in one process
 for several rounds with an untimed pass in front of each timed one (tools/kbench_steady.py's rule); the last round is
 reported, with the error of both against fp64 (max |c - c64| / max |c64|, on the first 2048 rows) and the cost of the
-split itself.
-    python tools/kbench_x6_linear.py [--batch 32] [--iters 20] [--rounds 3]
+split itself.  Then the five weight gradients (dWq | dWkv as one launch, dWo, dW12, dW3, each with its bias sums) on
+dense.gemm_tn (exact f32) against dense.gemm_x6_tn (csrc/gemm_x6_tn.hip, both operands split inside the kernel), the same
+way, their error against fp64 over the whole gradient (AMK_X6_TN_TK=128 | 256 forces that kernel's tile width).
+    python tools/kbench_x6_linear.py [--batch 32] [--iters 20] [--rounds 3] [--only all|fwd|dw]
 """
 import argparse
 import os
@@ -23,6 +25,7 @@ if __name__ == "__main__":
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--only", choices=("all", "fwd", "dw"), default="all", help="fwd: the nine forward / input-gradient rows; dw: the weight gradients")
     a = ap.parse_args()
     from amk import dense, ops, tuning
 
@@ -105,7 +108,7 @@ if __name__ == "__main__":
          lambda: d_ab[R_].double() @ W["w12"].double()),
     ]
     tot = [0.0, 0.0]
-    for name, fl, f32, x6, ref in cases:
+    for name, fl, f32, x6, ref in (cases if a.only != "dw" else []):
         want = ref()
         errs = [float((fn()[R_].double() - want).abs().max() / want.abs().max()) for fn in (f32, x6)]
         for rnd in range(a.rounds):
@@ -114,4 +117,29 @@ if __name__ == "__main__":
         tot[1] += ts[1]
         print(f"{name:42s} f32 {ts[0] * 1e6:7.1f} us {fl / ts[0] / 1e12:6.1f} TF/s err {errs[0]:.1e} | x6 {ts[1] * 1e6:7.1f} us "
               f"{fl / ts[1] / 1e12:6.1f} TF/s err {errs[1]:.1e} | x{ts[0] / ts[1]:.2f}", flush=True)
-    print(f"sum over the nine products (the gate counted in both forms): f32 {tot[0] * 1e3:.3f} ms, x6 {tot[1] * 1e3:.3f} ms")
+    if a.only != "dw":
+        print(f"sum over the nine products (the gate counted in both forms): f32 {tot[0] * 1e3:.3f} ms, x6 {tot[1] * 1e3:.3f} ms")
+    if a.only == "fwd":
+        sys.exit(0)
+
+    # ---- the weight gradients: (name, (y, y2 or None), x); every launch takes its bias sums along, as the step's do
+    dws = [("dWq | dWkv (512 | 1024 x 256, one launch)", (dq, dkv), x), ("dWo (256 x 512)", (dout, None), att),
+           ("dW12 (2736 x 256)", (d_ab, None), x), ("dW3 (256 x 1368)", (dout, None), gate)]
+    tot = [0.0, 0.0]
+    for name, (y, y2), xx in dws:
+        fns = [lambda tn=tn: tn(y, xx, y2=y2, want_bias=True) for tn in (dense.gemm_tn, dense.gemm_x6_tn)]
+        want = (torch.cat([y, y2], 1) if y2 is not None else y).double().t() @ xx.double()
+        errs = []
+        for fn in fns:
+            dw, dw2, _ = fn()
+            got = torch.cat([dw, dw2], 0) if dw2 is not None else dw
+            errs.append(float((got.double() - want).abs().max() / want.abs().max()))
+        del want
+        fl = 2.0 * M * (y.shape[1] + (y2.shape[1] if y2 is not None else 0)) * xx.shape[1]
+        for rnd in range(a.rounds):
+            ts = [time_launches(fn, a.iters, warm=a.iters) for fn in fns]
+        tot[0] += ts[0]
+        tot[1] += ts[1]
+        print(f"{name:42s} f32 {ts[0] * 1e6:7.1f} us {fl / ts[0] / 1e12:6.1f} TF/s err {errs[0]:.1e} | x6 {ts[1] * 1e6:7.1f} us "
+              f"{fl / ts[1] / 1e12:6.1f} TF/s err {errs[1]:.1e} | x{ts[0] / ts[1]:.2f}", flush=True)
+    print(f"sum over the four weight-gradient launches of a layer: f32 {tot[0] * 1e3:.3f} ms, x6 {tot[1] * 1e3:.3f} ms")

@@ -2,6 +2,7 @@
 # domains) over a micro-benchmark, folded by tools/pmc_quick.py into OUT/digest.txt.  Run on the GPU box through gpurun:
 #   OUT=r3_pmc_dense bash tools/pmc_dense.sh                       (dense GEMMs: tools/kbench_dense.py)
 #   OUT=r3_pmc_bf16 SCRIPT=tools/kbench_attn_bf16.py ARGS="--iters 5" FILTER="attn_bf16 attn_fwd_kernel attn_bwd_fused" bash tools/pmc_dense.sh
+#   OUT=x6_tn_pmc SCRIPT=tools/kbench_x6_linear.py ARGS="--only dw --rounds 1 --iters 3" FILTER="gemm_tn_kernel gemm_x6_tn_kernel" bash tools/pmc_dense.sh
 set -e
 R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/${OUT:-r3_pmc_dense}

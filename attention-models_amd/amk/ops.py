@@ -254,10 +254,19 @@ ATTN_BWD_KEYS128 = 16
 ATTN_BWD_KEYS256 = 32
 ATTN_BWD_DQ_REPRO = 64
 ATTN_BWD_FAST_REPRO = 73  # delta + fused + reproducible dq
+ATTN_BWD_X6 = 128         # kept-scores fused pass: dV / dK products on split-bf16 MFMA
+
+# The kept-scores backward of head dim 64 at 256 keys per workgroup with its dV and dK products on split-bf16 MFMA
+# (csrc/attn_bwd_fused_x6.hip; f32-grade results, dq unchanged): "1" whenever the call qualifies, "0" never, "auto" from
+# ATTENTION_BWD_X6_MIN_SCORES scores (B*H*I*J) on.  Only the autograd path (stages=None) takes it: a caller that passes
+# `stages` gets exactly those bits.
+ATTENTION_BACKWARD_X6 = os.environ.get("AMK_ATTN_BWD_X6", "auto")
+ATTENTION_BWD_X6_MIN_SCORES = 1 << 22
 
 
 def _attn_backward(q, k, v, o, stats, d_o, dq, dk, dv, key_mask, causal_mask, scale, stages=None, delta=None,
                    scores=None):
+    auto_stages = stages is None
     if stages is None:
         det = DETERMINISTIC_ATTENTION_BACKWARD or torch.are_deterministic_algorithms_enabled()
         stages = ATTN_BWD_ALL if ATTENTION_BACKWARD_TWO_KERNEL else (ATTN_BWD_FAST_REPRO if det else ATTN_BWD_FAST)
@@ -269,6 +278,13 @@ def _attn_backward(q, k, v, o, stats, d_o, dq, dk, dv, key_mask, causal_mask, sc
     if D != 64 and stages & ATTN_BWD_DQ_REPRO:
         scores = None   # head dims other than 64 under the reproducible mode: the two recompute kernels (no kept scores)
     J = k.shape[2]
+    if ATTENTION_BACKWARD_X6 not in ("auto", "0", "1"):
+        raise RuntimeError(f"ops.ATTENTION_BACKWARD_X6 must be auto, 0 or 1 (got {ATTENTION_BACKWARD_X6!r})")
+    keys256 = bool(stages & ATTN_BWD_KEYS256) or (not stages & ATTN_BWD_KEYS128 and J >= 256)
+    if (auto_stages and scores is not None and D == 64 and keys256 and dq.stride() == (I * H * D, D, H * D, 1)
+            and (ATTENTION_BACKWARD_X6 == "1"
+                 or (ATTENTION_BACKWARD_X6 == "auto" and B * H * I * J >= ATTENTION_BWD_X6_MIN_SCORES))):
+        stages |= ATTN_BWD_X6
     d_o = _as_kernel_view(d_o)
     L = _lib.load()
     need = L.amk_attn_bwd_ws_floats(B, H, I, J, int(stages))

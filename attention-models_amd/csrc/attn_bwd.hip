@@ -73,7 +73,21 @@ static int attn_bwd_impl(const float* scores, const float* q, const float* k, co
                           ((int64_t)I + TILE) * q_st * 4 < (1ll << 31) && ((int64_t)I + TILE) * do_st * 4 < (1ll << 31),
                       "amk_attn_bwd: one (batch, head) slab must span < 2 GiB");
   hipStream_t st = static_cast<hipStream_t>(stream);
+  const bool x6 = (stages & AMK_ATTN_BWD_X6) != 0;
+  if (x6) {   // the split-bf16 variant of the kept-scores kernel has one geometry and no fallback
+    const int keys = fused_keys_per_wg(J, (stages & AMK_ATTN_BWD_KEYS256) ? 256 : ((stages & AMK_ATTN_BWD_KEYS128) ? 128 : 0));
+    AMK_CHECK_SUPPORTED(scores && (stages & AMK_ATTN_BWD_FUSED), "amk_attn_bwd: AMK_ATTN_BWD_X6 is for amk_attn_bwd_kept with AMK_ATTN_BWD_FUSED");
+    AMK_CHECK_SUPPORTED(Dh == D, "amk_attn_bwd_kept: AMK_ATTN_BWD_X6 exists for head dim %d only (head dim %d)", D, Dh);
+    AMK_CHECK_SUPPORTED(keys == 256, "amk_attn_bwd_kept: AMK_ATTN_BWD_X6 runs at 256 keys per workgroup only (J = %d: %d)", J, keys);
+    AMK_CHECK_SUPPORTED(dq_sh == D && dq_st == (int64_t)H * D && dq_sb == (int64_t)I * H * D,
+                        "amk_attn_bwd_kept: AMK_ATTN_BWD_X6 needs the dense (B, I, H, %d) dq layout", D);
+  }
   if (stages & AMK_ATTN_BWD_DELTA) launch_attn_bwd_gen(p, Dh, AMK_ATTN_BWD_DELTA, st);
+  if (x6) {
+    AMK_CHECK_SUPPORTED(launch_attn_bwd_fused_x6(p, st), "amk_attn_bwd_kept: the split-bf16 one-pass kernel could not be launched");
+    AMK_CHECK_LAUNCH("amk_attn_bwd");
+    return AMK_OK;
+  }
   if (stages & AMK_ATTN_BWD_FUSED) {
     // the one-pass kernel of this head dim (attn_bwd_fused.hip: 32, 64, 128; the others have none) when the layout
     // allows it, else the two recompute kernels

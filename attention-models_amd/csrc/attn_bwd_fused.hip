@@ -474,6 +474,11 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_reduce_kernel(const float* __
   }
 }
 
+void launch_attn_bwd_dq_reduce(const float* part, int nk, int64_t n4, float* dq, hipStream_t st) {
+  const unsigned grid = (unsigned)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
+  hipLaunchKernelGGL(attn_bwd_dq_reduce_kernel, dim3(grid), dim3(256), 0, st, part, nk, n4, dq);
+}
+
 template <int DH, int NW, int QS, bool KEPT, int DQ, bool CAUSAL>
 static bool launch_one(BwdParams p, hipStream_t st) {
   using G = FGeom<DH, NW, QS>;
@@ -486,11 +491,7 @@ static bool launch_one(BwdParams p, hipStream_t st) {
   if (DQ == 0 && hipMemsetAsync(p.dq, 0, (size_t)ndq * sizeof(float), st) != hipSuccess) return false;
   const int64_t nk = (int64_t)p.B * p.H * p.nkblk;
   hipLaunchKernelGGL((attn_bwd_fused_kernel<DH, NW, QS, KEPT, DQ, CAUSAL>), dim3((unsigned)nk), dim3(G::NT), G::LDS_FLOATS * sizeof(float), st, p);
-  if (DQ == 1 && p.nkblk > 1) {
-    const int64_t n4 = ndq / 4;
-    const unsigned grid = (unsigned)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
-    hipLaunchKernelGGL(attn_bwd_dq_reduce_kernel, dim3(grid), dim3(256), 0, st, p.dq_part, p.nkblk, n4, p.dq);
-  }
+  if (DQ == 1 && p.nkblk > 1) launch_attn_bwd_dq_reduce(p.dq_part, p.nkblk, ndq / 4, p.dq, st);
   return true;
 }
 

@@ -130,6 +130,10 @@ void launch_attn_fwd_x6(const FwdParams& p, int64_t nwg, hipStream_t st, bool pl
 // attn_bwd_fused.hip: one-pass backward for head dims 32, 64, 128 (dQ by atomics); false = not applicable, nothing launched.
 bool launch_attn_bwd_fused(const BwdParams& p, int Dh, int keys_per_wg, hipStream_t st);
 int fused_keys_per_wg(int J, int keys_per_wg);
+// the ordered sum of the reproducible dq's per-key-block partials (n4: float4s of dq)
+void launch_attn_bwd_dq_reduce(const float* part, int nk, int64_t n4, float* dq, hipStream_t st);
+// attn_bwd_fused_x6.hip: the head-dim-64, 256-key, kept-scores one-pass backward with dV / dK on split-bf16 MFMA
+bool launch_attn_bwd_fused_x6(const BwdParams& p, hipStream_t st);
 
 // attn_generic.hip / attn_generic.h: the forward for head dims 32, 96, 128, 160, 192, 224, 256 (attn_gen_supported),
 // and the backward's delta and two recompute kernels for those and for 64 (stages: the DELTA, DKDV and DQ bits)

@@ -236,6 +236,12 @@ int amk_gemm_rows_bf16(const void* x, int64_t ldx, const void* w, int64_t ldw, c
  * (the deltas followed by the partials). */
 #define AMK_ATTN_BWD_DQ_REPRO 64
 #define AMK_ATTN_BWD_FAST_REPRO 73  /* delta + fused + reproducible dq */
+/* amk_attn_bwd_kept only, with AMK_ATTN_BWD_FUSED: the dV and dK products of the one-pass kernel on split-bf16 MFMA
+ * (six partial products of three bf16 planes per operand, f32 accumulation: f32-grade results, see amk_attn_fwd_x6;
+ * csrc/attn_bwd_fused_x6.hip).  dq is that of the call without the bit, bit for bit under AMK_ATTN_BWD_DQ_REPRO.
+ * Head dim 64 at 256 keys per workgroup (J >= 256, or AMK_ATTN_BWD_KEYS256) with the dense dq layout; every other
+ * call with the bit set -- amk_attn_bwd included -- is refused with AMK_EUNSUPPORTED, nothing launched. */
+#define AMK_ATTN_BWD_X6 128
 int64_t amk_attn_bwd_ws_floats(int B, int H, int I, int J, int stages);
 int amk_attn_bwd(const float* q, const float* k, const float* v, const float* o,
                  const float* stats, const float* d_o,

@@ -1,6 +1,7 @@
 """Attention core at the ViT-VQGAN layer shape: forward with / without kept scores, fused backward with
-128 / 256 keys per workgroup, recomputed / kept scores.
-    python tools/kbench_attn_bwd.py [--batch 32] [--iters 30]
+128 / 256 keys per workgroup, recomputed / kept scores, and the kept-scores backward with its dV / dK products on
+split-bf16 MFMA (AMK_ATTN_BWD_X6) back to back with the f32 one, arms alternating, dq by atomics and reproducible.
+    python tools/kbench_attn_bwd.py [--batch 32] [--iters 30] [--rounds 5]
 """
 import argparse
 import os
@@ -22,6 +23,7 @@ if __name__ == "__main__":
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--T", type=int, default=1024)
     ap.add_argument("--H", type=int, default=8)
+    ap.add_argument("--rounds", type=int, default=5, help="alternations of the f32 / split-bf16 kept-scores backward")
     a = ap.parse_args()
     from amk import lib, ops
 
@@ -56,5 +58,18 @@ if __name__ == "__main__":
         ops._attn_backward(q, k, v, o, stats, d_o, dq, dk, dv, None, None, scale, stages=1, delta=big)
         t = time_launches(fn, a.iters)
         rows.append((f"attn_bwd_fused keys=256 {'kept' if kept else 'recompute'} reproducible dq", t, 2 * core))
+    # f32 against split-bf16 dV / dK, kept scores, 256 keys: the arms alternate so that clock and temperature drift hits both
+    arms = [(f"attn_bwd_fused keys=256 kept {'x6 dV/dK' if x6 else 'f32'}{' reproducible dq' if repro else ''}", 8 | 32 | repro | x6)
+            for repro in (0, 64) for x6 in (0, 128)]
+    times = {name: [] for name, _ in arms}
+    for _ in range(a.rounds):
+        for name, st in arms:
+            fn = lambda: ops._attn_backward(q, k, v, o, stats, d_o, dq, dk, dv, None, None, scale, stages=st, delta=big, scores=scores)
+            times[name].append(time_launches(fn, a.iters, warm=max(3, a.iters)))
     for name, t, fl in rows:
         print(f"{name:44s} {t * 1e3:8.4f} ms  {fl / t / 1e12:7.2f} TFLOP/s  {fl / t / 1e12 / PEAK:.3f} of f32 MFMA peak", flush=True)
+    for name, _ in arms:
+        ts = sorted(times[name])
+        med = ts[len(ts) // 2]
+        print(f"{name:52s} median {med * 1e3:7.4f} ms  min {ts[0] * 1e3:7.4f}  max {ts[-1] * 1e3:7.4f}  ({a.rounds} alternating rounds)  "
+              f"{2 * core / med / 1e12:7.2f} algorithmic TFLOP/s", flush=True)

@@ -96,9 +96,7 @@ struct BwdParams {
                                    // backward, which adds the pooled term in f32 and rounds dq once
 };
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float4 f4(float x) { return make_float4(x, x, x, x); }
+__device__ __forceinline__ float4 splat4(float x) { return make_float4(x, x, x, x); }
 // Global rows through buffer descriptors with the validity folded into the OFFSET (an invalid row gets an offset past
 // the descriptor's range: the load returns zeros, the store is dropped).  `cond ? *ptr : 0` compiles to a branch
 // around the load, and behind such a branch every wait drains everything in flight: a tile's eight row requests
@@ -156,12 +154,6 @@ __device__ __forceinline__ void fma4(float4& a, float s, const float4& x) {
 }
 __device__ __forceinline__ void mad4(float4& a, const float4& w, const float4& x) {
   a.x += w.x * x.x; a.y += w.y * x.y; a.z += w.z * x.z; a.w += w.w * x.w;
-}
-// barrier that orders LDS only: global loads issued before it stay in flight across it (__syncthreads() drains them)
-__device__ __forceinline__ void lds_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 __host__ __device__ __forceinline__ int bin_lo(int i, int T, int P) { return (int)(((int64_t)i * T) / P); }
 __host__ __device__ __forceinline__ int bin_hi(int i, int T, int P) { return (int)((((int64_t)(i + 1)) * T + P - 1) / P); }
@@ -443,7 +435,6 @@ constexpr int PB = 64;   // tokens per workgroup of the pool backward
 
 using namespace amk_agent;
 
-static bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 // strides count elements: a row of a lane's 4 channels starts on a 16-byte boundary (4 floats, 8 bf16)
 static bool sok(const Strides& s, int64_t m) { return s.sb % m == 0 && s.st % m == 0 && s.sh % m == 0; }
 // the kernels address one batch entry's (h, T, d) slab through a 32-bit byte offset (offsets from 2^31 on mean "past the end")
@@ -654,9 +645,9 @@ __global__ __launch_bounds__(256) void agent_conv_reduce_kernel(const float* __r
   const int c4i = threadIdx.x & 3, part = threadIdx.x >> 2, c0 = blockIdx.y * 16;
   const float* src = (r < 9 ? wpart + (int64_t)r * D : bpart) + c0 + c4i * 4;
   const int64_t stride = r < 9 ? 9 * D : D;
-  float4 acc = amk_agent::f4(0.f);
+  float4 acc = amk_agent::splat4(0.f);
   for (int64_t i = part; i < rows; i += 64) {
-    const float4 v = amk_agent::ld4(src + i * stride);
+    const float4 v = ld4(src + i * stride);
     acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
   }
   red[part][c4i * 4 + 0] = acc.x; red[part][c4i * 4 + 1] = acc.y; red[part][c4i * 4 + 2] = acc.z; red[part][c4i * 4 + 3] = acc.w;

@@ -23,7 +23,7 @@ __global__ __launch_bounds__(NT) void AGENT_KERNEL(pool)(Params p) {
   const int h = bh % p.H, b = bh / p.H;
   const E* qb = static_cast<const E*>(p.q) + (int64_t)b * p.qs.sb + (int64_t)h * p.qs.sh;
   const int lo = bin_lo(i, p.T, p.P), hi = bin_hi(i, p.T, p.P);
-  float4 s = f4(0.f);
+  float4 s = splat4(0.f);
   for (int t = lo + (tid >> C::LPR_LOG); t < hi; t += C::RPP) {
     const float4 x = gld4<E>(qb + (int64_t)t * p.qs.st + c4);
     s.x += x.x; s.y += x.y; s.z += x.z; s.w += x.w;
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(NT) void AGENT_KERNEL(s1_partial)(Params p) {
   {  // phase B: D / 4 lanes per value row, RPP rows of the chunk per pass
     float4 acc[PM];
 #pragma unroll
-    for (int i = 0; i < PM; ++i) acc[i] = f4(0.f);
+    for (int i = 0; i < PM; ++i) acc[i] = splat4(0.f);
 #pragma unroll
     for (int j = 0; j < C::NPIECE; ++j) {
       const int r = C::RPP * j + sub;
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(NT) void AGENT_KERNEL(s2)(Params p) {
     load_taps(p.convw, c4, wq);
     const float4 cb = ld4(p.convb + c4);
 #pragma unroll
-    for (int i = 0; i < PM; ++i) var[i] = (i < P) ? ld4(p.vagent + (w.bh * P + i) * D + c4) : f4(0.f);
+    for (int i = 0; i < PM; ++i) var[i] = (i < P) ? ld4(p.vagent + (w.bh * P + i) * D + c4) : splat4(0.f);
     const __amdgpu_buffer_rsrc_t ors = slab(static_cast<E*>(p.o) + (int64_t)w.b * p.os.sb + (int64_t)w.h * p.os.sh);
 #pragma unroll
     for (int j = 0; j < RPG; ++j) {
@@ -313,7 +313,7 @@ __global__ __launch_bounds__(NT) void AGENT_KERNEL(s2_bwd)(BwdParams p) {
     float* dst = tile + tok * TS + HALF * half;
 #pragma unroll
     for (int j = 0; j < HALF / 4; ++j) {
-      float4 o = f4(0.f);
+      float4 o = splat4(0.f);
 #pragma unroll
       for (int i = 0; i < PM; ++i)
         if (i < P) fma4(o, dp[i], ld4(&As[i * D + HALF * half + 4 * j]));
@@ -323,11 +323,11 @@ __global__ __launch_bounds__(NT) void AGENT_KERNEL(s2_bwd)(BwdParams p) {
   __syncthreads();
   AG_STAMP(3);
   unstage_rows<D, float>(tile, dqb, dq_part_st<D, E>(p), t0, T, tid);
-  float4 accva[PM], acca[PM], dw9[9], dbs = f4(0.f);
+  float4 accva[PM], acca[PM], dw9[9], dbs = splat4(0.f);
 #pragma unroll
-  for (int i = 0; i < PM; ++i) { accva[i] = f4(0.f); acca[i] = f4(0.f); }
+  for (int i = 0; i < PM; ++i) { accva[i] = splat4(0.f); acca[i] = splat4(0.f); }
 #pragma unroll
-  for (int j = 0; j < 9; ++j) dw9[j] = f4(0.f);
+  for (int j = 0; j < 9; ++j) dw9[j] = splat4(0.f);
   {
 #pragma unroll 1
     for (int j = 0; j < RPG; ++j) {
@@ -471,7 +471,7 @@ __global__ __launch_bounds__(NT) void AGENT_KERNEL(s1_bwd)(BwdParams p) {
     float* dst = tile + tok * TS + HALF * half;
 #pragma unroll
     for (int j = 0; j < HALF / 4; ++j) {
-      float4 o = f4(0.f);
+      float4 o = splat4(0.f);
 #pragma unroll
       for (int i = 0; i < PM; ++i)
         if (i < P) fma4(o, ds[i], ld4(&As[i * D + HALF * half + 4 * j]));
@@ -489,7 +489,7 @@ __global__ __launch_bounds__(NT) void AGENT_KERNEL(s1_bwd)(BwdParams p) {
     float4 wq[9], dva[PM];
     load_taps(p.convw, c4, wq);
 #pragma unroll
-    for (int i = 0; i < PM; ++i) { acca[i] = f4(0.f); dva[i] = (i < P) ? ld4(&dVas[i * D + c4]) : f4(0.f); }
+    for (int i = 0; i < PM; ++i) { acca[i] = splat4(0.f); dva[i] = (i < P) ? ld4(&dVas[i * D + c4]) : splat4(0.f); }
     // dv[h, t] += sum_{a, b} w[a][b] dO[h - (a - 1), t - (b - 1)]: window slot s holds dO[., t - 1 + s] of head h + 1 - a
     const __amdgpu_buffer_rsrc_t grs = slab(gbatch), krs = slab(kb), dvrs = slab(dvb);
     auto ldg = [&](int a, int t) {
@@ -508,7 +508,7 @@ __global__ __launch_bounds__(NT) void AGENT_KERNEL(s1_bwd)(BwdParams p) {
     for (int j = 0; j < RPG; ++j) {
       const int r = RPG * grp + j, t = t0 + r;
       const float4 kv = krow[0];
-      float4 dvv = f4(0.f);
+      float4 dvv = splat4(0.f);
 #pragma unroll
       for (int a = 0; a < 3; ++a)
 #pragma unroll
@@ -566,9 +566,9 @@ __global__ __launch_bounds__(NT) void AGENT_KERNEL(s2_bwd_stream)(BwdParams p) {
   float4 A[PM], Va[PM], accva[PM], acca[PM];
 #pragma unroll
   for (int i = 0; i < PM; ++i) {
-    A[i] = i < P ? ld4(p.agents + (w.bh * P + i) * D + c4) : f4(0.f);
-    Va[i] = i < P ? ld4(p.vagent + (w.bh * P + i) * D + c4) : f4(0.f);
-    accva[i] = f4(0.f); acca[i] = f4(0.f);
+    A[i] = i < P ? ld4(p.agents + (w.bh * P + i) * D + c4) : splat4(0.f);
+    Va[i] = i < P ? ld4(p.vagent + (w.bh * P + i) * D + c4) : splat4(0.f);
+    accva[i] = splat4(0.f); acca[i] = splat4(0.f);
   }
 #pragma unroll 1
   for (int j = 0; j < RPG; ++j) {
@@ -589,7 +589,7 @@ __global__ __launch_bounds__(NT) void AGENT_KERNEL(s2_bwd_stream)(BwdParams p) {
     float dl = 0.f;
 #pragma unroll
     for (int i = 0; i < PM; ++i) { sc[i] *= il; dl += sc[i] * dp[i]; }
-    float4 dq = f4(0.f);
+    float4 dq = splat4(0.f);
 #pragma unroll
     for (int i = 0; i < PM; ++i) {
       const float ds = sc[i] * (dp[i] - dl);
@@ -666,18 +666,18 @@ __global__ __launch_bounds__(NT) void AGENT_KERNEL(s1_bwd_stream)(BwdParams p) {
     As[i * D + lane] = p.agents[(w.bh * P + i) * D + lane];
     dVas[i * D + lane] = p.dva[(w.bh * P + i) * D + lane];
   }
-  float4 acca[PM], dw9[9], dbs = f4(0.f);
+  float4 acca[PM], dw9[9], dbs = splat4(0.f);
 #pragma unroll
-  for (int i = 0; i < PM; ++i) acca[i] = f4(0.f);
+  for (int i = 0; i < PM; ++i) acca[i] = splat4(0.f);
 #pragma unroll
-  for (int j = 0; j < 9; ++j) dw9[j] = f4(0.f);
+  for (int j = 0; j < 9; ++j) dw9[j] = splat4(0.f);
   __syncthreads();
 #pragma unroll 1
   for (int j = 0; j < RPG; ++j) {
     const int t = tfirst + j;
     const float4 kr = kv[0][0], vr = kv[1][0];
     const bool ok = t < T;
-    float4 dk = f4(0.f), dvv = f4(0.f);
+    float4 dk = splat4(0.f), dvv = splat4(0.f);
 #pragma unroll
     for (int a = 0; a < 3; ++a)
 #pragma unroll
@@ -777,7 +777,7 @@ __global__ __launch_bounds__(NT) void AGENT_KERNEL(pool_bwd)(BwdParams p) {
   for (int r0 = 0; r0 < PB; r0 += C::RPP) {
     const int t = t0 + r0 + (tid >> C::LPR_LOG);
     if (t < T) {
-      float4 add = f4(0.f);
+      float4 add = splat4(0.f);
       for (int i = 0; i < P; ++i)
         if (t >= lo_s[i] && t < hi_s[i]) fma4(add, 1.f, ld4(&dA[i * D + c4]));
       E* dst = dqb + (int64_t)t * p.dqs.st + c4;

@@ -25,14 +25,12 @@
 // 16x16 output tile per wave.  dQ leaves as per-key-block f32 partials (plain stores) that a second launch sums in
 // key-block order and rounds to bf16: no atomics, bitwise reproducible.
 #include "attn_common.h"
+#include "amk_bf16.h"
 
 namespace amk_attn_bf16 {
 
 using amk_attn::Strides;
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 constexpr int KSTR = 72;   // bf16 per row of a row-read image (64 + 8): 144 B
@@ -52,13 +50,6 @@ struct Params {
   int nqblk, nkblk;
 };
 
-__device__ __forceinline__ f32x16 mfmab(bf16x8 a, bf16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f32x16 zero16() {
-  f32x16 z;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) z[i] = 0.f;
-  return z;
-}
 __device__ __forceinline__ float vmax(float a, float b, float pinf) { return __builtin_amdgcn_fmed3f(a, b, pinf); }
 // a * b - c with two roundings.  HIP contracts a plain a * b - c into one FMA (__fmul_rn / __fsub_rn included: they are
 // a * b and a - b), and an FMA leaves the rounding error of c = m * c2 in the exponent -- up to +-64 at the fill value's
@@ -71,11 +62,6 @@ __device__ __forceinline__ float mul_sub_rn(float a, float b, float c) {
 __device__ __forceinline__ float max3(float a, float b, float c) { return __builtin_fmaxf(__builtin_fmaxf(a, b), c); }
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-// transposing read: this lane's 4 elements = one column of a 4-row x 16-column block of 16-bit values
-__device__ __forceinline__ bf16x4 tr_read(const __bf16* p) {
-  const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p);
-  return __builtin_bit_cast(bf16x4, v);
-}
 __device__ __forceinline__ bf16x8 cat4(bf16x4 a, bf16x4 b) {
   bf16x8 r;
 #pragma unroll
@@ -90,22 +76,6 @@ __device__ __forceinline__ bf16x8 pack8(const f32x16& s, int t) {
   for (int j = 0; j < 8; ++j) r[j] = (__bf16)s[8 * t + j];
   return r;
 }
-// A fragment of X^T for a product that sums over the ROWS of the LDS tile X [row][col], rows in packed-accumulator
-// order: lane (col = c0 + (l & 31), half) gets rows 16 t + 4 half + (0..3) and + 8.
-//   img: tile base; stride in elements; c0: first column of the 32-column block
-__device__ __forceinline__ bf16x8 tr_frag(const __bf16* img, int stride, int t, int c0, int lane) {
-  const int hf = lane >> 5, grp = (lane >> 4) & 1, q = (lane & 15) >> 2, pp = lane & 3;
-  const __bf16* a = img + (16 * t + 4 * hf + q) * stride + c0 + 16 * grp + 4 * pp;
-  return cat4(tr_read(a), tr_read(a + 8 * stride));
-}
-
-// barrier that orders LDS only (global loads in flight stay in flight)
-__device__ __forceinline__ void lds_barrier_bf() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 template <bool MASKED>
 __global__ __launch_bounds__(256, 2) void attn_bf16_fwd_kernel(Params p) {
@@ -184,7 +154,7 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_fwd_kernel(Params p) {
   commit(0);
   prefetch(1);         // (unconditional throughout: a tile past the sequence is outside the descriptors and reads zeros; a
                        //  branch around a memory instruction would make every wait of the loop a full drain)
-  lds_barrier_bf();
+  lds_barrier();
   for (int t = 0; t < ntile; ++t) {
     const int j0 = t * 64;
     const __bf16* Ks = Ks2[t & 1];
@@ -217,7 +187,7 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_fwd_kernel(Params p) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int r = 4 * g + e;
-          const float fa = amk_attn::f4(f0, e), fb = amk_attn::f4(f1, e);
+          const float fa = f4(f0, e), fb = f4(f1, e);
           float t0 = ((cb0 >> r) & 1u) ? fill_raw : s0[r], t1 = ((cb1 >> r) & 1u) ? fill_raw : s1[r];
           s0[r] = fa == 0.f ? t0 : fa;     // (key-padding fill and the -inf past the sequence win over the causal fill: same value or -inf)
           s1[r] = fb == 0.f ? t1 : fb;
@@ -298,14 +268,14 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_fwd_kernel(Params p) {
     for (int g = 0; g < 4; ++g) {
       const bf16x8 pp = (g < 2) ? pack8(s0, g & 1) : pack8(s1, g & 1);
       const __bf16* vt = Vs + (32 * (g >> 1)) * TSTR;     // the 32-key block of this slot
-      const bf16x8 va = tr_frag(vt, TSTR, g & 1, 0, lane);
-      const bf16x8 vb = tr_frag(vt, TSTR, g & 1, 32, lane);
+      const bf16x8 va = tr_frag_packed<TSTR>(vt, g & 1, 0, lane);
+      const bf16x8 vb = tr_frag_packed<TSTR>(vt, g & 1, 32, lane);
       o0 = mfmab(va, pp, o0);
       o1 = mfmab(vb, pp, o1);
     }
     commit((t + 1) & 1);   // tile t + 1 (requested a tile ago) into the other stage; past the last tile: zeros nobody reads
     prefetch(t + 2);
-    lds_barrier_bf();      // every wave is done with stage t & 1 and has written its part of stage (t + 1) & 1
+    lds_barrier();   // every wave is done with stage t & 1 and has written its part of stage (t + 1) & 1
   }
   const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
   const float inv = 1.f / l_tot;
@@ -536,7 +506,7 @@ __global__ __launch_bounds__(64 * BW, 1) void attn_bf16_bwd_kernel(Params p) {
           const bool filled = kfilled || ((cbits >> r) & 1u);
           const float tt = filled ? fill_raw : s[r];
           // (s * c2) - m with two rounded operations, as the forward formed it: exactly 0 where the fill is the row maximum
-          float pr = __builtin_amdgcn_exp2f(mul_sub_rn(tt, c2, amk_attn::f4(m4, e))) * amk_attn::f4(l4, e);
+          float pr = __builtin_amdgcn_exp2f(mul_sub_rn(tt, c2, f4(m4, e))) * f4(l4, e);
           pr = kvalid ? pr : 0.f;
           s[r] = pr;                                 // a filled position still has its weight in P (dV), but passes no gradient
           dp[r] = filled ? 0.f : dp[r] * pr;
@@ -567,10 +537,10 @@ __global__ __launch_bounds__(64 * BW, 1) void attn_bf16_bwd_kernel(Params p) {
 #pragma unroll
     for (int u = 0; u < ((A16_ABLATE & 4) ? 0 : 2); ++u) {
       const bf16x8 pb = pack8(s, u), db = pack8(dp, u);
-      dv0 = mfmab(tr_frag(dOtr, TSTR, u, 0, lane), pb, dv0);
-      dv1 = mfmab(tr_frag(dOtr, TSTR, u, 32, lane), pb, dv1);
-      dk0 = mfmab(tr_frag(Qtr, TSTR, u, 0, lane), db, dk0);
-      dk1 = mfmab(tr_frag(Qtr, TSTR, u, 32, lane), db, dk1);
+      dv0 = mfmab(tr_frag_packed<TSTR>(dOtr, u, 0, lane), pb, dv0);
+      dv1 = mfmab(tr_frag_packed<TSTR>(dOtr, u, 32, lane), pb, dv1);
+      dk0 = mfmab(tr_frag_packed<TSTR>(Qtr, u, 0, lane), db, dk0);
+      dk1 = mfmab(tr_frag_packed<TSTR>(Qtr, u, 32, lane), db, dk1);
     }
     commit((t + 1) & 1, slot);   // (past the last tile: zeros nobody reads)
     prefetch(t + 3, slot);
@@ -701,16 +671,11 @@ extern "C" int amk_attn_bf16_bwd(const void* q, const void* k, const void* v, co
   const int64_t nwg = (int64_t)B * H * p.nkblk;
   AMK_CHECK_SUPPORTED(nwg < (1ll << 31), "amk_attn_bf16_bwd: grid too large");
   constexpr size_t lds = (size_t)(BKEYS * TSTR + 2 * BKEYS * DSTR + 4 * (32 * KSTR + 32 * TSTR)) * 2 + 2 * 128 * 4;
-  static bool attr_set[64] = {};   // per device ordinal (the opt-in to > 64 KiB of dynamic LDS is per device)
   int dev_id = 0;
   AMK_CHECK_ARG(hipGetDevice(&dev_id) == hipSuccess && dev_id >= 0 && dev_id < 64, "amk_attn_bf16_bwd: no current device");
-  if (!attr_set[dev_id]) {
-    AMK_CHECK_SUPPORTED(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bf16_bwd_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess &&
-                        hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bf16_bwd_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess &&
-                        hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bf16_bwd_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess,
-                        "amk_attn_bf16_bwd: the device refused %zu bytes of dynamic LDS", lds);
-    attr_set[dev_id] = true;
-  }
+  AMK_CHECK_SUPPORTED((amk_lds_optin<attn_bf16_bwd_kernel<false, false>>((int)lds) && amk_lds_optin<attn_bf16_bwd_kernel<true, false>>((int)lds) &&
+                       amk_lds_optin<attn_bf16_bwd_kernel<true, true>>((int)lds)),
+                      "amk_attn_bf16_bwd: the device refused %zu bytes of dynamic LDS", lds);
   if (causal_mask) hipLaunchKernelGGL((attn_bf16_bwd_kernel<true, true>), dim3((unsigned)nwg), dim3(64 * BW), lds, st, p);
   else if (key_mask) hipLaunchKernelGGL((attn_bf16_bwd_kernel<true, false>), dim3((unsigned)nwg), dim3(64 * BW), lds, st, p);
   else hipLaunchKernelGGL((attn_bf16_bwd_kernel<false, false>), dim3((unsigned)nwg), dim3(64 * BW), lds, st, p);

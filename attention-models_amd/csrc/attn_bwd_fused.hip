@@ -482,10 +482,7 @@ void launch_attn_bwd_dq_reduce(const float* part, int nk, int64_t n4, float* dq,
 template <int DH, int NW, int QS, bool KEPT, int DQ, bool CAUSAL>
 static bool launch_one(BwdParams p, hipStream_t st) {
   using G = FGeom<DH, NW, QS>;
-  static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_fused_kernel<DH, NW, QS, KEPT, DQ, CAUSAL>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                  G::LDS_FLOATS * (int)sizeof(float)) == hipSuccess;
-  if (!attr_ok) return false;
+  if (!amk_lds_optin<attn_bwd_fused_kernel<DH, NW, QS, KEPT, DQ, CAUSAL>>(G::LDS_FLOATS * (int)sizeof(float))) return false;
   p.nkblk = (p.J + G::KB - 1) / G::KB;
   const int64_t ndq = (int64_t)p.B * p.I * p.H * DH;
   if (DQ == 0 && hipMemsetAsync(p.dq, 0, (size_t)ndq * sizeof(float), st) != hipSuccess) return false;

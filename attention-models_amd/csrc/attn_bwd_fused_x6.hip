@@ -19,14 +19,11 @@
 // LDS: Gs 8.5 + K 68 + dS 32.5 + row constants 0.5 + six plane images 36 = 145.5 KiB: one workgroup per CU, as the
 // f32 kernel in fact runs (118 KiB), so the launch bounds give the wave its 256 registers.
 #include "attn_common.h"
+#include "amk_bf16.h"
 
 namespace amk_attn {
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int DH = 64, NW = 8, TQ = 32, NT = 64 * NW, KB = 32 * NW, HD = DH / 2, LS = DH + 4, NTILE = DH / 32;
 constexpr int DS_STRIDE = KB + 4, KPG = KB / 4;
@@ -37,66 +34,18 @@ constexpr int LDS_BYTES = F32_FLOATS * 4 + 6 * PIMG * 2;
 static_assert(F32_FLOATS % 4 == 0 && LDS_BYTES <= 160 * 1024, "16-byte aligned plane images inside the CU's LDS");
 
 __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f32x16 mfmab(bf16x8 a, bf16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-
-// x = h + m + l in bf16 (attn_fwd_x6.hip, gemm_x6.hip)
-__device__ __forceinline__ void split1(float x, __bf16& h, __bf16& m, __bf16& l) {
-  h = (__bf16)x;
-  const float r1 = x - (float)h;
-  m = (__bf16)r1;
-  l = (__bf16)(r1 - (float)m);
-}
-__device__ __forceinline__ void split4(const float4& x, bf16x4 (&pl)[3]) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    __bf16 h, m, l;
-    split1(f4(x, j), h, m, l);
-    pl[0][j] = h; pl[1][j] = m; pl[2][j] = l;
-  }
-}
-// registers 8t .. 8t+7 of a 32x32 accumulator as the three planes of a k-slot (the B operand of a product that sums
-// over the accumulator's rows)
-__device__ __forceinline__ void split_slot(const f32x16& s, int t, bf16x8 (&pl)[3]) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    __bf16 h, m, l;
-    split1(s[8 * t + j], h, m, l);
-    pl[0][j] = h; pl[1][j] = m; pl[2][j] = l;
-  }
-}
-// transposing read: this lane's 4 elements = one column of a 4-row x 16-column block of 16-bit values
-__device__ __forceinline__ bf16x4 tr_read(const __bf16* p) {
-  const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p);
-  return __builtin_bit_cast(bf16x4, v);
-}
-// A fragment of X^T for a product that sums over the ROWS of the LDS tile X [row][TSTR], rows in packed-accumulator
-// order: lane (col = c0 + (l & 31), half) gets rows 16 t + 4 half + (0..3) and + 8   (tr_frag of attn_bf16.hip)
-__device__ __forceinline__ bf16x8 tr_frag(const __bf16* img, int t, int c0, int lane) {
-  const int hf = lane >> 5, grp = (lane >> 4) & 1, q = (lane & 15) >> 2, pp = lane & 3;
-  const __bf16* a = img + (16 * t + 4 * hf + q) * TSTR + c0 + 16 * grp + 4 * pp;
-  const bf16x4 lo = tr_read(a), hi = tr_read(a + 8 * TSTR);
-  bf16x8 r;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) { r[i] = lo[i]; r[4 + i] = hi[i]; }
-  return r;
-}
 
 // c0 / c1 (dims 0..31 / 32..63 x this lane's key) += X^T acc over the 16 queries of k-slot ks: X the plane images of
 // dO or q, acc the P or dS accumulator
 __device__ __forceinline__ void x6_pair(const __bf16* img, const f32x16& acc, int ks, int lane, f32x16& c0, f32x16& c1) {
   bf16x8 b[3], a0[3], a1[3];
-  split_slot(acc, ks, b);
+  split8(acc, 8 * ks, b);   // registers 8 ks .. of the accumulator: the B operand's k-slot
 #pragma unroll
   for (int q = 0; q < 3; ++q) {
-    a0[q] = tr_frag(img + q * PIMG, ks, 0, lane);
-    a1[q] = tr_frag(img + q * PIMG, ks, 32, lane);
+    a0[q] = tr_frag_packed<TSTR>(img + q * PIMG, ks, 0, lane);
+    a1[q] = tr_frag_packed<TSTR>(img + q * PIMG, ks, 32, lane);
   }
-  c0 = mfmab(a0[1], b[1], c0); c1 = mfmab(a1[1], b[1], c1);
-  c0 = mfmab(a0[2], b[0], c0); c1 = mfmab(a1[2], b[0], c1);
-  c0 = mfmab(a0[0], b[2], c0); c1 = mfmab(a1[0], b[2], c1);
-  c0 = mfmab(a0[1], b[0], c0); c1 = mfmab(a1[1], b[0], c1);
-  c0 = mfmab(a0[0], b[1], c0); c1 = mfmab(a1[0], b[1], c1);
-  c0 = mfmab(a0[0], b[0], c0); c1 = mfmab(a1[0], b[0], c1);
+  mfma6x2(a0, b, c0, a1, b, c1);
 }
 
 // DQ and CAUSAL as in attn_bwd_fused_kernel
@@ -385,9 +334,7 @@ __global__ __launch_bounds__(NT, 1) void attn_bwd_fused_x6_kernel(BwdParams p) {
 
 template <int DQ, bool CAUSAL>
 bool launch_one(BwdParams p, hipStream_t st) {
-  static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_fused_x6_kernel<DQ, CAUSAL>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) == hipSuccess;
-  if (!attr_ok) return false;
+  if (!amk_lds_optin<attn_bwd_fused_x6_kernel<DQ, CAUSAL>>(LDS_BYTES)) return false;
   p.nkblk = (p.J + KB - 1) / KB;
   const int64_t ndq = (int64_t)p.B * p.I * p.H * DH;
   if (DQ == 0 && hipMemsetAsync(p.dq, 0, (size_t)ndq * sizeof(float), st) != hipSuccess) return false;

@@ -66,13 +66,6 @@ struct ScoreTiles {
 // med3 back into maxnum and re-inserts the canonicalisation.
 __device__ __forceinline__ float vmax(float a, float b, float pinf) { return __builtin_amdgcn_fmed3f(a, b, pinf); }
 
-__device__ __forceinline__ f32x16 zero16() {
-  f32x16 z;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) z[i] = 0.f;
-  return z;
-}
-
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // Streams ROWS rows x DH floats of one (batch, head) operand, global -> registers, 16 B per thread
@@ -116,12 +109,6 @@ typedef RowStagerT<TILE> RowStager;
 // what the f32 entry points ask of every tensor: float4 accesses
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline bool strides_ok(const Strides& s) { return (s.sb % 4 == 0) && (s.st % 4 == 0) && (s.sh % 4 == 0); }
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float f4(const float4& v, int e) {
-  return e == 0 ? v.x : (e == 1 ? v.y : (e == 2 ? v.z : v.w));
-}
 
 // attn_fwd_x6.hip: the forward with split-bf16 products (pre-pass + kernel; p.scores non-null: scores kept).
 // plain: unmasked calls may take the unmasked specialisation

@@ -24,7 +24,7 @@
 //   * append mode (k_new given): key n = *n_dev is the new row.  The key group that owns position n takes it from
 //     k_new / v_new -- never from the cache -- and is the only writer of cache row n, so no workgroup of the launch
 //     reads a row that another writes.
-#include "amk_common.h"
+#include "amk_bf16.h"
 #include "attn_common.h"
 
 #include <stdlib.h>
@@ -237,7 +237,6 @@ static void launch_chunks(int nv, dim3 grid, hipStream_t st, const Args& a) {
 // i < ceil(D / 64) and the group still reads 128 contiguous bytes per step.  At D % 64 == 32 the last step covers 32 dims:
 // lanes 0-3 load, lanes 4-7 hold exact zeros for q, k and v there (no load, no store).  The new row goes to the cache as the
 // 16-byte pieces it was loaded in, bitwise; chunking, workspace, n_dev and the order of every sum are those of the f32 kernels.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 struct ArgsB {
   const __bf16 *q, *k_new, *v_new;

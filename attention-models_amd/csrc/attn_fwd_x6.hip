@@ -27,62 +27,13 @@
 // unmasked specialisation with attn_fwd_plain_kernel's softmax (lazy reference, no fill path, peeled ragged tile,
 // v_max3_f32 row maxima: this file is built with -fno-honor-nans -mno-amdgpu-ieee as attn_fwd.hip is).
 #include "attn_common.h"
+#include "amk_bf16.h"
 #include <type_traits>
 
 namespace amk_attn {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
 constexpr int PSTR = 72;                 // bf16 per LDS row (64 + 8): 144 B, conflict-free 16-byte row reads
 constexpr int PLANE = TILE * PSTR;       // one plane of a 64-row tile
-
-__device__ __forceinline__ f32x16 mfmab(bf16x8 a, bf16x8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-// the six partial products, smallest first
-__device__ __forceinline__ f32x16 mfma6(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x16 c) {
-  c = mfmab(a[1], b[1], c);
-  c = mfmab(a[2], b[0], c);
-  c = mfmab(a[0], b[2], c);
-  c = mfmab(a[1], b[0], c);
-  c = mfmab(a[0], b[1], c);
-  c = mfmab(a[0], b[0], c);
-  return c;
-}
-// two independent accumulators fed by the same B planes, MFMAs alternating so that no MFMA waits on its predecessor
-__device__ __forceinline__ void mfma6x2(const bf16x8 (&a0)[3], const bf16x8 (&a1)[3], const bf16x8 (&b)[3], f32x16& c0, f32x16& c1) {
-  c0 = mfmab(a0[1], b[1], c0); c1 = mfmab(a1[1], b[1], c1);
-  c0 = mfmab(a0[2], b[0], c0); c1 = mfmab(a1[2], b[0], c1);
-  c0 = mfmab(a0[0], b[2], c0); c1 = mfmab(a1[0], b[2], c1);
-  c0 = mfmab(a0[1], b[0], c0); c1 = mfmab(a1[1], b[0], c1);
-  c0 = mfmab(a0[0], b[1], c0); c1 = mfmab(a1[0], b[1], c1);
-  c0 = mfmab(a0[0], b[0], c0); c1 = mfmab(a1[0], b[0], c1);
-}
-__device__ __forceinline__ void split1(float x, __bf16& h, __bf16& m, __bf16& l) {
-  h = (__bf16)x;
-  const float r1 = x - (float)h;
-  m = (__bf16)r1;
-  l = (__bf16)(r1 - (float)m);
-}
-__device__ __forceinline__ void split8(const float (&x)[8], bf16x8 (&pl)[3]) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    __bf16 h, m, l;
-    split1(x[j], h, m, l);
-    pl[0][j] = h; pl[1][j] = m; pl[2][j] = l;
-  }
-}
-__device__ __forceinline__ void split4(float a, float b, float c, float d, bf16x4 (&pl)[3]) {
-  const float x[4] = {a, b, c, d};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    __bf16 h, m, l;
-    split1(x[j], h, m, l);
-    pl[0][j] = h; pl[1][j] = m; pl[2][j] = l;
-  }
-}
-
 
 // Q^T operand: lane (query, half) holds, for each of the four 16-deep k-blocks c, the three planes of
 // (q * scale * log2 e)[query][16c + 8*half + j], j = 0..7
@@ -95,7 +46,7 @@ __device__ __forceinline__ void load_q_planes(const FwdParams& p, int b, int h, 
     const float4 t1 = qvalid ? ld4(qp + 16 * c + 4) : make_float4(0.f, 0.f, 0.f, 0.f);
     const float x[8] = {t0.x * qscale, t0.y * qscale, t0.z * qscale, t0.w * qscale,
                         t1.x * qscale, t1.y * qscale, t1.z * qscale, t1.w * qscale};
-    split8(x, qpl[c]);
+    split8(x, 0, qpl[c]);
   }
 }
 // S^T += K Q^T for the two 32-key halves of the tile: 2 x 4 k-blocks x 6 MFMAs
@@ -108,7 +59,7 @@ __device__ __forceinline__ void st_x6(const __bf16* Kp, const bf16x8 (&qpl)[4][3
       ka[q] = *reinterpret_cast<const bf16x8*>(&Kp[q * PLANE + ln * PSTR + 16 * c + 8 * hf]);
       kb2[q] = *reinterpret_cast<const bf16x8*>(&Kp[q * PLANE + (32 + ln) * PSTR + 16 * c + 8 * hf]);
     }
-    mfma6x2(ka, kb2, qpl[c], s0, s1);
+    mfma6x2(ka, qpl[c], s0, kb2, qpl[c], s1);
   }
 }
 // O^T += V^T P^T: 4 groups of 16 keys x 2 dim blocks x 6 MFMAs
@@ -120,14 +71,14 @@ __device__ __forceinline__ void pv_x6(const __bf16* Vt, const f32x16& s0, const 
 #pragma unroll
     for (int j = 0; j < 8; ++j) x[j] = (g < 2) ? s0[8 * (g & 1) + j] : s1[8 * (g & 1) + j];
     bf16x8 pp[3];
-    split8(x, pp);
+    split8(x, 0, pp);
     bf16x8 va[3], vb[3];
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
       va[q] = *reinterpret_cast<const bf16x8*>(&Vt[q * PLANE + ln * PSTR + 16 * g + 8 * hf]);
       vb[q] = *reinterpret_cast<const bf16x8*>(&Vt[q * PLANE + (32 + ln) * PSTR + 16 * g + 8 * hf]);
     }
-    mfma6x2(va, vb, pp, o0, o1);
+    mfma6x2(va, pp, o0, vb, pp, o1);
   }
 }
 // KEEP: the raw scores of one 64-key tile (log2 domain, before any fill), addressed as in attn_fwd.hip
@@ -481,7 +432,7 @@ __global__ __launch_bounds__(WG) void attn_split_kv_kernel(FwdParams p) {
 #pragma unroll
   for (int ps = 0; ps < 4; ++ps) {   // K: row srow + 16*ps, dims scol..scol+3
     bf16x4 pl[3];
-    split4(kst[ps].x, kst[ps].y, kst[ps].z, kst[ps].w, pl);
+    split4(kst[ps], pl);
     const int r = srow + 16 * ps;
 #pragma unroll
     for (int q = 0; q < 3; ++q) *reinterpret_cast<bf16x4*>(out + (r * 3 + q) * 64 + scol) = pl[q];
@@ -492,7 +443,7 @@ __global__ __launch_bounds__(WG) void attn_split_kv_kernel(FwdParams p) {
 #pragma unroll
   for (int dd = 0; dd < 4; ++dd) {
     bf16x4 pl[3];
-    split4(f4(vst[0], dd), f4(vst[1], dd), f4(vst[2], dd), f4(vst[3], dd), pl);
+    split4(make_float4(f4(vst[0], dd), f4(vst[1], dd), f4(vst[2], dd), f4(vst[3], dd)), pl);
 #pragma unroll
     for (int q = 0; q < 3; ++q) *reinterpret_cast<bf16x4*>(vout + ((scol + dd) * 3 + q) * 64 + vpos) = pl[q];
   }

@@ -46,8 +46,6 @@ using namespace amk_ce_common;   // TR, TA, SCAN, the limits, slices, the host d
 constexpr int BK = 16;       // contraction depth per LDS stage
 constexpr int LD = 132;      // LDS row stride (floats): 16-byte aligned rows
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 __device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 
 struct Stage { float4 v[2]; };
@@ -495,7 +493,7 @@ extern "C" int amk_ce_head_bias_fwd(const float* x, int64_t ldx, const float* w,
                                     const int64_t* target, int64_t ignore_index, int64_t M, int V, int K, float* loss, float* lse,
                                     int32_t* rows, int32_t* count, void* ws, int64_t ws_bytes, void* stream) {
   AMK_CHECK_ARG(bias, "amk_ce_head_bias_fwd: null pointer (bias)");
-  AMK_CHECK_ARG(ce_a16(bias), "amk_ce_head_bias_fwd: misaligned pointer (bias: 16 bytes)");
+  AMK_CHECK_ARG(a16(bias), "amk_ce_head_bias_fwd: misaligned pointer (bias: 16 bytes)");
   return fwd_impl<Head>("amk_ce_head_bias_fwd", x, ldx, w, ldw, target, ignore_index, M, V, K, loss, lse, rows, count, ws, ws_bytes,
                         stream, bias);
 }
@@ -513,7 +511,7 @@ extern "C" int amk_ce_head_bias_bwd(const float* x, int64_t ldx, const float* w,
                                     const float* lse, const int32_t* rows, const int32_t* count, float* dx, int64_t lddx, float* dw,
                                     int64_t lddw, float* dbias, void* ws, int64_t ws_bytes, void* stream) {
   AMK_CHECK_ARG(bias && dbias, "amk_ce_head_bias_bwd: null pointer (bias or dbias)");
-  AMK_CHECK_ARG(ce_a16(bias) && ce_a16(dbias), "amk_ce_head_bias_bwd: misaligned pointer (bias, dbias: 16 bytes)");
+  AMK_CHECK_ARG(a16(bias) && a16(dbias), "amk_ce_head_bias_bwd: misaligned pointer (bias, dbias: 16 bytes)");
   return bwd_impl<Head>("amk_ce_head_bias_bwd", x, ldx, w, ldw, target, ignore_index, M, V, K, d_loss, lse, rows, count, dx, lddx,
                         dw, lddw, ws, ws_bytes, stream, bias, dbias);
 }

@@ -14,7 +14,7 @@
 //               the workspace G (compacted row i at stride ldg = V rounded up to 128; columns V .. ldg are zeros).
 //   ce_bwd_dx : dx[rows[i], :] = sum_v G[i, v] w[v, :], f32 accumulation over ascending v, one rounding to bf16.  G has
 //               the contraction index contiguous (ds_read_b128); w has it as the memory row: staged as stored,
-//               [32 v][128 k] at a row stride of 160, fragments by ds_read_b64_tr_b16 (tr_frag of csrc/gemm_bf16.hip).
+//               [32 v][128 k] at a row stride of 160, fragments by ds_read_b64_tr_b16 (tr_frag of amk_bf16.h).
 //   ce_bwd_dw : dw[v, :] = sum_i G[i, v] x[rows[i], :], f32 accumulation over ascending i, written as f32 (what the
 //               gradient buckets hold).  Both operands have the contraction index as the memory row: both transposing.
 //   ce_zero_rows : dx rows whose target is ignore_index or outside [0, V) are written as zeros.
@@ -33,14 +33,11 @@
 // The tile loops hold no branch around a memory instruction: a piece outside the problem is loaded from a clamped
 // address and replaced by zeros with a select.  One LDS-only barrier per step: the global prefetch stays in flight.
 #include "ce_head_common.h"
+#include "amk_bf16.h"
 
 namespace amk_ce16 {
 
 using namespace amk_ce_common;   // TR, TA, the limits, slices, the host drivers
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BK = 32;       // contraction depth per LDS stage (two MFMA steps of 16)
 constexpr int FSTR = 32;     // bf16 per LDS row of a [128 rows][32 k] tile (chunk c of row r sits at c ^ ((r >> 2) & 3))
@@ -52,34 +49,12 @@ static_assert(FT >= 128 * FSTR, "the two tile shapes share one buffer");
 
 __device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 
-// barrier that orders LDS only: global loads in flight stay in flight
-__device__ __forceinline__ void lds_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
 // 16 bytes from p when ok, else zeros; the load itself is unconditional (from `safe`, always readable)
 __device__ __forceinline__ float4 ld16(const __bf16* p, const __bf16* safe, bool ok) {
   const float4 v = *reinterpret_cast<const float4*>(ok ? p : safe);
   return ok ? v : zero4();
 }
 
-__device__ __forceinline__ bf16x4 tr_read(const __bf16* p) {
-  const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p);
-  return __builtin_bit_cast(bf16x4, v);
-}
-// 32x32x16 operand whose contraction index is the ROW of the LDS tile: lane (col = c0 + (l & 31), half) gets rows
-// r0 + 8 half + (0..7)
-__device__ __forceinline__ bf16x8 tr_frag(const __bf16* img, int r0, int c0, int lane) {
-  const int hf = lane >> 5, grp = (lane >> 4) & 1, q = (lane & 15) >> 2, pp = lane & 3;
-  const __bf16* a = img + (r0 + 8 * hf + q) * STR + c0 + 16 * grp + 4 * pp;
-  const bf16x4 lo = tr_read(a), hi = tr_read(a + 4 * STR);
-  bf16x8 r;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) { r[i] = lo[i]; r[4 + i] = hi[i]; }
-  return r;
-}
 // 32x32x16 operand whose contraction index is contiguous in the LDS row: lane (row = r0 + (l & 31), half) gets
 // k = 16 s + 8 half + (0..7)   (r0 a multiple of 16: the swizzle is the lane's)
 __device__ __forceinline__ bf16x8 k_frag(const __bf16* img, int r0, int s, int ln, int hf) {
@@ -346,7 +321,7 @@ __global__ __launch_bounds__(256) void ce_bwd_dx_kernel(const __bf16* __restrict
               const bf16x8 b = k_frag(cur + FT, 32 * wave, s, ln, hf);
 #pragma unroll
               for (int blk = 0; blk < 4; ++blk)
-                acc[blk] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag(cur, 16 * s, 32 * blk, lane), b, acc[blk], 0, 0, 0);
+                acc[blk] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag<STR>(cur, 16 * s, 32 * blk, lane), b, acc[blk], 0, 0, 0);
             }
           });
   const int i = r0 + 32 * wave + ln;
@@ -409,10 +384,10 @@ __global__ __launch_bounds__(256) void ce_bwd_dw_kernel(const __bf16* __restrict
           [&](const __bf16* cur) {
 #pragma unroll
             for (int s = 0; s < BK / 16; ++s) {
-              const bf16x8 b = tr_frag(cur + FT, 16 * s, 32 * wave, lane);
+              const bf16x8 b = tr_frag<STR>(cur + FT, 16 * s, 32 * wave, lane);
 #pragma unroll
               for (int blk = 0; blk < 4; ++blk)
-                acc[blk] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag(cur, 16 * s, 32 * blk, lane), b, acc[blk], 0, 0, 0);
+                acc[blk] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag<STR>(cur, 16 * s, 32 * blk, lane), b, acc[blk], 0, 0, 0);
             }
           });
   const int k = kt0 + 32 * wave + ln;
@@ -491,7 +466,7 @@ extern "C" int amk_ce_head_bias_bf16_fwd(const void* x, int64_t ldx, const void*
                                          const int64_t* target, int64_t ignore_index, int64_t M, int V, int K, float* loss,
                                          float* lse, int32_t* rows, int32_t* count, void* ws, int64_t ws_bytes, void* stream) {
   AMK_CHECK_ARG(bias, "amk_ce_head_bias_bf16_fwd: null pointer (bias)");
-  AMK_CHECK_ARG(ce_a16(bias), "amk_ce_head_bias_bf16_fwd: misaligned pointer (bias: 16 bytes)");
+  AMK_CHECK_ARG(a16(bias), "amk_ce_head_bias_bf16_fwd: misaligned pointer (bias: 16 bytes)");
   return fwd_impl<Head>("amk_ce_head_bias_bf16_fwd", x, ldx, w, ldw, target, ignore_index, M, V, K, loss, lse, rows, count, ws,
                         ws_bytes, stream, bias);
 }
@@ -509,7 +484,7 @@ extern "C" int amk_ce_head_bias_bf16_bwd(const void* x, int64_t ldx, const void*
                                          const float* lse, const int32_t* rows, const int32_t* count, void* dx, int64_t lddx,
                                          float* dw, int64_t lddw, float* dbias, void* ws, int64_t ws_bytes, void* stream) {
   AMK_CHECK_ARG(bias && dbias, "amk_ce_head_bias_bf16_bwd: null pointer (bias or dbias)");
-  AMK_CHECK_ARG(ce_a16(bias) && ce_a16(dbias), "amk_ce_head_bias_bf16_bwd: misaligned pointer (bias, dbias: 16 bytes)");
+  AMK_CHECK_ARG(a16(bias) && a16(dbias), "amk_ce_head_bias_bf16_bwd: misaligned pointer (bias, dbias: 16 bytes)");
   return bwd_impl<Head>("amk_ce_head_bias_bf16_bwd", x, ldx, w, ldw, target, ignore_index, M, V, K, d_loss, lse, rows, count, dx,
                         lddx, dw, lddw, ws, ws_bytes, stream, bias, dbias);
 }

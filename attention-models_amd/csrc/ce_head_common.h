@@ -38,7 +38,6 @@ static void slices(int64_t M, int V, int* nsplit, int* vper) {
 
 static int64_t ldg_of(int V) { return ((int64_t)V + TA - 1) / TA * TA; }
 
-static bool ce_a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static bool ce_a4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 static bool ce_a8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 
@@ -83,7 +82,7 @@ static int fwd_impl(const char* who, const void* x, int64_t ldx, const void* w, 
   AMK_CHECK_ARG(x && w && target && loss && lse && rows && count && ws, "%s: null pointer", who);
   const int rc = check_common(who, H::MULT, ldx, ldw, M, V, K);
   if (rc != AMK_OK) return rc;
-  AMK_CHECK_ARG(ce_a16(x) && ce_a16(w) && ce_a16(ws) && ce_a8(target) && ce_a4(loss) && ce_a4(lse) && ce_a4(rows) && ce_a4(count),
+  AMK_CHECK_ARG(a16(x) && a16(w) && a16(ws) && ce_a8(target) && ce_a4(loss) && ce_a4(lse) && ce_a4(rows) && ce_a4(count),
                 "%s: misaligned pointer (x, w, ws: 16 bytes; target: 8; loss, lse, rows, count: 4)", who);
   AMK_CHECK_ARG(ws_bytes >= ce_fwd_ws_bytes(M, V, K), "%s: workspace of %lld bytes, %lld needed", who, (long long)ws_bytes,
                 (long long)ce_fwd_ws_bytes(M, V, K));
@@ -115,7 +114,7 @@ static int bwd_impl(const char* who, const void* x, int64_t ldx, const void* w, 
   AMK_CHECK_SUPPORTED(lddx % H::MULT == 0 && lddw % H::MULT == 0, "%s: lddx=%lld and lddw=%lld must be multiples of %d", who,
                       (long long)lddx, (long long)lddw, H::MULT);
   AMK_CHECK_ARG(lddx >= K && lddw >= K, "%s: a leading dimension is below K", who);
-  AMK_CHECK_ARG(ce_a16(x) && ce_a16(w) && ce_a16(dx) && ce_a16(dw) && ce_a16(ws) && ce_a8(target) && ce_a4(d_loss) && ce_a4(lse) &&
+  AMK_CHECK_ARG(a16(x) && a16(w) && a16(dx) && a16(dw) && a16(ws) && ce_a8(target) && ce_a4(d_loss) && ce_a4(lse) &&
                     ce_a4(rows) && ce_a4(count),
                 "%s: misaligned pointer (x, w, dx, dw, ws: 16 bytes; target: 8; d_loss, lse, rows, count: 4)", who);
   const int64_t need = ce_bwd_ws_bytes(M, V, K, sizeof(T));

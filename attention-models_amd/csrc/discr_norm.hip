@@ -22,7 +22,7 @@
 // the f32 arithmetic of the f32 kernels: gamma, beta, mean, rstd, the running statistics, dgamma, dbeta, the kept
 // sums, gg_gamma, gg_beta, g_gamma and every partial stay f32; y is recomputed from x in every pass and s is taken from
 // that f32 y, never from a rounded z.  SEG stays 4096 elements, so S, Q and the workspace are those of f32.
-#include "amk_common.h"
+#include "amk_bf16.h"
 
 namespace amk_bn {
 
@@ -97,8 +97,6 @@ __device__ __forceinline__ void st(float* p, const float (&v)[W]) {
   if constexpr (W == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
   else *p = v[0];
 }
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 template <int W>
 __device__ __forceinline__ void ld(const __bf16* p, float (&v)[W]) {
@@ -436,8 +434,6 @@ __global__ __launch_bounds__(BLOCK) void bwd_bwd_apply_kernel(
 }  // namespace amk_bn
 
 using namespace amk_bn;
-
-static bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 #define AMK_BN_SHAPE(what)                                                                       \
   AMK_CHECK_ARG(N > 0 && C > 0 && HW > 0, what ": non-positive size");                           \

@@ -9,10 +9,6 @@
 
 namespace amk_ew {
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
-
 __global__ __launch_bounds__(256) void swiglu_fwd_kernel(const float* __restrict__ ab, int64_t M, int H,
                                                          float* __restrict__ out) {
   const int hv = H >> 2;
@@ -94,7 +90,6 @@ __global__ __launch_bounds__(256) void geglu_bwd_kernel(const float* __restrict_
 
 using namespace amk_ew;
 
-static bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static unsigned grid_for(int64_t items) {
   const int64_t blocks = (items + 255) / 256;
   return (unsigned)(blocks < 8192 ? (blocks > 0 ? blocks : 1) : 8192);  // grid-stride beyond 32 blocks per CU

@@ -19,19 +19,16 @@
 // Partials: the backward runs at most 512 workgroups (two per CU) and each writes one (2, H) partial, so at the decoder's
 // shape (M 8192, H 4096) the partials are 16.8 MB written + 16.8 MB re-read against 335 MB of ab, dy and d_ab (10 %);
 // ln_mixed_bwd's 2048 rows would be 134 MB.
-#include "amk_common.h"
+#include "amk_bf16.h"
 
 namespace amk_gln {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int WAVES = 4;
 constexpr int MAX_PARTS = 512;
 constexpr int MAX_FWD_GRID = 2048;
 
 __device__ __forceinline__ bf16x8 ldb8(const __bf16* p) { return *reinterpret_cast<const bf16x8*>(p); }
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, const float* v) { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
+__device__ __forceinline__ void st4_array(float* p, const float* v) { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
 __device__ __forceinline__ void ld8f(const float* p, float* v) {
   const float4 a = ld4(p), b = ld4(p + 4);
   v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
@@ -41,11 +38,6 @@ __device__ __forceinline__ void stb8(__bf16* p, const float* v) {
 #pragma unroll
   for (int e = 0; e < 8; ++e) w[e] = (__bf16)v[e];
   *reinterpret_cast<bf16x8*>(p) = w;
-}
-__device__ __forceinline__ float wave_sum(float s) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
-  return s;
 }
 // Sum over the row's threads: the wave's, or the four waves' in a fixed order through `slot` (4 floats of LDS).  The
 // callers alternate slots so that one barrier per sum suffices.
@@ -201,8 +193,8 @@ __global__ __launch_bounds__(64 * WAVES) void geglu_ln_bwd_kernel(const __bf16* 
 #pragma unroll
     for (int j = 0; j < NCH; ++j)
       if (ok[j]) {
-        st4(p + col[j], dgm[j]); st4(p + col[j] + 4, dgm[j] + 4);
-        st4(p + H + col[j], dbt[j]); st4(p + H + col[j] + 4, dbt[j] + 4);
+        st4_array(p + col[j], dgm[j]); st4_array(p + col[j] + 4, dgm[j] + 4);
+        st4_array(p + H + col[j], dbt[j]); st4_array(p + H + col[j] + 4, dbt[j] + 4);
       }
   } else {         // the four waves hold four rows' worth of the same columns: sum them in wave order
 #pragma unroll
@@ -210,8 +202,8 @@ __global__ __launch_bounds__(64 * WAVES) void geglu_ln_bwd_kernel(const __bf16* 
 #pragma unroll
       for (int j = 0; j < NCH; ++j)
         if (ok[j]) {
-          st4(&acc[wave * NCH * 512 + col[j]], pass == 0 ? dgm[j] : dbt[j]);
-          st4(&acc[wave * NCH * 512 + col[j] + 4], (pass == 0 ? dgm[j] : dbt[j]) + 4);
+          st4_array(&acc[wave * NCH * 512 + col[j]], pass == 0 ? dgm[j] : dbt[j]);
+          st4_array(&acc[wave * NCH * 512 + col[j] + 4], (pass == 0 ? dgm[j] : dbt[j]) + 4);
         }
       __syncthreads();
       for (int i = threadIdx.x; i < H; i += 64 * WAVES) {
@@ -229,7 +221,6 @@ __global__ __launch_bounds__(64 * WAVES) void geglu_ln_bwd_kernel(const __bf16* 
 
 using namespace amk_gln;
 
-static bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static bool a4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 static int64_t rows_per_wg(int H) { return H <= 1024 ? WAVES : 1; }
 

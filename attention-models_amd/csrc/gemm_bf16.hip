@@ -9,14 +9,10 @@
 //   (bitwise reproducible); both operands are staged AS STORED -- [32 rows][128 columns] bf16, row stride 320 B -- and
 //   both MFMA operands (whose contraction index is the row) come from ds_read_b64_tr_b16, 4 rows x 64 B per
 //   half-wave on 64 distinct banks; db = column sums of the staged dY pieces (first k tile only).
-#include "amk_common.h"
+#include "amk_bf16.h"
 #include <stdlib.h>
 
 namespace amk_gemm16 {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int STR = 160;     // bf16 per LDS row: 128 + 32 (80 dwords = 16 mod 64: conflict-free transposing reads)
 constexpr unsigned COL_PAST = 0x40000000u;
@@ -27,37 +23,6 @@ struct Params {
   int64_t M, ldy, ldx, ldc;
   int N, K, ntk, total, nchunk, steps_per_chunk;
 };
-
-// barrier that orders LDS only: global loads and stores in flight stay in flight (__syncthreads() drains them, which
-// would serialise the register prefetch of the step loops and the row stores of the persistent kernel's epilogue)
-__device__ __forceinline__ void lds_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
-__device__ __forceinline__ f32x16 zero16() {
-  f32x16 z;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) z[i] = 0.f;
-  return z;
-}
-__device__ __forceinline__ bf16x4 tr_read(const __bf16* p) {
-  const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p);
-  return __builtin_bit_cast(bf16x4, v);
-}
-// 32x32x16 operand whose contraction index is the ROW of the LDS tile, natural order: lane (col = c0 + (l & 31), half)
-// gets rows r0 + 8 half + (0..7)
-template <int STRIDE = STR>
-__device__ __forceinline__ bf16x8 tr_frag(const __bf16* img, int r0, int c0, int lane) {
-  const int hf = lane >> 5, grp = (lane >> 4) & 1, q = (lane & 15) >> 2, pp = lane & 3;
-  const __bf16* a = img + (r0 + 8 * hf + q) * STRIDE + c0 + 16 * grp + 4 * pp;
-  const bf16x4 lo = tr_read(a), hi = tr_read(a + 4 * STRIDE);
-  bf16x8 r;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) { r[i] = lo[i]; r[4 + i] = hi[i]; }
-  return r;
-}
 
 // NWN x NWK waves of 64 x 64: tile 64 NWN (n) x 64 NWK (k); 64 rows of the contraction per step
 template <int NWN, int NWK>
@@ -325,7 +290,7 @@ __global__ __launch_bounds__(256, 4) void gemm_bf16_kernel(FParams p) {
         }
         const int sw = 8 * ((2 * s + hf) ^ ((ln >> 2) & 3));   // (row offsets 64 w + 32 i: multiples of 16, swizzle of ln)
         xf[i] = *reinterpret_cast<const bf16x8*>(&cur[(64 * wm + 32 * i + ln) * FSTR + sw]);
-        wf[i] = BTR ? tr_frag(cur + FT, 16 * s, 64 * wn + 32 * i, lane)
+        wf[i] = BTR ? tr_frag<STR>(cur + FT, 16 * s, 64 * wn + 32 * i, lane)
                     : *reinterpret_cast<const bf16x8*>(&cur[FT + (64 * wn + 32 * i + ln) * FSTR + sw]);
       }
 #pragma unroll
@@ -516,17 +481,11 @@ extern "C" int amk_gemm_tn_bf16(const void* y, int64_t ldy, const void* x, int64
   p.total = (int)total;
   hipStream_t st = static_cast<hipStream_t>(stream);
   constexpr size_t lds4 = (size_t)2 * 64 * ((128 + 32) + (128 + 32)) * 2, lds8 = (size_t)2 * 64 * ((128 + 32) + (256 + 32)) * 2;
-  // the opt-in to > 64 KiB of dynamic LDS is per device: one flag per device ordinal, and a refusal is an error here, not
-  // an opaque launch failure later
-  static bool attr_set[64] = {};
+  // the opt-in to > 64 KiB of dynamic LDS is per device: a refusal is an error here, not an opaque launch failure later
   int dev_id = 0;
   AMK_CHECK_ARG(hipGetDevice(&dev_id) == hipSuccess && dev_id >= 0 && dev_id < 64, "amk_gemm_tn_bf16: no current device");
-  if (!attr_set[dev_id]) {
-    AMK_CHECK_SUPPORTED(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_bf16_kernel<2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4) == hipSuccess &&
-                        hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_bf16_kernel<2, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds8) == hipSuccess,
-                        "amk_gemm_tn_bf16: the device refused %zu bytes of dynamic LDS", lds8);
-    attr_set[dev_id] = true;
-  }
+  AMK_CHECK_SUPPORTED((amk_lds_optin<gemm_tn_bf16_kernel<2, 2>>((int)lds4) && amk_lds_optin<gemm_tn_bf16_kernel<2, 4>>((int)lds8)),
+                      "amk_gemm_tn_bf16: the device refused %zu bytes of dynamic LDS", lds8);
   if (TK == 256) hipLaunchKernelGGL((gemm_tn_bf16_kernel<2, 4>), dim3((unsigned)total), dim3(512), lds8, st, p);
   else hipLaunchKernelGGL((gemm_tn_bf16_kernel<2, 2>), dim3((unsigned)total), dim3(256), lds4, st, p);
   if (p.nchunk > 1) {

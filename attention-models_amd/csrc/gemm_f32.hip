@@ -51,14 +51,6 @@ struct Geo {
   static_assert(BK * LSC <= BREG, "the C image must fit the operand region");
 };
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ f32x16 zero16() {
-  f32x16 z;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) z[i] = 0.f;
-  return z;
-}
 __device__ __forceinline__ float4 bload4(__amdgpu_buffer_rsrc_t r, int off) {
   return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
 }
@@ -70,14 +62,6 @@ __device__ __forceinline__ void bstore1(float v, __amdgpu_buffer_rsrc_t r, int o
 }
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t mkrsrc(const void* base, int64_t bytes) {
   return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)(bytes < 0 ? 0 : (bytes > 0x3FFFFFFF ? 0x3FFFFFFF : bytes)), 0x00020000);
-}
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
-
-// barrier that orders LDS only: the global loads in flight stay in flight (__syncthreads() would drain outstanding stores)
-__device__ __forceinline__ void lds_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
 enum { EPI_BIAS = 0, EPI_RESID = 1, EPI_SWIGLU = 2, EPI_SWIGLU_BWD = 3 };
@@ -1032,8 +1016,6 @@ __global__ __launch_bounds__(256) void row_stats_kernel(const float* __restrict_
 }  // namespace amk_dense
 
 using namespace amk_dense;
-
-static bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // Step depth of the tile loop: 16 (40 KiB of LDS, three workgroups per CU) or 32 (72 KiB, two per CU).
 // AMK_DENSE_BK overrides the default (A/B switch of tools/kbench_dense.py).

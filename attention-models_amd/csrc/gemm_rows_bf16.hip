@@ -20,11 +20,9 @@
 //     So a row's result is bitwise the same at M = 1 and in any batch.
 // The longest addition path of one element: ceil(ceil(K / 32) / 4) MFMAs of 32 products each in a wave, three additions of
 // partial tiles and the bias (tests/gemm_rows_bf16_ref.py derives the bound from it).
-#include "amk_common.h"
+#include "amk_bf16.h"
 
 namespace amk_rows {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int WAVES = 4;
 constexpr int TILE = 16;

@@ -23,37 +23,13 @@
 // the barrier window; two LDS stages with one barrier per step.  All sit at one barrier per ~768 matrix cycles
 // per wave -- the level of the guide's two-barrier bf16 structure (912 of 2500 TFLOP/s); the next step is its
 // 256 x 256 eight-phase pipeline, which needs N >= 512 to fill the chip at M = 32768.
-#include "amk_common.h"
+#include "amk_bf16.h"
 
 namespace amk_gemm {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BM = 128, BN = 128, BK = 32, NTHR = 512;
 constexpr int RS = BK + 8;            // bf16 per LDS row: 80 bytes
 constexpr int PLANE = 128 * RS;       // one plane of a 128-row tile
-
-__device__ __forceinline__ f32x16 mfmab(bf16x8 a, bf16x8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ void split1(float x, __bf16& h, __bf16& m, __bf16& l) {
-  h = (__bf16)x;
-  const float r1 = x - (float)h;
-  m = (__bf16)r1;
-  l = (__bf16)(r1 - (float)m);
-}
-
-__device__ __forceinline__ void split4(const float4& x, bf16x4 (&pl)[3]) {
-  const float v[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    __bf16 h, m, l;
-    split1(v[j], h, m, l);
-    pl[0][j] = h; pl[1][j] = m; pl[2][j] = l;
-  }
-}
 
 // planes[p][r][kp] = part p of W[r][k] (k < K), 0 for K <= kp < Kp
 __global__ __launch_bounds__(256) void split_planes_kernel(const float* __restrict__ W, int64_t ldw, int R, int K, int Kp,
@@ -79,8 +55,6 @@ struct Args {
   int M, N, K, Kp, K2, Kp2, NR;
   int64_t lda, lda2, ldc, ldg, ldab;
 };
-
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
 // EPI: X6_PLAIN     C = A B^T (+ bias)
 //      X6_GATE      B = w12 in the gate order (plane rows 128 t + j: column 64 t + j of a for j < 64, of b for j >= 64,
@@ -184,8 +158,6 @@ __global__ __launch_bounds__(NTHR, 4) void gemm_x6_nt_kernel(Args g) {
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       // six partial products per output tile, smallest first; the two tiles' chains interleave
-      constexpr int PA[6] = {1, 2, 0, 1, 0, 0};
-      constexpr int PB[6] = {1, 0, 2, 0, 1, 0};
       if constexpr (GATE) {
         bf16x8 a[3], b[2][3];
 #pragma unroll
@@ -198,7 +170,7 @@ __global__ __launch_bounds__(NTHR, 4) void gemm_x6_nt_kernel(Args g) {
 #pragma unroll
         for (int q = 0; q < 6; ++q)
 #pragma unroll
-          for (int i = 0; i < 2; ++i) acc[i] = mfmab(a[PA[q]], b[i][PB[q]], acc[i]);
+          for (int i = 0; i < 2; ++i) acc[i] = mfmab(a[x6_pa(q)], b[i][x6_pb(q)], acc[i]);
       } else {
         bf16x8 a[2][3], b[3];
 #pragma unroll
@@ -211,7 +183,7 @@ __global__ __launch_bounds__(NTHR, 4) void gemm_x6_nt_kernel(Args g) {
 #pragma unroll
         for (int q = 0; q < 6; ++q)
 #pragma unroll
-          for (int i = 0; i < 2; ++i) acc[i] = mfmab(a[i][PA[q]], b[PB[q]], acc[i]);
+          for (int i = 0; i < 2; ++i) acc[i] = mfmab(a[i][x6_pa(q)], b[x6_pb(q)], acc[i]);
       }
     }
   }

@@ -3,9 +3,8 @@
 //
 // The exact-f32 kernel for this product (gemm_tn_kernel, csrc/gemm_f32.hip) sits at 0.65 of the f32 MFMA peak and is the
 // last Linear product of the train step on the f32 matrix pipe.  Here every operand element is split into three bf16 parts
-// x = h + m + l (split4 of gemm_x6.hip, the same order) and a product is six v_mfma_f32_32x32x16_bf16 accumulated in f32,
-// smallest first as in gemm_x6_nt_kernel: (Y part, X part) = m.m, l.h, h.l, m.h, h.m, h.h -- f32-level error for 6 / 16 of
-// the f32 MFMA's matrix-pipe time.
+// x = h + m + l and a product is six v_mfma_f32_32x32x16_bf16 accumulated in f32, smallest first (the split-bf16 contract of
+// amk_bf16.h, Y the A operand) -- f32-level error for 6 / 16 of the f32 MFMA's matrix-pipe time.
 //
 // Both operands are activations, so both are split ON THE FLY between the global load and the LDS store.  The three
 // planes of each operand are staged AS STORED -- [rows of the step][columns] bf16, the padded row stride of
@@ -20,14 +19,10 @@
 // the same layout, but that kernel takes the f32 file's parameter block): bitwise reproducible.
 // Output row segments as in the f32 kernel: rows [0, split) come from y and go to c, rows [split, N) from y2 to c2 (dWq |
 // dWkv in one launch).  db = column sums of the f32 Y pieces, taken BEFORE the split by the workgroups of the first k tile.
-#include "amk_common.h"
+#include "amk_bf16.h"
 #include <stdlib.h>
 
 namespace amk_x6tn {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 constexpr unsigned COL_PAST = 0x40000000u;   // an offset past every descriptor (chunk panels are < 1 GiB): reads zeros
 
@@ -38,22 +33,10 @@ struct Params {
   int N, K, split, ntk, total, nchunk, steps_per_chunk;
 };
 
-// barrier that orders LDS only: global loads in flight stay in flight (__syncthreads() would drain the register prefetch)
-__device__ __forceinline__ void lds_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
-__device__ __forceinline__ f32x16 zero16() {
-  f32x16 z;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) z[i] = 0.f;
-  return z;
-}
-
-// x = h + m + l: split4 of gemm_x6.hip (h, m, l order)
-__device__ __forceinline__ void split4(const float4& x, bf16x4 (&pl)[3]) {
+// split4 of amk_bf16.h (the same values in the same planes) with the statements in another order: h and m are stored
+// before l is computed.  The compiler's schedule of the staging code follows the statement order, and this is the order
+// the kernel was measured with, so the variant stays here.
+__device__ __forceinline__ void split4_hm_first(const float4& x, bf16x4 (&pl)[3]) {
   const float v[4] = {x.x, x.y, x.z, x.w};
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -62,23 +45,6 @@ __device__ __forceinline__ void split4(const float4& x, bf16x4 (&pl)[3]) {
     const __bf16 m = (__bf16)r1;
     pl[0][j] = h; pl[1][j] = m; pl[2][j] = (__bf16)(r1 - (float)m);
   }
-}
-
-__device__ __forceinline__ bf16x4 tr_read(const __bf16* p) {
-  const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p);
-  return __builtin_bit_cast(bf16x4, v);
-}
-// 32x32x16 operand whose contraction index is the ROW of the LDS tile (tr_frag of gemm_bf16.hip): lane (column c0 + (l & 31),
-// half) gets rows r0 + 8 half + (0..7)
-template <int STRIDE>
-__device__ __forceinline__ bf16x8 tr_frag(const __bf16* img, int r0, int c0, int lane) {
-  const int hf = lane >> 5, grp = (lane >> 4) & 1, q = (lane & 15) >> 2, pp = lane & 3;
-  const __bf16* a = img + (r0 + 8 * hf + q) * STRIDE + c0 + 16 * grp + 4 * pp;
-  const bf16x4 lo = tr_read(a), hi = tr_read(a + 4 * STRIDE);
-  bf16x8 r;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) { r[i] = lo[i]; r[4 + i] = hi[i]; }
-  return r;
 }
 
 // NWN x NWK waves of 64 x 64: tile 64 NWN (n) x 64 NWK (k); BKM rows of the contraction per step
@@ -141,14 +107,14 @@ __global__ __launch_bounds__(64 * NWN * NWK) void gemm_x6_tn_kernel(Params p) {
       const float4 v = g.y[i];
       if (do_bias) { bsum.x += v.x; bsum.y += v.y; bsum.z += v.z; bsum.w += v.w; }   // (steps past the chunk carry zeros)
       bf16x4 pl[3];
-      split4(v, pl);
+      split4_hm_first(v, pl);
 #pragma unroll
       for (int q = 0; q < 3; ++q) *reinterpret_cast<bf16x4*>(&stage[q * YPL + (ysr + YRP * i) * YSTR + 4 * ycg]) = pl[q];
     }
 #pragma unroll
     for (int i = 0; i < XNP; ++i) {
       bf16x4 pl[3];
-      split4(g.x[i], pl);
+      split4_hm_first(g.x[i], pl);
 #pragma unroll
       for (int q = 0; q < 3; ++q) *reinterpret_cast<bf16x4*>(&stage[XT + q * XPL + (xsr + XRP * i) * XSTR + 4 * xcg]) = pl[q];
     }
@@ -181,14 +147,12 @@ __global__ __launch_bounds__(64 * NWN * NWK) void gemm_x6_tn_kernel(Params p) {
         }
       }
       // six partial products per output tile, smallest first; the four tiles' chains interleave
-      constexpr int PA[6] = {1, 2, 0, 1, 0, 0};
-      constexpr int PB[6] = {1, 0, 2, 0, 1, 0};
 #pragma unroll
       for (int q = 0; q < 6; ++q)
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-          for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][PA[q]], b[j][PB[q]], acc[i][j], 0, 0, 0);
+          for (int j = 0; j < 2; ++j) acc[i][j] = mfmab(a[i][x6_pa(q)], b[j][x6_pb(q)], acc[i][j]);
     }
     lds_barrier();
   };
@@ -350,15 +314,10 @@ extern "C" int amk_gemm_x6_tn(const float* y, int64_t ldy, const float* y2, int6
   hipStream_t st = static_cast<hipStream_t>(stream);
   constexpr size_t lds4 = (size_t)2 * 3 * 32 * ((128 + 32) + (128 + 32)) * 2, lds8 = (size_t)2 * 3 * 16 * ((128 + 32) + (256 + 32)) * 2;
   // the opt-in to > 64 KiB of dynamic LDS is per device: a refusal is an error here, not an opaque launch failure later
-  static bool attr_set[64] = {};
   int dev_id = 0;
   AMK_CHECK_ARG(hipGetDevice(&dev_id) == hipSuccess && dev_id >= 0 && dev_id < 64, "amk_gemm_x6_tn: no current device");
-  if (!attr_set[dev_id]) {
-    AMK_CHECK_SUPPORTED(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_x6_tn_kernel<2, 2, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4) == hipSuccess &&
-                        hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_x6_tn_kernel<2, 4, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds8) == hipSuccess,
-                        "amk_gemm_x6_tn: the device refused %zu bytes of dynamic LDS", lds4);
-    attr_set[dev_id] = true;
-  }
+  AMK_CHECK_SUPPORTED((amk_lds_optin<gemm_x6_tn_kernel<2, 2, 32>>((int)lds4) && amk_lds_optin<gemm_x6_tn_kernel<2, 4, 16>>((int)lds8)),
+                      "amk_gemm_x6_tn: the device refused %zu bytes of dynamic LDS", lds4);
   if (TK == 256) hipLaunchKernelGGL((gemm_x6_tn_kernel<2, 4, 16>), dim3((unsigned)total), dim3(512), lds8, st, p);
   else hipLaunchKernelGGL((gemm_x6_tn_kernel<2, 2, 32>), dim3((unsigned)total), dim3(256), lds4, st, p);
   AMK_CHECK_LAUNCH("amk_gemm_x6_tn");

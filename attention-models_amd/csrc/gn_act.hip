@@ -23,7 +23,7 @@
 // (512 x 16^2, 256 x 32^2) are one or two segments per run, latency-bound at one workgroup per CU, and halving their
 // workgroups to keep 16 KiB per segment would halve what hides that latency; at the large layers either choice fills the
 // device many times over.
-#include "amk_common.h"
+#include "amk_bf16.h"
 
 namespace amk_gn {
 
@@ -100,8 +100,6 @@ __device__ __forceinline__ void st(float* p, const float (&v)[W]) {
   if constexpr (W == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
   else *p = v[0];
 }
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 template <int W>
 __device__ __forceinline__ void ld(const __bf16* p, float (&v)[W]) {
@@ -399,8 +397,6 @@ __global__ __launch_bounds__(BLOCK) void param_grad_kernel(const float* __restri
 }  // namespace amk_gn
 
 using namespace amk_gn;
-
-static bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // The launch grid is N G S workgroups, one dimension.
 static int64_t grid_of(int N, int C, int64_t HW, int G, int VW = 4) {

@@ -15,14 +15,6 @@
 
 namespace amk_ln {
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float wave_sum(float s) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
-  return s;
-}
-
 constexpr int WAVES = 4;  // rows in flight per workgroup
 
 // NCH = 16-byte chunks per lane: D <= 256 * NCH
@@ -195,7 +187,6 @@ constexpr int MAX_PARTS = 2048;   // partial rows = workgroups of the reducing k
 
 using namespace amk_ln;
 
-static bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static int parts_for(int64_t M) {
   const int64_t wg = (M + WAVES - 1) / WAVES;
   return (int)(wg < MAX_PARTS ? (wg > 0 ? wg : 1) : MAX_PARTS);

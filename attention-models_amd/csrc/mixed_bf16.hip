@@ -9,14 +9,10 @@
 //                            h f32, y = LN(h) * gamma + beta in bf16 (its consumers are bf16 GEMMs), mean / rstd f32
 //   add_layernorm_mixed_bwd  dy bf16 or f32, h f32 -> dh f32 (+ dh_in), and a bf16 copy of dh for the bf16 branch
 // One wave per row, 4 elements per lane and chunk, two-pass statistics -- the structure of layernorm.hip.
-#include "amk_common.h"
+#include "amk_bf16.h"
 
 namespace amk_mixed {
 
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 __device__ __forceinline__ float4 ldb4(const __bf16* p) {
   const bf16x4 v = *reinterpret_cast<const bf16x4*>(p);
   return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
@@ -26,12 +22,6 @@ __device__ __forceinline__ void stb4(__bf16* p, float4 v) {
   w[0] = (__bf16)v.x; w[1] = (__bf16)v.y; w[2] = (__bf16)v.z; w[3] = (__bf16)v.w;
   *reinterpret_cast<bf16x4*>(p) = w;
 }
-__device__ __forceinline__ float wave_sum(float s) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
-  return s;
-}
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
 __global__ __launch_bounds__(256) void swiglu_bf16_fwd_kernel(const __bf16* __restrict__ ab, int64_t M, int H, __bf16* __restrict__ out) {
   const int hv = H >> 2;
@@ -202,7 +192,6 @@ __global__ __launch_bounds__(64 * WAVES) void ln_mixed_bwd_kernel(const void* __
 
 using namespace amk_mixed;
 
-static bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static bool a8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 static unsigned grid_for(int64_t items) {
   const int64_t blocks = (items + 255) / 256;

@@ -35,18 +35,7 @@
 
 namespace amk_moe {
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float f4(const float4& v, int e) {
-  return e == 0 ? v.x : (e == 1 ? v.y : (e == 2 ? v.z : v.w));
-}
 __device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ f32x16 zero16() {
-  f32x16 z;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) z[i] = 0.f;
-  return z;
-}
 
 constexpr int MAX_K = 8;
 
@@ -372,12 +361,6 @@ __device__ __forceinline__ int wave_incl_scan(int v, int lane) {
     const int t = __shfl_up(v, o, 64);
     if (lane >= o) v += t;
   }
-  return v;
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
 
@@ -1383,8 +1366,6 @@ __global__ __launch_bounds__(1024) void expert_lists_kernel(const unsigned long 
 }  // namespace amk_moe
 
 using namespace amk_moe;
-
-static bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // workgroups of the wide kernels resident at once: two per CU (LDS-bound)
 static int wg_slots() {

@@ -31,13 +31,9 @@
 // pairs, rows and columns past the end, the tail of the contraction: an offset past the range reads zeros), so the
 // tile loops have no branch around a memory instruction.  One register set is in flight beside the two LDS stages;
 // 45 KB of static LDS and at most 128 VGPRs keep two to three workgroups on a CU, which is what hides the loads.
-#include "amk_common.h"
+#include "amk_bf16.h"
 
 namespace amk_moe16 {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 constexpr unsigned PAST = 0x80000000u;   // beyond every descriptor's range (the host keeps all buffers below 2 GiB)
 constexpr int BK = 32;                   // contraction step
@@ -59,44 +55,12 @@ struct Params {
   unsigned a_bytes, x_bytes, s_bytes;
 };
 
-__device__ __forceinline__ void lds_barrier() {   // orders LDS only: global loads in flight stay in flight
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-__device__ __forceinline__ f32x16 zero16() {
-  f32x16 z;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) z[i] = 0.f;
-  return z;
-}
-__device__ __forceinline__ bf16x4 tr_read(const __bf16* p) {
-  const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p);
-  return __builtin_bit_cast(bf16x4, v);
-}
-// 32x32x16 operand whose contraction index is the ROW of the LDS image: lane (col = c0 + (l & 31), half) gets rows
-// r0 + 8 half + (0..7)
-template <int STRIDE>
-__device__ __forceinline__ bf16x8 tr_frag(const __bf16* img, int r0, int c0, int lane) {
-  const int hf = lane >> 5, grp = (lane >> 4) & 1, q = (lane & 15) >> 2, pp = lane & 3;
-  const __bf16* a = img + (r0 + 8 * hf + q) * STRIDE + c0 + 16 * grp + 4 * pp;
-  const bf16x4 lo = tr_read(a), hi = tr_read(a + 4 * STRIDE);
-  bf16x8 r;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) { r[i] = lo[i]; r[4 + i] = hi[i]; }
-  return r;
-}
 __device__ __forceinline__ int wave_incl_scan(int v, int lane) {
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) {
     const int t = __shfl_up(v, o, 64);
     if (lane >= o) v += t;
   }
-  return v;
-}
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
 __device__ __forceinline__ int div_by(int p, int d, int sh) { return sh >= 0 ? p >> sh : p / d; }

@@ -13,21 +13,12 @@
 //                           16 B written (p, 0, m, v) per element.
 // Parameters that received no gradient this step (the reference's W_d, bias1 / bias2, ...) are
 // skipped exactly as torch optimizers skip .grad None: the per-parameter table says so.
-#include "amk_common.h"
+#include "amk_bf16.h"
 
 namespace amk_opt {
 
 constexpr int NPART = 256;  // partial sums per bucket
 constexpr int SEG = 256;    // elements per segment (one wave x float4)
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-
-__device__ __forceinline__ float wave_sum(float x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-  return x;
-}
 
 // partials[w] = sum of x[i]^2 over the w-th of NPART equal ranges of whole segments
 __global__ __launch_bounds__(256) void sumsq_partials_kernel(const float* __restrict__ x, int64_t nseg, float* __restrict__ partials) {
@@ -106,7 +97,6 @@ __global__ __launch_bounds__(256) void adam_flat_kernel(AdamArgs a) {
 #undef AMK_ADAM_ONE
     st4(a.p + off, p);
     if (a.p16) {
-      typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
       bf16x4 h;
       h[0] = (__bf16)p.x; h[1] = (__bf16)p.y; h[2] = (__bf16)p.z; h[3] = (__bf16)p.w;
       *reinterpret_cast<bf16x4*>(a.p16 + off) = h;

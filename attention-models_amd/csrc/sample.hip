@@ -192,9 +192,7 @@ extern "C" int amk_sample_step(const float* logits, const float* null_logits, fl
   AMK_CHECK_SUPPORTED(R < (1ll << 31), "amk_sample_step: too many rows");
   AMK_CHECK_ARG(((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(null_logits) |
                   reinterpret_cast<uintptr_t>(gumbel)) & 15) == 0, "amk_sample_step: pointers must be 16-byte aligned");
-  static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(sample_step_kernel),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, 36864 * 4) == hipSuccess;
-  AMK_CHECK_SUPPORTED(attr_ok, "amk_sample_step: cannot reserve the LDS row buffer");
+  AMK_CHECK_SUPPORTED(amk_lds_optin<sample_step_kernel>(36864 * 4), "amk_sample_step: cannot reserve the LDS row buffer");
   Args a;
   a.logits = logits; a.null_logits = null_logits; a.gumbel = gumbel; a.mask = mask; a.ids = ids; a.scores = scores;
   a.seed = seed; a.offset = offset; a.cfg_scale = cfg_scale; a.tau = tau; a.unmasked_score = unmasked_score;

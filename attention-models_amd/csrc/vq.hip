@@ -35,12 +35,6 @@ template <int C> constexpr int codes_lds() { return C <= 64 ? 128 : (C == 128 ? 
 constexpr int FIN_ROWS = 16;   // z rows per workgroup in vq_finalize
 constexpr float EPS = 1e-12f;  // F.normalize default eps
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float f4(const float4& v, int e) {
-  return e == 0 ? v.x : (e == 1 ? v.y : (e == 2 ? v.z : v.w));
-}
-
 // ---------------------------------------------------------------------------------------
 template <int C>
 __global__ __launch_bounds__(256) void vq_prep_codebook_kernel(const float* __restrict__ E, int K, int Kpad,
@@ -466,8 +460,6 @@ extern "C" int amk_vq_padded_codes(int K, int nsplit) {
   const int q = 32 * nsplit;
   return (K + q - 1) / q * q;
 }
-
-static bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 extern "C" int amk_vq_lookup_fwd(const float* z, const float* codebook, int64_t N, int K, int C, int nsplit,
                                  float* en_ws, float* ee_ws, float* pmin_ws, int32_t* pidx_ws,

@@ -137,6 +137,12 @@ SIGNATURES = {
     "amk_gnact_bf16_ws_floats": (_L, [_I, _I, _L, _I]),
     "amk_gnact_bf16_fwd": (_I, [_P, _P, _P, _I, _I, _L, _I, _F, _I] + [_P] * 5),
     "amk_gnact_bf16_bwd": (_I, [_P] * 6 + [_I, _I, _L, _I, _I] + [_P] * 5),
+    "amk_lpips_ws_floats": (_L, [_I, _I, _L]),
+    "amk_lpips_fwd": (_I, [_P, _P, _P, _I, _I, _L, _F] + [_P] * 4),
+    "amk_lpips_bwd": (_I, [_P] * 5 + [_I, _I, _L, _F, _P, _P]),
+    "amk_lpips_bf16_ws_floats": (_L, [_I, _I, _L]),
+    "amk_lpips_bf16_fwd": (_I, [_P, _P, _P, _I, _I, _L, _F] + [_P] * 4),
+    "amk_lpips_bf16_bwd": (_I, [_P] * 5 + [_I, _I, _L, _F, _P, _P]),
     "amk_ce_head_fwd_ws_bytes": (_L, [_L, _I, _I]),
     "amk_ce_head_bwd_ws_bytes": (_L, [_L, _I, _I]),
     "amk_ce_head_fwd": (_I, [_P, _L, _P, _L, _P, _L, _L, _I, _I, _P, _P, _P, _P, _P, _L, _P]),

@@ -13,6 +13,7 @@ from .vit_moe import ViTMoE
 from .vitvqgan import Codebook, ViTVQGAN
 from . import vqgan  # the conv VQGAN's own codebook stays vqgan.Codebook (models/vqgan.py:138-182)
 from .vqgan import VQGAN
+from .lpips import LPIPS  # the GAN step's perceptual loss: not a name of the reference's package, so not in __all__ (the alias package re-exports that)
 
 __all__ = ["SoftmaxAttention", "AgentAttention", "SwitchHeadAttention", "MoELayer", "Codebook", "ViTVQGAN", "VQGAN",
            "ViT", "ViTMoE", "MUSE", "BidirectionalDecoder", "MaskGitTransformer", "BiDirectionalTransformer", "build_model",

@@ -2835,6 +2835,95 @@ def group_norm_act(x, gn, act):
     return _GNAct.apply(x, gn.weight, gn.bias, gn.num_groups, gn.eps, act)
 
 
+# ---------------------------------------------------------------------------- LPIPS distance head
+# AMK_LPIPS: "1" = the per-level distance head of amk.models.lpips.LPIPS (unit-normalise both feature tensors over the
+# channels, weight the squared difference with the level's 1x1 convolution, average over the pixels) runs on
+# csrc/lpips.hip, forward and the gradient for the first tensor: two reads of each feature tensor forward, two reads and
+# one write backward, three f32 numbers per pixel saved; "0" (default) = the torch chain (about a dozen memory-bound ops
+# per level, several feature-sized tensors kept for the backward).  f32 features outside autocast, bf16 features under bf16
+# autocast (amk_lpips_bf16_*; there the fused head returns f32 where the chain returns bf16).  Read once per process.
+# Measured per head, forward + backward, arms alternating in one process (tools/kbench_lpips.py, profiles/kbench_lpips*.log):
+# at batch 32 the five levels of a 256 px step take 1.95 ms fused against 9.04 ms in f32 (536 against 2 576 MiB above the
+# inputs at level 1) and 1.45 against 9.97 ms under bf16 autocast.  The GAN step with the term on is NOT MEASURED: the
+# step benchmark has not yet completed a run with finite losses, and the rule for this switch is a
+# win at the step level, so it ships off.
+LPIPS = os.environ.get("AMK_LPIPS", "0") != "0"
+
+
+def _lpips_chain(a, b, w, eps):
+    """The head as lpips 0.1.4 runs it: normalize_tensor on both, the squared difference, the 1x1 lin convolution,
+    spatial_average.  (N,) in the dtype torch gives it."""
+    na = torch.sqrt(torch.sum(a ** 2, dim=1, keepdim=True))
+    nb = torch.sqrt(torch.sum(b ** 2, dim=1, keepdim=True))
+    diff = (a / (na + eps) - b / (nb + eps)) ** 2
+    return torch.nn.functional.conv2d(diff, w.reshape(1, -1, 1, 1).to(diff.dtype)).mean([2, 3]).reshape(-1)
+
+
+class _LpipsDist(torch.autograd.Function):
+    """out_n of the head for f32 (outside autocast) or bf16 (under bf16 autocast) features; differentiates with respect to
+    a only.  Saves a, b, w and the three f32 rows (N, HW) the forward writes; a zero-norm pixel of a gets a zero gradient."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda")
+    def forward(ctx, a, b, w, eps):
+        N, C, HW = _bn_dims(a)
+        L = _lib.load()
+        bf = a.dtype == torch.bfloat16
+        f32 = dict(device=a.device, dtype=torch.float32)
+        out, rows = torch.empty(N, **f32), torch.empty((3, N, HW), **f32)
+        ws = torch.empty(int((L.amk_lpips_bf16_ws_floats if bf else L.amk_lpips_ws_floats)(N, C, HW)), **f32)
+        name = "amk_lpips_bf16_fwd" if bf else "amk_lpips_fwd"
+        with _timed(name[4:]):
+            _lib.check(getattr(L, name)(_ptr(a), _ptr(b), _ptr(w), N, C, HW, float(eps), _ptr(out), _ptr(rows), _ptr(ws),
+                                        _stream()), name)
+        ctx.save_for_backward(a, b, w, rows)
+        ctx.eps = float(eps)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, g):
+        a, b, w, rows = ctx.saved_tensors
+        N, C, HW = _bn_dims(a)
+        L = _lib.load()
+        g = g.to(torch.float32).contiguous()
+        ga = torch.empty_like(a)
+        name = "amk_lpips_bf16_bwd" if a.dtype == torch.bfloat16 else "amk_lpips_bwd"
+        with _timed(name[4:]):
+            _lib.check(getattr(L, name)(_ptr(g), _ptr(a), _ptr(b), _ptr(w), _ptr(rows), N, C, HW, ctx.eps, _ptr(ga),
+                                        _stream()), name)
+        return ga, None, None, None
+
+
+def lpips_distance_ok(a, b, w):
+    """True when the head can run on amk_lpips_*: the switch on; a and b contiguous 4-D HIP tensors of one shape and one
+    dtype with at least one element, f32 outside autocast or bf16 inside bf16 autocast; w f32 on the device with C elements;
+    neither b nor w requiring grad.  Everything else (CPU, f16, f32 under autocast, non-contiguous or channels-last features,
+    a b or w that requires grad, AMK_LPIPS=0) keeps the torch chain."""
+    if not (LPIPS and a.is_cuda and b.is_cuda and w.is_cuda and a.dim() == 4 and a.shape == b.shape and a.dtype == b.dtype
+            and a.is_contiguous() and b.is_contiguous() and a.numel() > 0 and w.dtype == torch.float32
+            and w.numel() == a.shape[1] and not b.requires_grad and not w.requires_grad):
+        return False
+    if a.dtype == torch.float32:
+        return not torch.is_autocast_enabled()
+    return a.dtype == torch.bfloat16 and _bf16_autocast()
+
+
+def lpips_distance(a, b, w, eps=1e-10):
+    """The LPIPS distance of one feature level, (N,): mean over the pixels of sum_c w_c (a_c / (|a| + eps) - b_c / (|b| + eps))^2,
+    |.| the norm over the channels of a pixel.  a, b (N, C, H, W), w C elements (the level's 1x1 convolution).
+
+    On the fused kernels (see lpips_distance_ok) the result is f32, also for bf16 features under bf16 autocast, where the
+    torch chain returns bf16; the gradient flows to a only, and a pixel of a whose norm is 0 gets a zero gradient where
+    autograd gives NaN.  Everything the kernels do not take runs the torch chain."""
+    if not lpips_distance_ok(a, b, w):
+        return _lpips_chain(a, b, w, eps)
+    a = a if a.data_ptr() % 16 == 0 else a.clone()
+    b = b if b.data_ptr() % 16 == 0 else b.clone()
+    return _LpipsDist.apply(a, b, w.detach().reshape(-1).contiguous(), eps)
+
+
 # ---------------------------------------------------------------------------- masked-token loss head
 # Logits + cross-entropy on the valid rows only (csrc/ce_head.hip) in place of F.linear + F.cross_entropy at the end of
 # the Muse / MaskGit train step: the (rows, vocabulary) logits, their log-softmax and their gradient are never written.

@@ -3,10 +3,13 @@ GPU, gradients reduced by amk.dp.GradReducer instead of accelerate's DDP wrap.
 
 Per step and image: 2 generator forwards + 1 generator backward (24 attention-core forwards,
 12 backwards, 2 VQ lookups, 1 VQ backward), the PatchGAN discriminator three times plus its
-gradient penalty (double backward), two Adam updates.  The LPIPS term of the reference needs
-downloaded VGG weights (unavailable offline): ``per_loss_weight`` is therefore 0 here -- the
-config key exists in the reference (cfg/vitvqgan.yaml:67) -- everything else follows the
-recipe, including the quirks (gradient-penalty norm over the channel axis only).
+gradient penalty (double backward), two Adam updates.  The LPIPS term of the reference
+(``per_loss_weight``, cfg/vitvqgan.yaml:67) is ``VQGANTrainStep(per_loss=amk.models.LPIPS(...),
+per_loss_weight=1.0)``: the module is written here from the published definition and takes the VGG
+and lin weights a user has (they are a download, so none ship); its distance heads run on
+csrc/lpips.hip.  ``per_loss`` defaults to None and the weight to 0 -- the four-term step the
+benchmark measures.  Everything else follows the recipe, including the quirks (gradient-penalty
+norm over the channel axis only).
 """
 import math
 
@@ -312,8 +315,15 @@ class VQGANTrainStep:
                  adv_loss_weight=0.1, logit_laplace_weight=1.0, max_grad_norm=1.0,
                  warmup_steps=50000, decay_steps=100000, gp_lambda=10.0, bucket_bytes=32 << 20,
                  share_forward=False, capturable=False, fused_optimizer=None, autocast=None, communicate_when_alone=False,
-                 overlap=True):
+                 overlap=True, per_loss=None, per_loss_weight=0.0):
         self.model, self.discr = model, discr
+        # per_loss: the perceptual loss module (amk.models.LPIPS), per_loss_weight its weight in the generator loss
+        # (trainers/vitgqgan.py:173-181).  Frozen and in eval mode: its parameters are in no reducer and no optimizer.
+        # None or a zero weight: the step without the term, its log keys included.
+        self.per_loss, self.per_w = per_loss, float(per_loss_weight)
+        if per_loss is not None:
+            per_loss.requires_grad_(False)
+            per_loss.eval()
         # autocast: None (f32, the parity mode) or a dtype (torch.bfloat16): the forward passes and losses of both phases
         # run inside torch.autocast as the reference's do (trainers/vitgqgan.py:149,168 `accelerator.autocast()`);
         # parameters, gradients and optimizer state stay f32
@@ -540,12 +550,19 @@ class VQGANTrainStep:
             l2 = F.mse_loss(rec, img)
             g_loss = g_nonsaturating_loss(discr(rec))
             loss = codebook_loss + self.adv_w * g_loss + self.laplace_w * l1 + l2
+            per = None
+            if self.per_loss is not None and self.per_w != 0.0:
+                per = self.per_loss(rec, img).mean()
+                loss = loss + self.per_w * per
         (loss if accum_steps == 1 else loss / accum_steps).backward()
         self.g_red.finish()
         if sync:
             self._optim_step(self.g_optim, self.g_red, model)
-        return dict(g_loss=g_loss.detach(), l1=l1.detach(), l2=l2.detach(),
+        logs = dict(g_loss=g_loss.detach(), l1=l1.detach(), l2=l2.detach(),
                     codebook_loss=codebook_loss.detach(), loss=loss.detach())
+        if per is not None:
+            logs["per_loss"] = per.detach()
+        return logs
 
     def step_body(self, img, sync=True, accum_steps=1, eta=None):
         """Everything of a step that runs on the device (no host-side schedule): what a HIP graph captures."""

@@ -894,6 +894,40 @@ int amk_gnact_bf16_bwd(const void* gz, const void* x, const float* gamma, const 
                        float* ws, void* stream);
 
 /* --------------------------------------------------------------------------
+ * LPIPS distance head on one feature level (csrc/lpips.hip), f32, contiguous NCHW a, b (N, C, HW), w (C); replaces,
+ * per level, normalize_tensor on both features, (feats0 - feats1) ** 2, the level's 1x1 NetLinLayer convolution and
+ * spatial_average of lpips 0.1.4 (LPIPS(net='vgg', lpips=True, spatial=False)), which the reference's generator loss
+ * calls at trainers/vitgqgan.py:173-181.
+ * Per sample n and pixel p: na = sqrt(sum_c a_c^2), ah_c = a_c / (na + eps), likewise nb and bh_c; e_c = ah_c - bh_c,
+ * d = sum_c w_c e_c^2, t = sum_c w_c e_c ah_c.
+ *   fwd : out_n = (1 / HW) sum_p d (N); rows (3, N, HW) for the backward: 1 / (na + eps) -- stored as 0 where
+ *         na == 0 --, 1 / (nb + eps), and t (na + eps) / na (0 where na == 0).
+ *   bwd : with g (N) the cotangent of out and k = 2 g_n / HW:  ga_c = k (w_c e_c - ah_c t (na + eps) / na) / (na + eps).
+ *         A pixel with na == 0 gets ga_c = 0 for every c, where autograd gives NaN (sqrt'(0) * 0): the one deliberate
+ *         difference; the in-place ReLU in front of every level discards what arrives at such a pixel.  No gradient
+ *         for b or w.  eps is read through the rows.
+ * Any C and HW; a, b, ga and rows 16-byte aligned, null pointers and sizes < 1 are AMK_EINVAL; a grid beyond 2^31
+ * workgroups is AMK_EUNSUPPORTED; all before any launch.  The per-workgroup sums of d go through ws
+ * (amk_lpips_ws_floats(N, C, HW) floats) and are folded per sample in a fixed order, no atomics: out and ga are bitwise
+ * reproducible, and a sample's outputs do not depend on the rest of the batch.  Two launches forward, one backward.
+ * -------------------------------------------------------------------------- */
+int64_t amk_lpips_ws_floats(int N, int C, int64_t HW);
+int amk_lpips_fwd(const float* a, const float* b, const float* w, int N, int C, int64_t HW, float eps, float* out,
+                  float* rows, float* ws, void* stream);
+int amk_lpips_bwd(const float* g, const float* a, const float* b, const float* w, const float* rows, int N, int C,
+                  int64_t HW, float eps, float* ga, void* stream);
+
+/* The same head under bf16 autocast (the same kernels on bf16 elements): a, b and ga are bf16 (const void* / void*), w, g,
+ * out, rows and ws f32.  Replaces what the chain above runs as on the convolutions' bf16 features.  a and b are widened to
+ * f32 on the load, everything between is the f32 arithmetic of amk_lpips_*, ga is rounded to bf16 once, to nearest even,
+ * on the store.  The same refusals, launches and reproducibility; ws holds amk_lpips_bf16_ws_floats(N, C, HW) floats. */
+int64_t amk_lpips_bf16_ws_floats(int N, int C, int64_t HW);
+int amk_lpips_bf16_fwd(const void* a, const void* b, const float* w, int N, int C, int64_t HW, float eps, float* out,
+                       float* rows, float* ws, void* stream);
+int amk_lpips_bf16_bwd(const float* g, const void* a, const void* b, const float* w, const float* rows, int N, int C,
+                       int64_t HW, float eps, void* ga, void* stream);
+
+/* --------------------------------------------------------------------------
  * Masked-token loss head (csrc/ce_head.hip): logits + cross-entropy on the rows that count, f32 on
  * v_mfma_f32_32x32x2_f32.  Replaces decoder.linear(...) followed by F.cross_entropy(logits.transpose(1, 2), tgt,
  * ignore_index=-1) of the reference's train steps (models/muse.py:176, models/maskgit.py:187):

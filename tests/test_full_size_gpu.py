@@ -193,6 +193,33 @@ def test_vitvqgan_config2_full_size_train_step(device):
         assert float((p.detach() - q.detach()).abs().max()) <= 1e-5 * max(1.0, float(p.detach().abs().max())) + 2.1e-4, n  # (+ 2 lr: an Adam sign flip)
 
 
+def test_vitvqgan_config2_full_size_steps_with_poisoned_allocations(device):
+    """The benchmarked workload at the benchmark's batch (32 x 256 px), two eager steps with every buffer amk allocates
+    filled with NaN first (tests/poison.py): finite losses and parameters.  Default switches and the library's default
+    convolution algorithms, so the size gates -- 2^22 scores for the split-bf16 forward and backward, 256 keys per
+    workgroup -- are taken without any forcing."""
+    import bench
+    from amk.models import ViTVQGAN
+    from amk.models.discriminator import NLayerDiscriminator
+    from amk.train import VQGANTrainStep
+    from poison import poisoned_empty
+
+    torch.manual_seed(0)
+    model = ViTVQGAN(bench.VIT, bench.CODEBOOK).to(device)
+    discr = NLayerDiscriminator(3, 64, 3).to(device)
+    imgs = torch.rand(32, 3, 256, 256, generator=torch.Generator().manual_seed(3)).to(device)
+    with poisoned_empty("nan"):
+        tr = VQGANTrainStep(model, discr, warmup_steps=1)
+        for s in range(2):
+            logs = tr.step(imgs)
+            for k, v in logs.items():
+                assert bool(torch.isfinite(v).all()), f"step {s}: {k} = {float(v)}"
+    assert set(logs) == {"g_loss", "l1", "l2", "codebook_loss", "loss", "d_loss"}
+    for mod, what in ((model, "generator"), (discr, "discriminator")):
+        for n, p in mod.named_parameters():
+            assert bool(torch.isfinite(p).all()), f"{what} {n}"
+
+
 def test_bf16_gemms_at_the_configs2_layer_shape(device):
     """The mixed-precision GEMMs (csrc/gemm_bf16.hip) at the full configs[2] layer shape (batch 32: M = 32 768 rows, the FFN's
     256 -> 2 x 1368 -> 256): size-independent properties and a float64 check of sampled rows / columns.

@@ -11,9 +11,11 @@ same run, and the peak memory above the inputs (a, b, w) during one forward + ba
 --px P: the five level shapes of a P px image instead (224: 196 pixels at the last level, no multiple of 8).
 --step: the whole GAN step (bench.py's model and discriminator) with per_loss = LPIPS() at weight 1 and the switch
 alternated: one trainer (the same initial weights) and one captured step per arm, replayed in alternating rounds; the losses
-are checked after every round and the tool stops at a non-finite one.  As it stands this flow ends that way within ten
-replays, with either value of the switch and also with --no-per-loss (the step without the perceptual term), so it has
-given no step-level figure yet; --arms, --no-per-loss and --no-conv-autotune are there to narrow that down."""
+are checked after every round and the tool stops at a non-finite one.  As it stands the two-arm flow ends that way in its
+first round, so it has given no step-level figure yet.  With one arm (--arms 0 --no-per-loss) it runs to the end with finite
+losses that are still wrong (an l1 of 12.6 next to an l2 of 0.67 on the same reconstruction), while the same model, batch
+and seed without the two tuning calls below replay cleanly: DESIGN.md section 4k.  --arms, --no-per-loss and
+--no-conv-autotune are there to narrow that down."""
 import argparse
 import copy
 import os

@@ -98,6 +98,9 @@ SIGNATURES = {
     "amk_attn_bf16_fwd": (_I, [_P] * 7 + [_I] * 5 + [_L] * 12 + [_F, _P]),
     "amk_attn_bf16_bwd_ws_floats": (_L, [_I, _I, _I, _I]),
     "amk_attn_bf16_bwd": (_I, [_P] * 12 + [_I] * 5 + [_L] * 24 + [_F, _P]),
+    "amk_attn_bf16_hd_fwd": (_I, [_P] * 7 + [_I] * 5 + [_L] * 12 + [_F, _P]),
+    "amk_attn_bf16_hd_bwd_ws_floats": (_L, [_I, _I, _I, _I, _I]),
+    "amk_attn_bf16_hd_bwd": (_I, [_P] * 12 + [_I] * 5 + [_L] * 24 + [_F, _P]),
     "amk_swiglu_bf16_fwd": (_I, [_P, _L, _I, _P, _P]),
     "amk_swiglu_bf16_bwd": (_I, [_P, _P, _L, _I, _P, _P]),
     "amk_add_layernorm_mixed_fwd": (_I, [_P, _I, _P, _P, _P, _L, _I, _F, _P, _P, _P, _P, _P]),

@@ -395,16 +395,38 @@ class _AttnFusedKV(torch.autograd.Function):
 ATTENTION_BF16 = os.environ.get("AMK_ATTENTION_BF16", "1") == "1"
 
 
+def _parse_bf16_dims(text):
+    """AMK_ATTENTION_BF16_DIMS: a comma list out of 32, 64, 128 -> frozenset of ints."""
+    dims = set()
+    for part in text.split(","):
+        part = part.strip()
+        if part not in ("32", "64", "128"):
+            raise ValueError(f"AMK_ATTENTION_BF16_DIMS={text!r}: a comma list out of 32, 64, 128 (got {part!r})")
+        dims.add(int(part))
+    return frozenset(dims)
+
+
+# Head dims whose bf16 projections take the bf16-MFMA core under ATTENTION_BF16: 64 on csrc/attn_bf16.hip, 32 and 128 on
+# csrc/attn_bf16_hd.hip (opt-in: AMK_ATTENTION_BF16_DIMS=32,64,128).  A head dim outside the set takes the exact-f32
+# kernels on upcast inputs.  Read once per process.
+ATTENTION_BF16_DIMS = _parse_bf16_dims(os.environ.get("AMK_ATTENTION_BF16_DIMS", "64"))
+
+
 class _AttnFusedKVBF16(torch.autograd.Function):
-    """_AttnFusedKV on bf16 tensors: q2 (B,I,h*64), kv2 (B,J,2*h*64) bf16 -> (B,I,h*64) bf16."""
+    """_AttnFusedKV on bf16 tensors: q2 (B,I,h*d), kv2 (B,J,2*h*d) bf16 -> (B,I,h*d) bf16.  dim_head 64 (the default)
+    runs on amk_attn_bf16_fwd / _bwd, 32 and 128 on amk_attn_bf16_hd_fwd / _bwd."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda")
-    def forward(ctx, q2, kv2, H, scale, key_mask=None, causal_mask=None):
+    def forward(ctx, q2, kv2, H, scale, key_mask=None, causal_mask=None, dim_head=64):
         """key_mask: uint8 (B, J), 1 = keep; causal_mask: uint8 (I, J), 1 = masked (see _mask_u8); or None."""
         B, I, _ = q2.shape
         J = kv2.shape[1]
-        D = 64
+        D = int(dim_head)
+        if D not in (32, 64, 128) or q2.shape[2] != H * D or kv2.shape[2] != 2 * H * D:
+            raise RuntimeError(f"bf16 attention: q {tuple(q2.shape)} / kv {tuple(kv2.shape)} do not fit heads={H}, "
+                               f"dim_head={D} (dim_head 32, 64 or 128)")
+        hd = "_hd" if D != 64 else ""
         q2 = q2.contiguous()
         kv2 = kv2.contiguous()
         o2 = torch.empty((B, I, H * D), device=q2.device, dtype=torch.bfloat16)
@@ -412,13 +434,14 @@ class _AttnFusedKVBF16(torch.autograd.Function):
         L = _lib.load()
         qs, kvs = (I * H * D, H * D, D), (J * 2 * H * D, 2 * H * D, D)
         masked = key_mask is not None or causal_mask is not None
-        with _timed("attn_bf16_fwd_kernel<masked>" if masked else "attn_bf16_fwd_kernel"):
-            rc = L.amk_attn_bf16_fwd(_ptr(q2), _ptr(kv2), ctypes.c_void_p(kv2.data_ptr() + 2 * H * D), _ptr(o2), _ptr(stats),
-                                     _ptr(key_mask), _ptr(causal_mask),
-                                     B, H, I, J, D, *qs, *kvs, *kvs, *qs, float(scale), _stream())
-        _lib.check(rc, "amk_attn_bf16_fwd")
+        fwd = L.amk_attn_bf16_hd_fwd if hd else L.amk_attn_bf16_fwd
+        with _timed(f"attn_bf16{hd}_fwd_kernel<masked>" if masked else f"attn_bf16{hd}_fwd_kernel"):
+            rc = fwd(_ptr(q2), _ptr(kv2), ctypes.c_void_p(kv2.data_ptr() + 2 * H * D), _ptr(o2), _ptr(stats),
+                     _ptr(key_mask), _ptr(causal_mask),
+                     B, H, I, J, D, *qs, *kvs, *kvs, *qs, float(scale), _stream())
+        _lib.check(rc, f"amk_attn_bf16{hd}_fwd")
         ctx.save_for_backward(q2, kv2, o2, stats, key_mask, causal_mask)
-        ctx.cfg = (H, scale)
+        ctx.cfg = (H, scale, D)
         return o2
 
     @staticmethod
@@ -426,24 +449,26 @@ class _AttnFusedKVBF16(torch.autograd.Function):
     @_amp_bwd
     def backward(ctx, d_o2):
         q2, kv2, o2, stats, key_mask, causal_mask = ctx.saved_tensors
-        H, scale = ctx.cfg
+        H, scale, D = ctx.cfg
         B, I, _ = q2.shape
         J = kv2.shape[1]
-        D = 64
+        hd = "_hd" if D != 64 else ""
         d_o2 = d_o2.to(torch.bfloat16).contiguous()
         dq2 = torch.empty_like(q2)
         dkv2 = torch.empty_like(kv2)
         L = _lib.load()
-        ws = torch.empty((L.amk_attn_bf16_bwd_ws_floats(B, H, I, J),), device=q2.device, dtype=torch.float32)
+        ws_floats = L.amk_attn_bf16_hd_bwd_ws_floats(B, H, I, J, D) if hd else L.amk_attn_bf16_bwd_ws_floats(B, H, I, J)
+        ws = torch.empty((ws_floats,), device=q2.device, dtype=torch.float32)
         qs, kvs = (I * H * D, H * D, D), (J * 2 * H * D, 2 * H * D, D)
         masked = key_mask is not None or causal_mask is not None
-        with _timed("attn_bf16_bwd_kernel<masked>" if masked else "attn_bf16_bwd_kernel"):
-            rc = L.amk_attn_bf16_bwd(_ptr(q2), _ptr(kv2), ctypes.c_void_p(kv2.data_ptr() + 2 * H * D), _ptr(o2), _ptr(stats), _ptr(d_o2),
-                                     _ptr(dq2), _ptr(dkv2), ctypes.c_void_p(dkv2.data_ptr() + 2 * H * D), _ptr(ws),
-                                     _ptr(key_mask), _ptr(causal_mask),
-                                     B, H, I, J, D, *qs, *kvs, *kvs, *qs, *qs, *qs, *kvs, *kvs, float(scale), _stream())
-        _lib.check(rc, "amk_attn_bf16_bwd")
-        return dq2, dkv2, None, None, None, None
+        bwd = L.amk_attn_bf16_hd_bwd if hd else L.amk_attn_bf16_bwd
+        with _timed(f"attn_bf16{hd}_bwd_kernel<masked>" if masked else f"attn_bf16{hd}_bwd_kernel"):
+            rc = bwd(_ptr(q2), _ptr(kv2), ctypes.c_void_p(kv2.data_ptr() + 2 * H * D), _ptr(o2), _ptr(stats), _ptr(d_o2),
+                     _ptr(dq2), _ptr(dkv2), ctypes.c_void_p(dkv2.data_ptr() + 2 * H * D), _ptr(ws),
+                     _ptr(key_mask), _ptr(causal_mask),
+                     B, H, I, J, D, *qs, *kvs, *kvs, *qs, *qs, *qs, *kvs, *kvs, float(scale), _stream())
+        _lib.check(rc, f"amk_attn_bf16{hd}_bwd")
+        return dq2, dkv2, None, None, None, None, None
 
 
 def attention(q, k, v, scale, key_mask=None, causal_mask=None):
@@ -465,8 +490,8 @@ def attention_fused_kv(q2, kv2, num_heads, dim_head, scale, key_mask=None, causa
     J = kv2.shape[1]
     km = _mask_u8(key_mask, (B, J), "context_mask")
     cm = _mask_u8(causal_mask, (I, J), "causal_mask")
-    if ATTENTION_BF16 and q2.dtype == torch.bfloat16 and kv2.dtype == torch.bfloat16 and q2.is_cuda and dim_head == 64:
-        return _AttnFusedKVBF16.apply(q2, kv2, num_heads, scale, km, cm)
+    if ATTENTION_BF16 and q2.dtype == torch.bfloat16 and kv2.dtype == torch.bfloat16 and q2.is_cuda and dim_head in ATTENTION_BF16_DIMS:
+        return _AttnFusedKVBF16.apply(q2, kv2, num_heads, scale, km, cm, dim_head)
     return _AttnFusedKV.apply(q2, kv2, km, cm, num_heads, dim_head, scale)
 
 

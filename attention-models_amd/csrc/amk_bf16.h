@@ -46,6 +46,46 @@ __device__ __forceinline__ bf16x8 tr_frag_packed(const __bf16* img, int t, int c
   return r;
 }
 
+// ---- helpers of the bf16 attention kernels (attn_bf16.hip, attn_bf16_hd.hip) -----------------------------------
+typedef float f32x4v __attribute__((ext_vector_type(4)));
+
+// a * b - c with two roundings.  HIP contracts a plain a * b - c into one FMA (__fmul_rn / __fsub_rn included: they are
+// a * b and a - b), and an FMA leaves the rounding error of c = m * c2 in the exponent -- up to +-64 at the fill value's
+// 1.4e9, so a fully masked row lost its uniform weights (and overflowed to NaN over a long row of rescales)
+__device__ __forceinline__ float mul_sub_rn(float a, float b, float c) {
+#pragma clang fp contract(off)
+  return a * b - c;
+}
+// v_max3_f32 (in files built with -fno-honor-nans -mno-amdgpu-ieee, see the Makefile: no canonicalising v_max in front)
+__device__ __forceinline__ float max3(float a, float b, float c) { return __builtin_fmaxf(__builtin_fmaxf(a, b), c); }
+
+__device__ __forceinline__ bf16x8 cat4(bf16x4 a, bf16x4 b) {
+  bf16x8 r;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) { r[i] = a[i]; r[4 + i] = b[i]; }
+  return r;
+}
+// registers 8t .. 8t+7 of a 32x32 accumulator as the 8 bf16 of a k-slot (the B operand of a product that sums over
+// the accumulator's rows)
+__device__ __forceinline__ bf16x8 pack8(const f32x16& s, int t) {
+  bf16x8 r;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) r[j] = (__bf16)s[8 * t + j];
+  return r;
+}
+
+// v_mfma_f32_16x16x32_bf16: D(16x16) += A(16x32) * B(32x16); lane l supplies A[l & 15][8 (l >> 4) + (0..7)] and
+// B[8 (l >> 4) + (0..7)][l & 15], accumulator register r of lane l is D[4 (l >> 4) + r][l & 15]
+__device__ __forceinline__ f32x4v mfma16(bf16x8 a, bf16x8 b, f32x4v c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+
+// 16x16x32 operand out of an LDS tile X [row][col] by transposing reads, for a product that sums over X's ROWS in
+// natural order: lane (col = c0 + (l & 15), kq = l >> 4) gets rows r0 + 8 kq + (0..7)
+__device__ __forceinline__ bf16x8 tr_frag16(const __bf16* img, int stride, int r0, int c0, int lane) {
+  const int kq = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
+  const __bf16* a = img + (r0 + 8 * kq + q) * stride + c0 + 4 * pp;
+  return cat4(tr_read(a), tr_read(a + 4 * stride));
+}
+
 // ---- the split-bf16 contract ------------------------------------------------------------------------------------
 // An f32 x is three bf16 parts, x = h + m + l: h = bf16(x), m = bf16(x - h), l = bf16((x - h) - m), every conversion
 // round-to-nearest-even and every residual exact in f32 (24 mantissa bits in all).  Planes are indexed 0 = h, 1 = m,

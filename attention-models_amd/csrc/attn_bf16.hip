@@ -24,58 +24,19 @@
 // ([key][query] image) and dQ(32 x 64) = dS K over the workgroup's 256 keys runs on v_mfma_f32_16x16x32_bf16, one
 // 16x16 output tile per wave.  dQ leaves as per-key-block f32 partials (plain stores) that a second launch sums in
 // key-block order and rounds to bf16: no atomics, bitwise reproducible.
+// Head dims 32 and 128: the same two designs with the head dim as a template argument, csrc/attn_bf16_hd.hip.
 #include "attn_common.h"
 #include "amk_bf16.h"
 
 namespace amk_attn_bf16 {
 
 using amk_attn::Strides;
-
-typedef float f32x4v __attribute__((ext_vector_type(4)));
+using amk_attn::vmax;
+using amk_attn::f32x2;
 
 constexpr int KSTR = 72;   // bf16 per row of a row-read image (64 + 8): 144 B
 constexpr int TSTR = 96;   // bf16 per row of a transposed-read image (64 + 32): 192 B
 
-struct Params {
-  const __bf16 *q, *k, *v, *o, *d_o;
-  __bf16 *out, *dq, *dk, *dv;
-  float* stats;        // (B, H, I, 2): row max in the log2 domain, row sum
-  float* delta;        // (B, H, I) x 4: the backward row constants {-(m + log2 l) / c2, -rowsum(dO * O), m, 1 / l}
-  const uint8_t *key_mask, *causal_mask;   // (B, J) 1 = keep; (I, J) 1 = masked; or null
-  float* dq_part;      // (nkblk, B, I, H, 64) f32
-  int B, H, I, J;
-  Strides qs, ks, vs, os, dos, dqs, dks, dvs;
-  float scale;
-  float pinf;
-  int nqblk, nkblk;
-};
-
-__device__ __forceinline__ float vmax(float a, float b, float pinf) { return __builtin_amdgcn_fmed3f(a, b, pinf); }
-// a * b - c with two roundings.  HIP contracts a plain a * b - c into one FMA (__fmul_rn / __fsub_rn included: they are
-// a * b and a - b), and an FMA leaves the rounding error of c = m * c2 in the exponent -- up to +-64 at the fill value's
-// 1.4e9, so a fully masked row lost its uniform weights (and overflowed to NaN over a long row of rescales)
-__device__ __forceinline__ float mul_sub_rn(float a, float b, float c) {
-#pragma clang fp contract(off)
-  return a * b - c;
-}
-// v_max3_f32 (this file is built with -fno-honor-nans -mno-amdgpu-ieee, see the Makefile: no canonicalising v_max in front)
-__device__ __forceinline__ float max3(float a, float b, float c) { return __builtin_fmaxf(__builtin_fmaxf(a, b), c); }
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ bf16x8 cat4(bf16x4 a, bf16x4 b) {
-  bf16x8 r;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) { r[i] = a[i]; r[4 + i] = b[i]; }
-  return r;
-}
-// registers 8t .. 8t+7 of a 32x32 accumulator as the 8 bf16 of a k-slot (the B operand of a product that sums over
-// the accumulator's rows)
-__device__ __forceinline__ bf16x8 pack8(const f32x16& s, int t) {
-  bf16x8 r;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = (__bf16)s[8 * t + j];
-  return r;
-}
 // ---------------------------------------------------------------------------------------------------------------
 template <bool MASKED>
 __global__ __launch_bounds__(256, 2) void attn_bf16_fwd_kernel(Params p) {
@@ -328,16 +289,6 @@ __global__ __launch_bounds__(256) void attn_bf16_delta_kernel(Params p) {
 constexpr int BW = 8;            // waves per backward workgroup
 constexpr int BKEYS = 32 * BW;   // keys per workgroup
 constexpr int DSTR = 48;         // bf16 per row of the dS^T image [key][32 queries]
-
-__device__ __forceinline__ f32x4v mfma16(bf16x8 a, bf16x8 b, f32x4v c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-
-// 16x16x32 operand out of an LDS tile X [row][col] by transposing reads, for a product that sums over X's ROWS in
-// natural order: lane (col = c0 + (l & 15), kq = l >> 4) gets rows r0 + 8 kq + (0..7)
-__device__ __forceinline__ bf16x8 tr_frag16(const __bf16* img, int stride, int r0, int c0, int lane) {
-  const int kq = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
-  const __bf16* a = img + (r0 + 8 * kq + q) * stride + c0 + 4 * pp;
-  return cat4(tr_read(a), tr_read(a + 4 * stride));
-}
 
 template <bool MASKED, bool CAUSAL>
 __global__ __launch_bounds__(64 * BW, 1) void attn_bf16_bwd_kernel(Params p) {
@@ -596,8 +547,7 @@ __global__ __launch_bounds__(256) void attn_bf16_dq_reduce_kernel(Params p) {
 
 using namespace amk_attn_bf16;
 
-static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static bool st_ok(const Strides& s) { return s.sb % 8 == 0 && s.st % 8 == 0 && s.sh % 8 == 0; }
+using amk_attn::strides_ok8;
 
 extern "C" int amk_attn_bf16_fwd(const void* q, const void* k, const void* v, void* o, float* stats,
                                  const uint8_t* key_mask, const uint8_t* causal_mask,
@@ -615,7 +565,7 @@ extern "C" int amk_attn_bf16_fwd(const void* q, const void* k, const void* v, vo
   p.qs = {q_sb, q_st, q_sh}; p.ks = {k_sb, k_st, k_sh}; p.vs = {v_sb, v_st, v_sh}; p.os = {o_sb, o_st, o_sh};
   p.scale = scale; p.pinf = INFINITY;
   p.nqblk = (I + 127) / 128;
-  AMK_CHECK_ARG(al16(q) && al16(k) && al16(v) && al16(o) && st_ok(p.qs) && st_ok(p.ks) && st_ok(p.vs) && st_ok(p.os),
+  AMK_CHECK_ARG(a16(q) && a16(k) && a16(v) && a16(o) && strides_ok8(p.qs) && strides_ok8(p.ks) && strides_ok8(p.vs) && strides_ok8(p.os),
                 "amk_attn_bf16_fwd: pointers must be 16-byte aligned and strides multiples of 8 elements");
   const int64_t nwg = (int64_t)B * H * p.nqblk;
   AMK_CHECK_SUPPORTED(nwg < (1ll << 31), "amk_attn_bf16_fwd: grid too large");
@@ -659,8 +609,8 @@ extern "C" int amk_attn_bf16_bwd(const void* q, const void* k, const void* v, co
   p.nkblk = (J + BKEYS - 1) / BKEYS;
   p.delta = ws;
   p.dq_part = ws + 4 * (int64_t)B * H * I;
-  AMK_CHECK_ARG(al16(q) && al16(k) && al16(v) && al16(o) && al16(d_o) && al16(dq) && al16(dk) && al16(dv) && al16(p.dq_part) &&
-                    st_ok(p.qs) && st_ok(p.ks) && st_ok(p.vs) && st_ok(p.os) && st_ok(p.dos) && st_ok(p.dqs) && st_ok(p.dks) && st_ok(p.dvs),
+  AMK_CHECK_ARG(a16(q) && a16(k) && a16(v) && a16(o) && a16(d_o) && a16(dq) && a16(dk) && a16(dv) && a16(p.dq_part) &&
+                    strides_ok8(p.qs) && strides_ok8(p.ks) && strides_ok8(p.vs) && strides_ok8(p.os) && strides_ok8(p.dos) && strides_ok8(p.dqs) && strides_ok8(p.dks) && strides_ok8(p.dvs),
                 "amk_attn_bf16_bwd: pointers must be 16-byte aligned and strides multiples of 8 elements");
   AMK_CHECK_SUPPORTED(((int64_t)J + BKEYS) * k_st * 2 < (1ll << 31) && ((int64_t)J + BKEYS) * v_st * 2 < (1ll << 31) &&
                           ((int64_t)I + 32) * q_st * 2 < (1ll << 31) && ((int64_t)I + 32) * do_st * 2 < (1ll << 31),

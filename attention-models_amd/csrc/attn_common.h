@@ -109,6 +109,8 @@ typedef RowStagerT<TILE> RowStager;
 // what the f32 entry points ask of every tensor: float4 accesses
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline bool strides_ok(const Strides& s) { return (s.sb % 4 == 0) && (s.st % 4 == 0) && (s.sh % 4 == 0); }
+// and the bf16 entry points: 16-byte accesses of 8 elements
+inline bool strides_ok8(const Strides& s) { return (s.sb % 8 == 0) && (s.st % 8 == 0) && (s.sh % 8 == 0); }
 
 // attn_fwd_x6.hip: the forward with split-bf16 products (pre-pass + kernel; p.scores non-null: scores kept).
 // plain: unmasked calls may take the unmasked specialisation
@@ -129,3 +131,20 @@ void launch_attn_fwd_gen(const FwdParams& p, int Dh, int64_t nwg, hipStream_t st
 void launch_attn_bwd_gen(const BwdParams& p, int Dh, int stages, hipStream_t st);
 
 }  // namespace amk_attn
+
+// attn_bf16.hip, attn_bf16_hd.hip: the parameter block of the bf16-MFMA kernels (Dh: the head dim they are built for)
+namespace amk_attn_bf16 {
+struct Params {
+  const __bf16 *q, *k, *v, *o, *d_o;
+  __bf16 *out, *dq, *dk, *dv;
+  float* stats;        // (B, H, I, 2): row max in the log2 domain, row sum
+  float* delta;        // (B, H, I) x 4: the backward row constants {-(m + log2 l) / c2, -rowsum(dO * O), m, 1 / l}
+  const uint8_t *key_mask, *causal_mask;   // (B, J) 1 = keep; (I, J) 1 = masked; or null
+  float* dq_part;      // (nkblk, B, I, H, Dh) f32
+  int B, H, I, J;
+  amk_attn::Strides qs, ks, vs, os, dos, dqs, dks, dvs;
+  float scale;
+  float pinf;
+  int nqblk, nkblk;
+};
+}  // namespace amk_attn_bf16

@@ -741,6 +741,29 @@ int amk_attn_bf16_bwd(const void* q, const void* k, const void* v, const void* o
                       int64_t dk_sb, int64_t dk_st, int64_t dk_sh, int64_t dv_sb, int64_t dv_st, int64_t dv_sh,
                       float scale, void* stream);
 
+/* The same two kernels for head dims 32 and 128 (models/softmax_attention.py:62-76 under bf16 autocast at the head dims
+ * a user who changes d_head picks first; csrc/attn_bf16_hd.hip: the head dim is a template argument; 256 keys per
+ * backward workgroup at head dim 32, 128 at head dim 128).  Arguments, masks, alignment rules, statistics and error codes as amk_attn_bf16_fwd / _bwd; the
+ * workspace size takes the head dim.  D must be 32 or 128: anything else is AMK_EUNSUPPORTED (0 floats from
+ * amk_attn_bf16_hd_bwd_ws_floats) -- head dim 64 runs on amk_attn_bf16_fwd / _bwd.  Argument errors are AMK_EINVAL
+ * with nothing launched. */
+int amk_attn_bf16_hd_fwd(const void* q, const void* k, const void* v, void* o, float* stats,
+                         const uint8_t* key_mask, const uint8_t* causal_mask,
+                         int B, int H, int I, int J, int D,
+                         int64_t q_sb, int64_t q_st, int64_t q_sh, int64_t k_sb, int64_t k_st, int64_t k_sh,
+                         int64_t v_sb, int64_t v_st, int64_t v_sh, int64_t o_sb, int64_t o_st, int64_t o_sh,
+                         float scale, void* stream);
+int64_t amk_attn_bf16_hd_bwd_ws_floats(int B, int H, int I, int J, int D);
+int amk_attn_bf16_hd_bwd(const void* q, const void* k, const void* v, const void* o, const float* stats, const void* d_o,
+                         void* dq, void* dk, void* dv, float* ws,
+                         const uint8_t* key_mask, const uint8_t* causal_mask,
+                         int B, int H, int I, int J, int D,
+                         int64_t q_sb, int64_t q_st, int64_t q_sh, int64_t k_sb, int64_t k_st, int64_t k_sh,
+                         int64_t v_sb, int64_t v_st, int64_t v_sh, int64_t o_sb, int64_t o_st, int64_t o_sh,
+                         int64_t do_sb, int64_t do_st, int64_t do_sh, int64_t dq_sb, int64_t dq_st, int64_t dq_sh,
+                         int64_t dk_sb, int64_t dk_st, int64_t dk_sh, int64_t dv_sb, int64_t dv_st, int64_t dv_sh,
+                         float scale, void* stream);
+
 /* --------------------------------------------------------------------------
  * Element-wise passes of the mixed-precision (bf16 autocast) mode: the ops of amk_swiglu_* / amk_add_layernorm_*
  * (models/vitvqgan.py:20-61) reading and writing bf16 where the neighbouring GEMM is a bf16 GEMM, so that no separate

@@ -784,7 +784,10 @@ def sample_step(logits, ids, mask=None, null_logits=None, cfg_scale=3.0, tau=1.0
     returns scores (B, T).  gumbel: explicit noise (B, T, V) -- else drawn in-kernel: Philox4x32-10 keyed by the seed
     and stream offset of torch's CUDA generator (`generator`, default the device's), which is advanced by the call, so
     torch.manual_seed reproduces a run; an explicit `seed` uses this module's call counter as the offset instead.
-    Ties at the keep-th largest logit: every logit >= that value is kept (the reference's topk keeps exactly k)."""
+    Ties at the keep-th largest logit: every logit >= that value is kept (the reference's topk keeps exactly k);
+    -0.0 and +0.0 are one value there, as for torch.topk (the kernel stores the scaled logit as x + 0.0).
+    In-kernel noise: word w of the stream gives u = ((w >> 9) + 0.5) 2^-23, strictly inside (0, 1), and
+    g = -log(-log u), always finite."""
     import math
 
     global _SAMPLE_CALLS

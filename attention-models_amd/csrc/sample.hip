@@ -6,7 +6,7 @@
 // by the temperature, another softmax, an argmax, a gather of the chosen probability and two masked
 // writes -- a dozen HBM passes over 33.5 MB per image.  Here a workgroup owns one (b, t) row:
 //
-//   s_j   = null_j + scale (l_j - null_j)              (or l_j without guidance), kept in LDS
+//   s_j   = null_j + scale (l_j - null_j)              (or l_j without guidance), kept in LDS; -0.0 is stored as +0.0
 //   m, Z  = max_j s_j, sum_j exp(s_j - m)              (the softmax the score is read from)
 //   thr   = the keep-th largest s_j                    (radix select on order-preserving keys, LDS histograms)
 //   pred  = argmax_{j : s_j >= thr} (s_j + g_j)        (= argmax softmax((filtered + g) / tau) for tau > 0;
@@ -50,7 +50,9 @@ __device__ __forceinline__ void philox4(uint64_t seed, uint64_t ctr_hi, uint64_t
 }
 
 __device__ __forceinline__ float gumbel_of(uint32_t bits) {
-  const float u = ((float)(bits >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0, 1)
+  // 23 bits: (bits >> 9) + 0.5 <= 8388607.5 is an f32 and the product is exact, so u lies in [2^-24, 1 - 2^-24].  (With
+  // 24 bits 16777215.5 rounds to 2^24: u = 1, -log u = 0 and g = +inf -- one word in 2^24 won whatever its logit.)
+  const float u = ((float)(bits >> 9) + 0.5f) * (1.0f / 8388608.0f);
   return -__logf(-__logf(u));
 }
 
@@ -86,6 +88,9 @@ __global__ __launch_bounds__(256) void sample_step_kernel(Args a) {
       x.x = n.x + a.cfg_scale * (x.x - n.x); x.y = n.y + a.cfg_scale * (x.y - n.y);
       x.z = n.z + a.cfg_scale * (x.z - n.z); x.w = n.w + a.cfg_scale * (x.w - n.w);
     }
+    // -0.0 + 0.0 = +0.0: one zero in LDS, so that key_of orders no zero below another ("every logit >= the keep-th
+    // largest is kept" holds for -0.0 against a threshold of +0.0, as torch.topk treats them)
+    x.x += 0.0f; x.y += 0.0f; x.z += 0.0f; x.w += 0.0f;
     *reinterpret_cast<float4*>(sv + j) = x;
     mx = fmaxf(fmaxf(mx, fmaxf(x.x, x.y)), fmaxf(x.z, x.w));
   }

@@ -490,14 +490,15 @@ static int vq_bwd_impl(const char* who, const float* z, const float* codebook, c
   AMK_CHECK_ARG(N > 0 && K > 0, "%s: non-positive size", who);
   AMK_CHECK_SUPPORTED(C == 32 || C == 64 || C == 128 || C == 256, "%s: codebook_dim %d not supported (32, 64, 128, 256)", who, C);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (!ge_rows && hipMemsetAsync(dcodebook, 0, (size_t)K * C * sizeof(float), st) != hipSuccess) {
-    amk_set_error("%s: hipMemsetAsync failed", who);
-    return AMK_ELAUNCH;
-  }
   const int rpb = C <= 64 ? 256 / C : 256 / (C / 4);
   const int64_t nb = (N + rpb - 1) / rpb;
   AMK_CHECK_SUPPORTED(nb < (1ll << 31), "%s: grid too large", who);
   AMK_CHECK_ARG(C <= 64 || (a16(z) && a16(codebook) && a16(zn) && a16(zq) && a16(g_out) && a16(dz)), "%s: pointers must be 16-byte aligned", who);
+  // (after every refusal: a refused call leaves the codebook gradient untouched)
+  if (!ge_rows && hipMemsetAsync(dcodebook, 0, (size_t)K * C * sizeof(float), st) != hipSuccess) {
+    amk_set_error("%s: hipMemsetAsync failed", who);
+    return AMK_ELAUNCH;
+  }
   if (C == 32)
     hipLaunchKernelGGL(vq_bwd_kernel<32>, dim3((unsigned)nb), dim3(256), 0, st, z, codebook, zn, zq, idx, g_out, g_loss, beta, N, K, dz, dcodebook, ge_rows);
   else if (C == 64)

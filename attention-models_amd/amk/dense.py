@@ -256,6 +256,18 @@ def gemm_x6_nt(a, planes, N, bias=None, *, a2=None, planes2=None):
     return c
 
 
+def gemm_x6_nt_cols2(a, planes1, N1, planes2, N2):
+    """(a W1^T, a W2^T) against the planes of W1 (N1, K) and W2 (N2, K) in one launch that splits a once (K <= 256)."""
+    a = _mat(a, "a")
+    M, K = a.shape
+    c1 = torch.empty((M, N1), device=a.device, dtype=torch.float32)
+    c2 = torch.empty((M, N2), device=a.device, dtype=torch.float32)
+    rc = _lib.load().amk_gemm_x6_nt_cols2(_p(a), a.stride(0), _p(planes1), _p(planes2), _p(c1), N1, _p(c2), N2, M, N1, N2, K,
+                                          _stream())
+    _lib.check(rc, "amk_gemm_x6_nt_cols2")
+    return c1, c2
+
+
 def gemm_x6_nt_swiglu(a, gate_planes, H, b12=None, *, keep_ab=True):
     """(silu(a) * b, (a | b) or None) with (a | b) = a w12^T + b12, w12's planes in the gate order."""
     a = _mat(a, "a")

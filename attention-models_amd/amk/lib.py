@@ -86,6 +86,8 @@ SIGNATURES = {
     "amk_gemm_x6_split": (_I, [_P, _L, _I, _I, _P, _P]),
     "amk_gemm_x6_nt": (_I, [_P, _L, _P, _P, _P, _L, _I, _I, _I, _P]),
     "amk_gemm_x6_nt2": (_I, [_P, _L, _P, _I, _P, _L, _P, _I, _P, _L, _I, _I, _P]),
+    "amk_gemm_x6_nt_cols2": (_I, [_P, _L, _P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _P]),
+    "amk_gemm_x6_short_k": (_I, [_I]),
     "amk_gemm_x6_gate_rows": (_I, [_I]),
     "amk_gemm_x6_nt_swiglu": (_I, [_P, _L, _P, _P, _P, _L, _P, _L, _I, _I, _I, _P]),
     "amk_gemm_x6_nt_swiglu_bwd": (_I, [_P, _L, _P, _P, _L, _P, _L, _I, _I, _I, _P]),

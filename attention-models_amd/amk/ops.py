@@ -1882,6 +1882,11 @@ X6_AUTO_KINDS = frozenset(k for k in os.environ.get("AMK_X6_KINDS", "linear,line
 # back to back (x1.40 - x1.47, profiles/kbench_x6_tn.log) and the step with all of them cleared the A/B at the first attempt,
 # so no shape is held back on the f32 kernel.
 X6_AUTO_FORMS = frozenset(k for k in os.environ.get("AMK_X6_FORMS", "fwd,dw").split(",") if k)
+# AMK_X6_SHORT_K=0: the forward products with K <= 256 (q | kv, w12 + gate, the patch embedding) run the tile kernel of
+# every other form instead of the row-block-stationary one, and q | kv is two launches again (the A/B switch; bit-identical
+# results either way).  The library holds the switch (amk_gemm_x6_short_k); it is set here once.
+X6_SHORT_K_MAX = 256
+_lib.load().amk_gemm_x6_short_k(int(os.environ.get("AMK_X6_SHORT_K", "1") != "0"))
 
 
 def _x6_tn_ok(M, N, K, *lds):
@@ -2028,7 +2033,10 @@ class _X6Linear2(torch.autograd.Function):
         x2 = x.reshape(-1, x.shape[-1])
         ctx.save_for_backward(x2, wa, wb)
         ctx.x_shape, ctx.params, ctx.pl = x.shape, (wa, wb), (pa, pb)
-        a, b = dense.gemm_x6_nt(x2, pa.w, pa.R), dense.gemm_x6_nt(x2, pb.w, pb.R)
+        if X6_SHORT_K_MAX >= x2.shape[1] and _lib.load().amk_gemm_x6_short_k(-1):
+            a, b = dense.gemm_x6_nt_cols2(x2, pa.w, pa.R, pb.w, pb.R)   # one launch: x2 is read and split once
+        else:
+            a, b = dense.gemm_x6_nt(x2, pa.w, pa.R), dense.gemm_x6_nt(x2, pb.w, pb.R)
         return a.view(*x.shape[:-1], pa.R), b.view(*x.shape[:-1], pb.R)
 
     @staticmethod

@@ -9,20 +9,30 @@
 // (tools/ubench_bf16x6.hip) -- at 6 / 16 of the f32 MFMA's matrix-pipe time.  Its roofline is the bf16
 // MFMA peak / 6 (417 TFLOP/s), NOT the 157.3 TFLOP/s f32 peak; bench.py reports it as a variant.
 //
-// B is the WEIGHT: small and shared by every row tile, so it is split ONCE per call into three bf16
-// planes (split_planes_kernel: [plane][row][K rounded up to 32], zero padded) and the GEMM streams those;
-// A (the activations, read once) is split on the fly between its global load and its LDS store.
+// B is the WEIGHT: small and shared by every row tile, so it is split ONCE per call (or once per optimizer
+// step, split_table_kernel) into three bf16 planes ([plane][row][K rounded up to 32], zero padded) and the
+// GEMM streams those; A (the activations) is split inside the GEMM.  Two kernels share the arithmetic -- one
+// f32 accumulator per output element, k-blocks of 16 in ascending order, the six products in the order of
+// x6_pa / x6_pb, then the epilogue -- and so agree bit for bit:
 //
-// Workgroup: 128 x 128 output tile, 8 waves as 2 (m) x 4 (n), each 64 x 32 = two MFMA tiles; K in steps
-// of 32; two workgroups per CU (four waves per SIMD: one wave's split / LDS traffic runs under another's
-// MFMAs).  LDS: three bf16 planes per operand, [row][32 k] with 80-byte rows (conflict-free 16-byte
-// fragment reads), 60 KB.  The loads of step k+1 are in flight under the MFMAs of step k.
-// Measured at the ViT-VQGAN shapes (tools/kbench_gemm.py): 125-168 TFLOP/s = 0.30-0.40 of the bf16x6 bound,
-// 1.15-1.4 x the tuned exact-f32 library GEMM.  Three other structures were built and measured within 8 % of
-// it: 4 waves x (64 x 64) with both operands split on the fly; a 256 x 128 tile with the split hoisted out of
-// the barrier window; two LDS stages with one barrier per step.  All sit at one barrier per ~768 matrix cycles
-// per wave -- the level of the guide's two-barrier bf16 structure (912 of 2500 TFLOP/s); the next step is its
-// 256 x 256 eight-phase pipeline, which needs N >= 512 to fill the chip at M = 32768.
+// gemm_x6_nt_kernel (every K, two contraction segments, the gate's backward): one workgroup per 128 x 128
+// output tile, 8 waves as 2 (m) x 4 (n), each 64 x 32 = two MFMA tiles; K in steps of 32; two workgroups per
+// CU.  A is split on the fly between its global load and its LDS store, by EVERY column tile of a row block.
+// LDS: three bf16 planes per operand, [row][32 k] with 80-byte rows (conflict-free 16-byte fragment reads),
+// 60 KB.  The loads of step k+1 are in flight under the MFMAs of step k.  125-168 TFLOP/s = 0.30-0.40 of the
+// bf16x6 bound at the ViT-VQGAN shapes (tools/kbench_gemm.py).  Three other structures were built and
+// measured within 8 % of it: 4 waves x (64 x 64) with both operands split on the fly; a 256 x 128 tile with
+// the split hoisted out of the barrier window; two LDS stages with one barrier per step.  At K = 256 a
+// workgroup lives for eight steps and its cost is per tile (the split, the prologue, the epilogue), not in
+// the K loop.
+//
+// gemm_x6_short_k_kernel (K <= 256, one segment, PLAIN and GATE; taken by x6_launch unless
+// amk_gemm_x6_short_k(0)): the row block owns the contraction.  A workgroup of 4 waves loads its 128 rows
+// of A once, splits them once and keeps the planes in registers as MFMA fragments for the whole K; it then
+// walks every column tile of the row block streaming only the weight planes through a double-buffered LDS
+// stage, and a tile's stores drain under the next tile's MFMAs.  Details at the kernel.
+#include <atomic>
+
 #include "amk_bf16.h"
 
 namespace amk_gemm {
@@ -223,6 +233,223 @@ __global__ __launch_bounds__(NTHR, 4) void gemm_x6_nt_kernel(Args g) {
   }
 }
 
+// ---- the short-K kernel: the whole contraction (K <= 256) of a row block stays in registers.
+// Workgroup: 4 waves, one per SIMD, 128 rows; wave w owns rows 32 w .. 32 w + 31 and holds their three planes as MFMA
+// A fragments for all 16 k-blocks (192 registers), loaded and split ONCE.  The workgroup then walks every column tile of
+// its row block -- 64 plane rows: 64 output columns (PLAIN), or the a and the b rows of 32 gate columns (GATE) -- in
+// stages of 64 k: the weight planes of stage s + 2 are in flight to registers and those of stage s + 1 go to the other
+// LDS buffer while the MFMAs of stage s run, with one LDS-only barrier per stage (48 MFMAs per wave).  The stores of a
+// tile are issued in the first stage of the next tile, behind that stage's loads, and drain under its products (neither
+// the barrier nor the wait for the next planes waits for them).
+// PLAIN walks the tiles of a second weight (Bp2 -> C2, no bias) behind those of the first: q | kv in one launch.
+// Every output element is one accumulator that takes its k-blocks in ascending order and the six products in the order
+// of x6_pa / x6_pb, then the epilogue arithmetic of gemm_x6_nt_kernel: the two kernels agree bit for bit.
+constexpr int SK_THR = 256, SK_BM = 128, SK_KC = 64, SK_ROWS = 64, SK_MAXK = 256;
+constexpr int SK_RS = SK_KC + 8;             // bf16 per LDS row: 144 bytes (conflict-free 16-byte fragment reads)
+constexpr int SK_PLANE = SK_ROWS * SK_RS;    // one plane of a stage
+constexpr int SK_STAGE = 3 * SK_PLANE;
+
+struct SkArgs {
+  const float *A, *bias;
+  const __bf16 *Bp, *Bp2;    // [3][NR][Kp], [3][NR2][Kp]
+  float *C, *C2, *G;
+  int M, K, Kp, N, N2, NR, NR2, nt1, ntiles;
+  int64_t lda, ldc, ldc2, ldg;
+};
+
+// FULL: Kp == 256 (every k-block and every stage exists: no guards in the stage loop)
+// KEEP (GATE): (a | b) is written to C
+template <int EPI, bool FULL, bool KEEP>
+__global__ __launch_bounds__(SK_THR) void gemm_x6_short_k_kernel(SkArgs g) {
+  constexpr bool GATE = EPI == X6_GATE;
+  __shared__ __attribute__((aligned(16))) __bf16 Bs[2 * SK_STAGE];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r = lane & 31, h = lane >> 5;
+  const int m0 = blockIdx.x * SK_BM;
+  const int nkb = FULL ? 16 : g.Kp / 16, nst = FULL ? 4 : (nkb + 3) / 4;   // Kp is a multiple of 32: nkb is even
+  const int S = g.ntiles * nst;
+
+  // B staging: a stage is 3 planes x 64 rows x 8 pieces of 16 B; thread -> rows tid / 8 and + 32, piece tid % 8
+  const int srow = tid >> 3, spc = (tid & 7) * 8;
+  const __amdgpu_buffer_rsrc_t b_rsrc =
+      __builtin_amdgcn_make_buffer_rsrc((void*)g.Bp, 0, (int)((int64_t)3 * g.NR * g.Kp * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t b2_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)(g.Bp2 ? g.Bp2 : g.Bp), 0, g.Bp2 ? (int)((int64_t)3 * g.NR2 * g.Kp * 2) : 0, 0x00020000);
+  uint4 bst[6];
+  int pt = 0, pc = 0;   // the stage the next prefetch() loads: tile pt, k chunk pc
+  auto prefetch = [&]() {
+    if (pt < g.ntiles) {
+      const bool second = !GATE && pt >= g.nt1;
+      const int tl = second ? pt - g.nt1 : pt, NR = second ? g.NR2 : g.NR;
+      const int k = SK_KC * pc + spc;
+      int off[6];
+#pragma unroll
+      for (int jj = 0; jj < 2; ++jj) {
+        const int prow = GATE ? 128 * (tl >> 1) + 32 * (tl & 1) + 64 * jj + srow : 64 * tl + 32 * jj + srow;
+        const bool ok = prow < NR && k < g.Kp;   // rows past the planes, chunks past Kp: zeros
+#pragma unroll
+        for (int p = 0; p < 3; ++p) off[2 * p + jj] = ok ? (int)((((int64_t)p * NR + prow) * g.Kp + k) * 2) : 0x7ffffff0;
+      }
+      if (second) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) bst[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(b2_rsrc, off[i], 0, 0));
+      } else {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) bst[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(b_rsrc, off[i], 0, 0));
+      }
+    }
+    if (++pc == nst) { pc = 0; ++pt; }
+  };
+  auto commit = [&](int par) {
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+#pragma unroll
+      for (int jj = 0; jj < 2; ++jj)
+        *reinterpret_cast<uint4*>(&Bs[par * SK_STAGE + p * SK_PLANE + (32 * jj + srow) * SK_RS + spc]) = bst[2 * p + jj];
+  };
+
+  prefetch();   // stage 0, in flight under the A loads
+
+  // the row block's A: lane (r, h) holds A[m0 + 32 wave + r][16 kb + 8 h + (0..7)] of every k-block, split once
+  bf16x8 a[16][3];
+  {
+    const __amdgpu_buffer_rsrc_t a_rsrc =
+        __builtin_amdgcn_make_buffer_rsrc((void*)g.A, 0, (int)(((int64_t)(g.M - 1) * g.lda + g.K) * 4), 0x00020000);
+    const int row = m0 + 32 * wave + r;
+    const bool rin = row < g.M;
+    const int abase = rin ? (int)(((int64_t)row * g.lda + 8 * h) * 4) : 0;
+#pragma unroll
+    for (int kb = 0; kb < 16; ++kb) {
+      bf16x4 lo[3], hi[3];
+      const int col = 16 * kb + 8 * h;   // columns past K (and rows past M) read zeros
+      const float4 x0 = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, rin && col < g.K ? abase + 64 * kb : 0x7ffffff0, 0, 0));
+      const float4 x1 = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, rin && col + 4 < g.K ? abase + 64 * kb + 16 : 0x7ffffff0, 0, 0));
+      split4(x0, lo);
+      split4(x1, hi);
+#pragma unroll
+      for (int p = 0; p < 3; ++p) a[kb][p] = cat4(lo[p], hi[p]);
+    }
+  }
+
+  commit(0);
+  prefetch();   // stage 1
+  lds_barrier();
+
+  // Outputs and bias go through buffer resources: a column past N, a row past M (beyond the resource's range: the host
+  // checks that the offsets fit) and "no tile" are offsets out of range, which the hardware drops or reads as 0.  So the
+  // stage loop has NO branch around a load or a store, and the compiler's s_waitcnt vmcnt(n) counts exactly: the wait for
+  // the next stage's planes leaves the younger stores in flight (behind a branch it would have to assume none were issued).
+  const auto out_rsrc = [&](float* p, int64_t ld, int width) {
+    return __builtin_amdgcn_make_buffer_rsrc((void*)p, 0, p ? (int)(((int64_t)(g.M - 1) * ld + width) * 4) : 0, 0x00020000);
+  };
+  const __amdgpu_buffer_rsrc_t c_rsrc = out_rsrc(g.C, g.ldc, GATE ? 2 * g.N : g.N);
+  const __amdgpu_buffer_rsrc_t c2_rsrc = out_rsrc(GATE ? g.G : g.C2, GATE ? g.ldg : g.ldc2, GATE ? g.N : g.N2);   // GATE: the gate
+  const __amdgpu_buffer_rsrc_t bias_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)(g.bias ? g.bias : g.A), 0, g.bias ? (GATE ? 2 * g.N : g.N) * 4 : 0, 0x00020000);
+  const int mrow = m0 + 32 * wave + 4 * h;   // register e of lane (r, h): row mrow + (e & 3) + 8 (e >> 2)
+  auto st = [&](__amdgpu_buffer_rsrc_t rs, int off, float v) {
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs, off, 0, 0);
+  };
+
+  // a finished tile: its accumulators and its bias, stored under the first stage of the NEXT tile (t < 0: nothing)
+  f32x16 out[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) out[i][e] = 0.f;
+  float ob0 = 0.f, ob1 = 0.f;
+  auto store_tile = [&](int t) {
+    const bool second = !GATE && t >= g.nt1;
+    const int tl = second ? t - g.nt1 : t;
+    const int Nt = second ? g.N2 : g.N;
+    const int n = GATE ? 32 * tl + r : 64 * tl + r;
+    if constexpr (GATE) {
+      const bool ok = t >= 0 && n < Nt;
+      const int goff = ok ? (int)(((int64_t)mrow * g.ldg + n) * 4) : 0x7ffffff0, gstep = (int)g.ldg * 4;
+      const int coff = ok ? (int)(((int64_t)mrow * g.ldc + n) * 4) : 0x7ffffff0, cstep = (int)g.ldc * 4;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int re = (e & 3) + 8 * (e >> 2);
+        const float av = out[0][e] + ob0, bv = out[1][e] + ob1;
+        st(c2_rsrc, goff + re * gstep, av * sigmoidf_(av) * bv);
+        if constexpr (KEEP) {
+          st(c_rsrc, coff + re * cstep, av);
+          st(c_rsrc, coff + re * cstep + Nt * 4, bv);
+        }
+      }
+    } else {
+      const int64_t ldt = second ? g.ldc2 : g.ldc;
+      const int step = (int)ldt * 4;
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int off = t >= 0 && n + 32 * i < Nt ? (int)(((int64_t)mrow * ldt + n + 32 * i) * 4) : 0x7ffffff0;
+        const float bv = i ? ob1 : ob0;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int re = (e & 3) + 8 * (e >> 2);
+          if (second) st(c2_rsrc, off + re * step, out[i][e] + bv);   // (a uniform choice of the resource, both arms store)
+          else st(c_rsrc, off + re * step, out[i][e] + bv);
+        }
+      }
+    }
+  };
+
+  f32x16 acc[2];
+  float b0 = 0.f, b1 = 0.f;   // GATE: the bias of a and of b; PLAIN: of columns n and n + 32
+  int par = 0, s = 0;
+  for (int t = 0; t < g.ntiles; ++t) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][e] = 0.f;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      if (FULL || c < nst) {
+        if (s + 1 < S) commit(par ^ 1);   // stage s + 1: its buffer was last read before the previous barrier
+        prefetch();                       // stage s + 2
+        __builtin_amdgcn_sched_barrier(0);   // issued HERE, under the MFMAs below
+        if (c == 0) {
+          // this tile's bias (used when the tile is stored), then the previous tile's stores: all BEHIND this stage's
+          // loads, so that the next stage waits for the loads alone; they drain under this tile's MFMAs
+          const bool second = !GATE && t >= g.nt1;
+          const int n = GATE ? 32 * t + r : 64 * t + r;
+          const int N1 = g.N;
+          b0 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(bias_rsrc, !second && n < N1 ? n * 4 : 0x7ffffff0, 0, 0));
+          b1 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
+                                             bias_rsrc, GATE ? (n < N1 ? (N1 + n) * 4 : 0x7ffffff0) : (!second && n + 32 < N1 ? (n + 32) * 4 : 0x7ffffff0), 0, 0));
+          store_tile(t - 1);
+        }
+        const __bf16* bs = Bs + par * SK_STAGE;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if (FULL || 4 * c + j < nkb) {
+            bf16x8 b[2][3];
+#pragma unroll
+            for (int p = 0; p < 3; ++p)
+#pragma unroll
+              for (int i = 0; i < 2; ++i)
+                b[i][p] = *reinterpret_cast<const bf16x8*>(&bs[p * SK_PLANE + (32 * i + r) * SK_RS + 16 * j + 8 * h]);
+#pragma unroll
+            for (int q = 0; q < 6; ++q)
+#pragma unroll
+              for (int i = 0; i < 2; ++i) acc[i] = mfmab(a[4 * c + j][x6_pa(q)], b[i][x6_pb(q)], acc[i]);
+          }
+        }
+        if (FULL ? c == 3 : c == nst - 1) {
+          out[0] = acc[0];
+          out[1] = acc[1];
+          ob0 = b0;
+          ob1 = b1;
+        }
+        lds_barrier();   // LDS only: stores and the loads of stage s + 2 stay in flight
+        par ^= 1;
+        ++s;
+      }
+    }
+  }
+  store_tile(g.ntiles - 1);
+}
+
 // ---- the plane shadow: every weight of a flat parameter buffer split in ONE launch, driven by a table.
 // Entry e (SPLIT_ENT int64 each): {src, R, K, H, blk0, dst_w, dst_wt, NR}: W = flat + src is (R, K) row-major;
 // its planes go to planes + dst_w as [3][NR][K padded to 32] -- row r of W at plane row r (H == 0), or in the gate
@@ -305,6 +532,50 @@ extern "C" int amk_gemm_x6_split(const float* W, int64_t ldw, int N, int K, void
   return AMK_OK;
 }
 
+// A/B switch: 1 = the forms with K <= 256 and one contraction segment run gemm_x6_short_k_kernel; 0 = every launch is
+// gemm_x6_nt_kernel
+static std::atomic<int> g_short_k{1};
+
+extern "C" int amk_gemm_x6_short_k(int on) {
+  const int prev = g_short_k.load(std::memory_order_relaxed);
+  if (on >= 0) g_short_k.store(on != 0, std::memory_order_relaxed);
+  return prev;
+}
+
+// The short-K kernel addresses its outputs with 32-bit byte offsets (rows up to a block past M included)
+static bool sk_out_ok(const float* p, int64_t ld, int M, int width) {
+  return !p || (ld >= width && ((int64_t)(M + SK_BM) * ld + width) * 4 < 0x7ffffff0ll);
+}
+
+// The short-K kernel over one weight (N2 == 0) or two (PLAIN only); the caller has made the checks of x6_launch.
+static int sk_launch(const char* who, int epi, const float* A, int64_t lda, const void* planes, const void* planes2, int K,
+                     const float* bias, float* C, int64_t ldc, float* C2, int64_t ldc2, float* G, int64_t ldg, int M, int N,
+                     int N2, void* stream) {
+  SkArgs g;
+  g.A = A; g.bias = bias; g.C = C; g.C2 = C2; g.G = G;
+  g.Bp = static_cast<const __bf16*>(planes); g.Bp2 = static_cast<const __bf16*>(planes2);
+  g.M = M; g.K = K; g.Kp = padded_k(K); g.N = N; g.N2 = N2;
+  g.NR = epi == X6_GATE ? (N + 63) / 64 * 128 : N; g.NR2 = N2;
+  g.nt1 = epi == X6_GATE ? (N + 31) / 32 : (N + 63) / 64;
+  g.ntiles = g.nt1 + (N2 + 63) / 64;
+  g.lda = lda; g.ldc = ldc; g.ldc2 = ldc2; g.ldg = ldg;
+  const dim3 grid((unsigned)((M + SK_BM - 1) / SK_BM)), blk(SK_THR);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const bool full = g.Kp == SK_MAXK;
+  if (epi == X6_GATE && C) {
+    if (full) hipLaunchKernelGGL((gemm_x6_short_k_kernel<X6_GATE, true, true>), grid, blk, 0, st, g);
+    else hipLaunchKernelGGL((gemm_x6_short_k_kernel<X6_GATE, false, true>), grid, blk, 0, st, g);
+  } else if (epi == X6_GATE) {
+    if (full) hipLaunchKernelGGL((gemm_x6_short_k_kernel<X6_GATE, true, false>), grid, blk, 0, st, g);
+    else hipLaunchKernelGGL((gemm_x6_short_k_kernel<X6_GATE, false, false>), grid, blk, 0, st, g);
+  } else {
+    if (full) hipLaunchKernelGGL((gemm_x6_short_k_kernel<X6_PLAIN, true, false>), grid, blk, 0, st, g);
+    else hipLaunchKernelGGL((gemm_x6_short_k_kernel<X6_PLAIN, false, false>), grid, blk, 0, st, g);
+  }
+  AMK_CHECK_LAUNCH(who);
+  return AMK_OK;
+}
+
 // One driver for every form: checks as amk_gemm_x6_nt always made them (sizes, 16-byte rows, operands < 2 GiB).
 static int x6_launch(const char* who, int epi, const float* A, int64_t lda, const void* planes, int K, const float* A2,
                      int64_t lda2, const void* planes2, int K2, const float* bias, const float* AB, int64_t ldab, float* C,
@@ -323,6 +594,9 @@ static int x6_launch(const char* who, int epi, const float* A, int64_t lda, cons
     AMK_CHECK_SUPPORTED(((int64_t)(M - 1) * lda2 + K2) * 4 < 0x7ffffff0ll && (int64_t)3 * NR * padded_k(K2) * 2 < 0x7ffffff0ll,
                         "%s: an operand must span < 2 GiB", who);
   }
+  if (g_short_k.load(std::memory_order_relaxed) && !two && K <= SK_MAXK && (epi == X6_PLAIN || epi == X6_GATE) &&
+      sk_out_ok(C, ldc, M, epi == X6_GATE ? 2 * N : N) && sk_out_ok(G, ldg, M, N))
+    return sk_launch(who, epi, A, lda, planes, nullptr, K, bias, C, ldc, nullptr, 0, G, ldg, M, N, 0, stream);
   Args g;
   g.A = A; g.A2 = A2; g.bias = bias; g.AB = AB; g.C = C; g.G = G;
   g.Bp = static_cast<const __bf16*>(planes); g.Bp2 = static_cast<const __bf16*>(planes2);
@@ -345,6 +619,27 @@ extern "C" int amk_gemm_x6_nt(const float* A, int64_t lda, const void* b_planes,
                               float* C, int64_t ldc, int M, int N, int K, void* stream) {
   AMK_CHECK_ARG(C, "amk_gemm_x6_nt: null pointer");
   return x6_launch("amk_gemm_x6_nt", X6_PLAIN, A, lda, b_planes, K, nullptr, 0, nullptr, 0, bias, nullptr, 0, C, ldc, nullptr, 0, M, N, stream);
+}
+
+// C1 = A W1^T and C2 = A W2^T in one launch of the short-K kernel (the q and kv projections of one x): A is read and
+// split once, the column walk runs over both weights.  With the switch off: two launches of gemm_x6_nt_kernel.
+extern "C" int amk_gemm_x6_nt_cols2(const float* A, int64_t lda, const void* planes1, const void* planes2, float* C1,
+                                    int64_t ldc1, float* C2, int64_t ldc2, int M, int N1, int N2, int K, void* stream) {
+  const char* who = "amk_gemm_x6_nt_cols2";
+  AMK_CHECK_ARG(A && planes1 && planes2 && C1 && C2, "%s: null pointer", who);
+  AMK_CHECK_ARG(M > 0 && N1 > 0 && N2 > 0 && K > 0, "%s: non-positive size M=%d N1=%d N2=%d K=%d", who, M, N1, N2, K);
+  AMK_CHECK_SUPPORTED(K <= SK_MAXK, "%s: K must be <= %d", who, SK_MAXK);
+  AMK_CHECK_SUPPORTED(K % 4 == 0 && lda % 4 == 0 &&
+                          ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(planes1) | reinterpret_cast<uintptr_t>(planes2)) & 15) == 0,
+                      "%s: K, lda must be multiples of 4 and A, the planes 16-byte aligned", who);
+  AMK_CHECK_SUPPORTED(((int64_t)(M - 1) * lda + K) * 4 < 0x7ffffff0ll && (int64_t)3 * N1 * padded_k(K) * 2 < 0x7ffffff0ll &&
+                          (int64_t)3 * N2 * padded_k(K) * 2 < 0x7ffffff0ll,
+                      "%s: an operand must span < 2 GiB", who);
+  if (!g_short_k.load(std::memory_order_relaxed) || !sk_out_ok(C1, ldc1, M, N1) || !sk_out_ok(C2, ldc2, M, N2)) {
+    const int rc = amk_gemm_x6_nt(A, lda, planes1, nullptr, C1, ldc1, M, N1, K, stream);
+    return rc != AMK_OK ? rc : amk_gemm_x6_nt(A, lda, planes2, nullptr, C2, ldc2, M, N2, K, stream);
+  }
+  return sk_launch(who, X6_PLAIN, A, lda, planes1, planes2, K, nullptr, C1, ldc1, C2, ldc2, nullptr, 0, M, N1, N2, stream);
 }
 
 extern "C" int amk_gemm_x6_nt2(const float* A, int64_t lda, const void* planes, int K, const float* A2, int64_t lda2,

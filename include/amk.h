@@ -638,6 +638,15 @@ int amk_gemm_x6_nt(const float* A, int64_t lda, const void* w_planes, const floa
  *                              flat_elems / planes_elems writes nothing. */
 int amk_gemm_x6_nt2(const float* A, int64_t lda, const void* planes, int K, const float* A2, int64_t lda2,
                     const void* planes2, int K2, float* C, int64_t ldc, int M, int N, void* stream);
+/* C1 = A W1^T (M, N1) and C2 = A W2^T (M, N2) in one launch that reads and splits A once (the q and kv projections of
+ * one x); preconditions and error codes of amk_gemm_x6_nt, and AMK_EUNSUPPORTED for K > 256.  Bit for bit the two
+ * amk_gemm_x6_nt calls. */
+int amk_gemm_x6_nt_cols2(const float* A, int64_t lda, const void* planes1, const void* planes2, float* C1,
+                         int64_t ldc1, float* C2, int64_t ldc2, int M, int N1, int N2, int K, void* stream);
+/* Process-wide A/B switch of the kernel for K <= 256 (one contraction segment, the plain and the gate form): on != 0
+ * (the default) they run the row-block-stationary kernel, 0 the tile kernel of every other form; bit-identical results.
+ * Returns the previous value; a negative argument only queries. */
+int amk_gemm_x6_short_k(int on);
 int amk_gemm_x6_gate_rows(int H);
 int amk_gemm_x6_nt_swiglu(const float* A, int64_t lda, const void* gate_planes, const float* bias, float* gate,
                           int64_t ldg, float* ab, int64_t ldab, int M, int H, int K, void* stream);

@@ -13,6 +13,7 @@ import sys
 
 FAMILIES = [
     ("x6 Linear GEMMs (gemm_x6_nt_kernel)", r"gemm_x6_nt_kernel"),
+    ("x6 Linear GEMMs, K <= 256 (gemm_x6_short_k_kernel)", r"gemm_x6_short_k_kernel"),
     ("plane split (split_table_kernel)", r"split_table_kernel"),
     ("per-call split (split_planes_kernel)", r"split_planes_kernel"),
     ("f32 NT (gemm_nt_dkernel / gemm_nt_kernel)", r"amk_dense.*gemm_nt_"),

@@ -6,7 +6,10 @@ reported, with the error of both against fp64 (max |c - c64| / max |c64|, on the
 split itself.  Then the five weight gradients (dWq | dWkv as one launch, dWo, dW12, dW3, each with its bias sums) on
 dense.gemm_tn (exact f32) against dense.gemm_x6_tn (csrc/gemm_x6_tn.hip, both operands split inside the kernel), the same
 way, their error against fp64 over the whole gradient (AMK_X6_TN_TK=128 | 256 forces that kernel's tile width).
-    python tools/kbench_x6_linear.py [--batch 32] [--iters 20] [--rounds 3] [--only all|fwd|dw]
+--only short_k: the three forward products with K = 256 (the gate with and without (a | b), q | kv) on the tile kernel
+against the row-block-stationary one (amk_gemm_x6_short_k off / on), the two arms alternating in one process for five
+rounds: medians and spreads, after a check that the two arms agree bit for bit.
+    python tools/kbench_x6_linear.py [--batch 32] [--iters 20] [--rounds 3] [--only all|fwd|dw|short_k]
 """
 import argparse
 import os
@@ -25,7 +28,8 @@ if __name__ == "__main__":
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--only", choices=("all", "fwd", "dw"), default="all", help="fwd: the nine forward / input-gradient rows; dw: the weight gradients")
+    ap.add_argument("--only", choices=("all", "fwd", "dw", "short_k"), default="all",
+                    help="fwd: the nine forward / input-gradient rows; dw: the weight gradients; short_k: tile kernel against short-K kernel")
     a = ap.parse_args()
     from amk import dense, ops, tuning
 
@@ -107,6 +111,32 @@ if __name__ == "__main__":
          lambda: ops._nn_plain(d_ab, W["w12"]), lambda: dense.gemm_x6_nt(d_ab, P["w12"].wt, Dm),
          lambda: d_ab[R_].double() @ W["w12"].double()),
     ]
+    if a.only == "short_k":
+        import statistics
+
+        from amk import lib
+
+        L = lib.load()
+        rows = [("w12 + SwiGLU gate, (a | b) kept", 2.0 * M * Dm * 2 * Hf, lambda: dense.gemm_x6_nt_swiglu(x, P["w12"].w, Hf, b12, keep_ab=True)),
+                ("w12 + SwiGLU gate, gate only", 2.0 * M * Dm * 2 * Hf, lambda: dense.gemm_x6_nt_swiglu(x, P["w12"].w, Hf, b12, keep_ab=False)[:1]),
+                ("q | kv forward (two launches | one)", 2.0 * M * Dm * 3 * Hh, lambda: dense.gemm_x6_nt_cols2(x, P["q"].w, Hh, P["kv"].w, 2 * Hh))]
+        for name, fl, fn in rows:
+            outs = []
+            for on in (0, 1):
+                L.amk_gemm_x6_short_k(on)
+                outs.append(fn())
+            same = all(torch.equal(u, v) for u, v in zip(*outs))
+            del outs
+            ts = {0: [], 1: []}
+            for rnd in range(5):
+                for on in (0, 1):
+                    L.amk_gemm_x6_short_k(on)
+                    ts[on].append(time_launches(fn, a.iters, warm=a.iters) * 1e6)
+            L.amk_gemm_x6_short_k(1)
+            m0, m1 = statistics.median(ts[0]), statistics.median(ts[1])
+            print(f"{name:38s} tile kernel {m0:7.1f} us [{min(ts[0]):.1f} .. {max(ts[0]):.1f}] {fl / m0 / 1e6:6.1f} TF/s | short-K {m1:7.1f} us "
+                  f"[{min(ts[1]):.1f} .. {max(ts[1]):.1f}] {fl / m1 / 1e6:6.1f} TF/s | x{m0 / m1:.2f} | bit-equal {same}", flush=True)
+        sys.exit(0)
     tot = [0.0, 0.0]
     for name, fl, f32, x6, ref in (cases if a.only != "dw" else []):
         want = ref()

@@ -92,9 +92,9 @@ def _as_kernel_view(t):
     return t.permute(0, 2, 1, 3).contiguous().permute(0, 2, 1, 3)  # (B,T,H,D) storage
 
 
-def _new_bthd(B, H, T, D, like):
+def _new_bthd(B, H, T, D, like, dtype=torch.float32):
     """(B,H,T,D) view over fresh (B,T,H*D) storage: the layout the W_o projection consumes."""
-    return torch.empty((B, T, H, D), device=like.device, dtype=torch.float32).permute(0, 2, 1, 3)
+    return torch.empty((B, T, H, D), device=like.device, dtype=dtype).permute(0, 2, 1, 3)
 
 
 def _mask_u8(mask, shape, what):
@@ -1398,57 +1398,70 @@ def summed_experts(a2, logits2, W, k, H):
 
 
 # ---------------------------------------------------------------------------- agent attention
+# The op's two element types: (dtype of qkv, o and their gradients, forward, backward, workspace query).  agents, vagent,
+# stats1, the workspaces and the convolution's parameters and gradients are f32 in both.
+_AGENT_F32 = (torch.float32, "amk_agent_attn_fwd", "amk_agent_attn_bwd", "amk_agent_ws_floats_dh")
+_AGENT_BF16 = (torch.bfloat16, "amk_agent_attn_bf16_fwd", "amk_agent_attn_bf16_bwd", "amk_agent_bf16_ws_floats")
+
+
+def _agent_fwd(ctx, elem, qkv2, conv_w, conv_b, H, D, P, scale):
+    ctx.elem = elem
+    dtype, fwd, _, ws_floats = elem
+    B, T, _ = qkv2.shape
+    qkv2 = qkv2.contiguous()
+    qkv = qkv2.view(B, T, 3, H, D)
+    q, k, v = (qkv[:, :, j].permute(0, 2, 1, 3) for j in range(3))
+    dev = qkv2.device
+    o = _new_bthd(B, H, T, D, qkv2, dtype)
+    agents = torch.empty((B, H, P, D), device=dev, dtype=torch.float32)
+    vagent = torch.empty_like(agents)
+    stats1 = torch.empty((B, H, P, 2), device=dev, dtype=torch.float32)
+    cw, cb = conv_w.contiguous(), conv_b.contiguous()
+    L = _lib.load()
+    ws = torch.empty((max(getattr(L, ws_floats)(B, H, T, P, D, 0), 1),), device=dev, dtype=torch.float32)
+    rc = getattr(L, fwd)(_ptr(q), _ptr(k), _ptr(v), _ptr(cw), _ptr(cb), _ptr(o), _ptr(agents), _ptr(vagent), _ptr(stats1),
+                         _ptr(ws), B, H, T, D, P, *_strides4(q), *_strides4(k), *_strides4(v), *_strides4(o), float(scale),
+                         _stream())
+    _lib.check(rc, fwd)
+    ctx.save_for_backward(qkv2, cw, agents, vagent, stats1)
+    ctx.cfg = (H, D, P, scale)
+    return o.permute(0, 2, 1, 3).reshape(B, T, H * D)
+
+
 class _AgentAttn(torch.autograd.Function):
     """qkv (B,T,3*h*d) with the reference's '(qkv h d)' column order -> o (B,T,h*d)."""
 
     @staticmethod
     @_amp_fwd
-    def forward(ctx, qkv2, conv_w, conv_b, H, D, P, scale):
+    def forward(ctx, qkv2, conv_w, conv_b, *cfg):
         _require_device(qkv2, conv_w, conv_b)
-        B, T, _ = qkv2.shape
-        qkv2 = qkv2.contiguous()
-        qkv = qkv2.view(B, T, 3, H, D)
-        q, k, v = (qkv[:, :, j].permute(0, 2, 1, 3) for j in range(3))
-        dev = qkv2.device
-        o = _new_bthd(B, H, T, D, qkv2)
-        agents = torch.empty((B, H, P, D), device=dev, dtype=torch.float32)
-        vagent = torch.empty_like(agents)
-        stats1 = torch.empty((B, H, P, 2), device=dev, dtype=torch.float32)
-        cw, cb = conv_w.contiguous(), conv_b.contiguous()
-        L = _lib.load()
-        ws = torch.empty((max(L.amk_agent_ws_floats_dh(B, H, T, P, D, 0), 1),), device=dev, dtype=torch.float32)
-        rc = L.amk_agent_attn_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(cw), _ptr(cb), _ptr(o), _ptr(agents), _ptr(vagent),
-                                  _ptr(stats1), _ptr(ws), B, H, T, D, P, *_strides4(q), *_strides4(k), *_strides4(v), *_strides4(o),
-                                  float(scale), _stream())
-        _lib.check(rc, "amk_agent_attn_fwd")
-        ctx.save_for_backward(qkv2, cw, agents, vagent, stats1)
-        ctx.cfg = (H, D, P, scale)
-        return o.permute(0, 2, 1, 3).reshape(B, T, H * D)
+        return _agent_fwd(ctx, _AGENT_F32, qkv2, conv_w, conv_b, *cfg)
 
     @staticmethod
     @once_differentiable
     @_amp_bwd
     def backward(ctx, d_o2):
+        dtype, _, bwd, ws_floats = ctx.elem
         qkv2, cw, agents, vagent, stats1 = ctx.saved_tensors
         H, D, P, scale = ctx.cfg
         B, T, _ = qkv2.shape
         dev = qkv2.device
         qkv = qkv2.view(B, T, 3, H, D)
         q, k, v = (qkv[:, :, j].permute(0, 2, 1, 3) for j in range(3))
-        d_o = d_o2.contiguous().view(B, T, H, D).permute(0, 2, 1, 3)
+        d_o = d_o2.to(dtype).contiguous().view(B, T, H, D).permute(0, 2, 1, 3)
         dqkv2 = torch.empty_like(qkv2)
         dqkv = dqkv2.view(B, T, 3, H, D)
         dq, dk, dv = (dqkv[:, :, j].permute(0, 2, 1, 3) for j in range(3))
         L = _lib.load()
         cells = B * H * L.amk_agent_num_chunks_dh(T, D)
-        ws = torch.empty((max(L.amk_agent_ws_floats_dh(B, H, T, P, D, 1), 1),), device=dev, dtype=torch.float32)
+        ws = torch.empty((max(getattr(L, ws_floats)(B, H, T, P, D, 1), 1),), device=dev, dtype=torch.float32)
         dw_part = torch.empty((cells, 9, D), device=dev, dtype=torch.float32)
         db_part = torch.empty((cells, D), device=dev, dtype=torch.float32)
-        rc = L.amk_agent_attn_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(cw), _ptr(d_o), _ptr(agents), _ptr(vagent), _ptr(stats1),
-                                  _ptr(dq), _ptr(dk), _ptr(dv), _ptr(ws), _ptr(dw_part), _ptr(db_part),
-                                  B, H, T, D, P, *_strides4(q), *_strides4(k), *_strides4(v), *_strides4(d_o),
-                                  *_strides4(dq), *_strides4(dk), *_strides4(dv), float(scale), _stream())
-        _lib.check(rc, "amk_agent_attn_bwd")
+        rc = getattr(L, bwd)(_ptr(q), _ptr(k), _ptr(v), _ptr(cw), _ptr(d_o), _ptr(agents), _ptr(vagent), _ptr(stats1),
+                             _ptr(dq), _ptr(dk), _ptr(dv), _ptr(ws), _ptr(dw_part), _ptr(db_part),
+                             B, H, T, D, P, *_strides4(q), *_strides4(k), *_strides4(v), *_strides4(d_o),
+                             *_strides4(dq), *_strides4(dk), *_strides4(dv), float(scale), _stream())
+        _lib.check(rc, bwd)
         dconv_w = torch.empty((D, 1, 3, 3), device=dev, dtype=torch.float32)
         dconv_b = torch.empty((D,), device=dev, dtype=torch.float32)
         _lib.check(L.amk_agent_conv_grad_reduce(_ptr(dw_part), _ptr(db_part), cells, D, _ptr(dconv_w), _ptr(dconv_b), _stream()),
@@ -1465,61 +1478,13 @@ class _AgentAttn(torch.autograd.Function):
 AGENT_BF16 = os.environ.get("AMK_AGENT_BF16", "1") == "1"
 
 
-class _AgentAttnBF16(torch.autograd.Function):
+class _AgentAttnBF16(_AgentAttn):
     """_AgentAttn on bf16 elements: qkv (B,T,3*h*d) bf16 -> o (B,T,h*d) bf16; conv_w / conv_b and their gradients f32."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda")
-    def forward(ctx, qkv2, conv_w, conv_b, H, D, P, scale):
-        B, T, _ = qkv2.shape
-        qkv2 = qkv2.contiguous()
-        qkv = qkv2.view(B, T, 3, H, D)
-        q, k, v = (qkv[:, :, j].permute(0, 2, 1, 3) for j in range(3))
-        dev = qkv2.device
-        o = torch.empty((B, T, H, D), device=dev, dtype=torch.bfloat16).permute(0, 2, 1, 3)
-        agents = torch.empty((B, H, P, D), device=dev, dtype=torch.float32)
-        vagent = torch.empty_like(agents)
-        stats1 = torch.empty((B, H, P, 2), device=dev, dtype=torch.float32)
-        cw, cb = conv_w.contiguous(), conv_b.contiguous()
-        L = _lib.load()
-        ws = torch.empty((max(L.amk_agent_bf16_ws_floats(B, H, T, P, D, 0), 1),), device=dev, dtype=torch.float32)
-        rc = L.amk_agent_attn_bf16_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(cw), _ptr(cb), _ptr(o), _ptr(agents), _ptr(vagent),
-                                       _ptr(stats1), _ptr(ws), B, H, T, D, P, *_strides4(q), *_strides4(k), *_strides4(v),
-                                       *_strides4(o), float(scale), _stream())
-        _lib.check(rc, "amk_agent_attn_bf16_fwd")
-        ctx.save_for_backward(qkv2, cw, agents, vagent, stats1)
-        ctx.cfg = (H, D, P, scale)
-        return o.permute(0, 2, 1, 3).reshape(B, T, H * D)
-
-    @staticmethod
-    @once_differentiable
-    @_amp_bwd
-    def backward(ctx, d_o2):
-        qkv2, cw, agents, vagent, stats1 = ctx.saved_tensors
-        H, D, P, scale = ctx.cfg
-        B, T, _ = qkv2.shape
-        dev = qkv2.device
-        qkv = qkv2.view(B, T, 3, H, D)
-        q, k, v = (qkv[:, :, j].permute(0, 2, 1, 3) for j in range(3))
-        d_o = d_o2.to(torch.bfloat16).contiguous().view(B, T, H, D).permute(0, 2, 1, 3)
-        dqkv2 = torch.empty_like(qkv2)
-        dqkv = dqkv2.view(B, T, 3, H, D)
-        dq, dk, dv = (dqkv[:, :, j].permute(0, 2, 1, 3) for j in range(3))
-        L = _lib.load()
-        cells = B * H * L.amk_agent_num_chunks_dh(T, D)
-        ws = torch.empty((max(L.amk_agent_bf16_ws_floats(B, H, T, P, D, 1), 1),), device=dev, dtype=torch.float32)
-        dw_part = torch.empty((cells, 9, D), device=dev, dtype=torch.float32)
-        db_part = torch.empty((cells, D), device=dev, dtype=torch.float32)
-        rc = L.amk_agent_attn_bf16_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(cw), _ptr(d_o), _ptr(agents), _ptr(vagent), _ptr(stats1),
-                                       _ptr(dq), _ptr(dk), _ptr(dv), _ptr(ws), _ptr(dw_part), _ptr(db_part),
-                                       B, H, T, D, P, *_strides4(q), *_strides4(k), *_strides4(v), *_strides4(d_o),
-                                       *_strides4(dq), *_strides4(dk), *_strides4(dv), float(scale), _stream())
-        _lib.check(rc, "amk_agent_attn_bf16_bwd")
-        dconv_w = torch.empty((D, 1, 3, 3), device=dev, dtype=torch.float32)
-        dconv_b = torch.empty((D,), device=dev, dtype=torch.float32)
-        _lib.check(L.amk_agent_conv_grad_reduce(_ptr(dw_part), _ptr(db_part), cells, D, _ptr(dconv_w), _ptr(dconv_b), _stream()),
-                   "amk_agent_conv_grad_reduce")
-        return dqkv2, dconv_w, dconv_b, None, None, None, None
+    def forward(ctx, *args):
+        return _agent_fwd(ctx, _AGENT_BF16, *args)
 
 
 def _agent_bf16_ok(qkv2, conv_w, conv_b, dim_head, pool):
@@ -2516,11 +2481,6 @@ def discr_norm_mode():
     return os.environ.get("AMK_DISCR_NORM", "amk")
 
 
-def _bn_aligned(t):
-    t = t.contiguous()
-    return t if t.data_ptr() % 16 == 0 else t.clone()
-
-
 def _bn_dims(x):
     N, C, H, W = x.shape
     return N, C, H * W
@@ -2531,22 +2491,35 @@ def _bn_ws(x):
     return torch.empty(int(_lib.load().amk_bnact_ws_floats(N, C, HW)), device=x.device, dtype=torch.float32)
 
 
+def _bn_f32(t):
+    return None if t is None else t.to(torch.float32).contiguous()
+
+
+# The op's two element types: (dtype of the (N, C, HW) tensors, forward, backward, double backward).  The parameters, the
+# statistics, the kept sums and the workspace (amk_bnact_ws_floats) are f32 in both.
+_BN_F32 = (torch.float32, "amk_bnact_fwd", "amk_bnact_bwd", "amk_bnact_bwd_bwd")
+_BN_BF16 = (torch.bfloat16, "amk_bnact_bf16_fwd", "amk_bnact_bf16_bwd", "amk_bnact_bf16_bwd_bwd")
+
+
 class _BNActGrad(torch.autograd.Function):
     """(gx, dgamma, dbeta) of z = leaky_relu(batch_norm(x), slope) for a given gz; differentiable in gz, x and gamma
-    (its backward is the double backward the gradient penalty takes)."""
+    (its backward is the double backward the gradient penalty takes).  Incoming gradients are brought to the element
+    dtype (gg_gamma / gg_beta to f32); a subclass sets ELEM."""
+    ELEM = _BN_F32
 
-    @staticmethod
-    def forward(ctx, gz, x, weight, bias, mean, rstd, slope):
-        gz = _bn_aligned(gz)
+    @classmethod
+    def forward(cls, ctx, gz, x, weight, bias, mean, rstd, slope):
+        ctx.elem = cls.ELEM
+        dtype, _, bwd, _ = cls.ELEM
+        gz = _c16(gz.to(dtype))
         N, C, HW = _bn_dims(x)
-        L = _lib.load()
         gx = torch.empty_like(x)
         sums = torch.empty((2, C), device=x.device, dtype=torch.float32)
         dw = torch.empty_like(weight)
         db = torch.empty_like(bias)
-        _lib.check(L.amk_bnact_bwd(_ptr(gz), _ptr(x), _ptr(weight), _ptr(bias), _ptr(mean), _ptr(rstd), N, C, HW,
-                                   float(slope), _ptr(gx), _ptr(sums), _ptr(dw), _ptr(db), _ptr(_bn_ws(x)), _stream()),
-                   "amk_bnact_bwd")
+        _lib.check(getattr(_lib.load(), bwd)(
+            _ptr(gz), _ptr(x), _ptr(weight), _ptr(bias), _ptr(mean), _ptr(rstd), N, C, HW, float(slope), _ptr(gx), _ptr(sums),
+            _ptr(dw), _ptr(db), _ptr(_bn_ws(x)), _stream()), bwd)
         ctx.save_for_backward(gz, x, weight, bias, mean, rstd, sums)
         ctx.slope = slope
         ctx.set_materialize_grads(False)   # absent gradients of dgamma / dbeta cost nothing
@@ -2558,45 +2531,48 @@ class _BNActGrad(torch.autograd.Function):
         gz, x, weight, bias, mean, rstd, sums = ctx.saved_tensors
         if ggx is None and ggw is None and ggb is None:
             return None, None, None, None, None, None, None
-        ggx = torch.zeros_like(x) if ggx is None else _bn_aligned(ggx)
+        dtype, _, _, bwd_bwd = ctx.elem
+        ggx = torch.zeros_like(x) if ggx is None else _c16(ggx.to(dtype))
         N, C, HW = _bn_dims(x)
         g_gz = torch.empty_like(x)
         g_x = torch.empty_like(x)
         g_w = torch.empty_like(weight) if ctx.needs_input_grad[2] else None
-        _lib.check(_lib.load().amk_bnact_bwd_bwd(
-            _ptr(ggx), _ptr(ggw.contiguous() if ggw is not None else None), _ptr(ggb.contiguous() if ggb is not None else None),
-            _ptr(gz), _ptr(x), _ptr(weight), _ptr(bias), _ptr(mean), _ptr(rstd), _ptr(sums), N, C, HW, float(ctx.slope),
-            _ptr(g_gz), _ptr(g_x), _ptr(g_w), _ptr(_bn_ws(x)), _stream()), "amk_bnact_bwd_bwd")
+        _lib.check(getattr(_lib.load(), bwd_bwd)(
+            _ptr(ggx), _ptr(_bn_f32(ggw)), _ptr(_bn_f32(ggb)), _ptr(gz), _ptr(x), _ptr(weight), _ptr(bias), _ptr(mean),
+            _ptr(rstd), _ptr(sums), N, C, HW, float(ctx.slope), _ptr(g_gz), _ptr(g_x), _ptr(g_w), _ptr(_bn_ws(x)),
+            _stream()), bwd_bwd)
         return (g_gz if ctx.needs_input_grad[0] else None, g_x if ctx.needs_input_grad[1] else None, g_w,
                 None, None, None, None)
 
 
 class _BNAct(torch.autograd.Function):
-    """z = leaky_relu(batch_norm(x, training=True), slope) with the running statistics updated in place."""
+    """z = leaky_relu(batch_norm(x, training=True), slope) with the running statistics updated in place; a subclass sets
+    GRAD, whose ELEM names the forward too."""
+    GRAD = _BNActGrad
 
-    @staticmethod
-    def forward(ctx, x, weight, bias, running_mean, running_var, eps, momentum, slope):
+    @classmethod
+    def forward(cls, ctx, x, weight, bias, running_mean, running_var, eps, momentum, slope):
+        fwd = cls.GRAD.ELEM[1]
         N, C, HW = _bn_dims(x)
-        L = _lib.load()
         z = torch.empty_like(x)
         mean = torch.empty(C, device=x.device, dtype=torch.float32)
         rstd = torch.empty(C, device=x.device, dtype=torch.float32)
-        _lib.check(L.amk_bnact_fwd(_ptr(x), _ptr(weight), _ptr(bias), N, C, HW, float(eps), float(momentum), float(slope),
-                                   _ptr(z), _ptr(mean), _ptr(rstd), _ptr(running_mean), _ptr(running_var),
-                                   _ptr(_bn_ws(x)), _stream()), "amk_bnact_fwd")
+        _lib.check(getattr(_lib.load(), fwd)(
+            _ptr(x), _ptr(weight), _ptr(bias), N, C, HW, float(eps), float(momentum), float(slope), _ptr(z), _ptr(mean),
+            _ptr(rstd), _ptr(running_mean), _ptr(running_var), _ptr(_bn_ws(x)), _stream()), fwd)
         ctx.save_for_backward(x, weight, bias, mean, rstd)
         ctx.slope = slope
         ctx.set_materialize_grads(False)
         return z
 
-    @staticmethod
-    def backward(ctx, gz):
+    @classmethod
+    def backward(cls, ctx, gz):
         if gz is None:
             return (None,) * 8
         x, weight, bias, mean, rstd = ctx.saved_tensors
         from .models.discriminator import input_grad_only_active   # (lazy: the models package imports this module)
 
-        gx, dw, db = _BNActGrad.apply(gz, x, weight, bias, mean, rstd, ctx.slope)
+        gx, dw, db = cls.GRAD.apply(gz, x, weight, bias, mean, rstd, ctx.slope)
         if input_grad_only_active():
             dw = db = None
         return (gx if ctx.needs_input_grad[0] else None, dw if ctx.needs_input_grad[1] else None,
@@ -2618,7 +2594,7 @@ def bn_leaky_relu(x, bn, slope):
     _require_device(x, bn.weight, bn.bias)
     if bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
-    return _BNAct.apply(_bn_aligned(x), bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum,
+    return _BNAct.apply(_c16(x), bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum,
                         float(slope))
 
 
@@ -2635,84 +2611,15 @@ def discr_norm_bf16_on():
     return os.environ.get("AMK_DISCR_NORM_BF16", "1") != "0"
 
 
-def _bn_aligned_bf16(t):
-    return _bn_aligned(t.to(torch.bfloat16))
-
-
-def _bn_f32(t):
-    return None if t is None else t.to(torch.float32).contiguous()
-
-
-class _BNActGradBF16(torch.autograd.Function):
+class _BNActGradBF16(_BNActGrad):
     """_BNActGrad on bf16 gz and x: gx bf16, rounded once; dgamma, dbeta and the kept sums f32.  Its backward is the double
     backward on bf16 ggx with bf16 g_gz and g_x and an f32 g_gamma."""
-
-    @staticmethod
-    def forward(ctx, gz, x, weight, bias, mean, rstd, slope):
-        gz = _bn_aligned_bf16(gz)
-        N, C, HW = _bn_dims(x)
-        L = _lib.load()
-        gx = torch.empty_like(x)
-        sums = torch.empty((2, C), device=x.device, dtype=torch.float32)
-        dw = torch.empty_like(weight)
-        db = torch.empty_like(bias)
-        _lib.check(L.amk_bnact_bf16_bwd(_ptr(gz), _ptr(x), _ptr(weight), _ptr(bias), _ptr(mean), _ptr(rstd), N, C, HW,
-                                        float(slope), _ptr(gx), _ptr(sums), _ptr(dw), _ptr(db), _ptr(_bn_ws(x)),
-                                        _stream()), "amk_bnact_bf16_bwd")
-        ctx.save_for_backward(gz, x, weight, bias, mean, rstd, sums)
-        ctx.slope = slope
-        ctx.set_materialize_grads(False)   # absent gradients of dgamma / dbeta cost nothing
-        return gx, dw, db
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, ggx, ggw, ggb):
-        gz, x, weight, bias, mean, rstd, sums = ctx.saved_tensors
-        if ggx is None and ggw is None and ggb is None:
-            return None, None, None, None, None, None, None
-        ggx = torch.zeros_like(x) if ggx is None else _bn_aligned_bf16(ggx)
-        N, C, HW = _bn_dims(x)
-        g_gz = torch.empty_like(x)
-        g_x = torch.empty_like(x)
-        g_w = torch.empty_like(weight) if ctx.needs_input_grad[2] else None
-        _lib.check(_lib.load().amk_bnact_bf16_bwd_bwd(
-            _ptr(ggx), _ptr(_bn_f32(ggw)), _ptr(_bn_f32(ggb)), _ptr(gz), _ptr(x), _ptr(weight), _ptr(bias), _ptr(mean),
-            _ptr(rstd), _ptr(sums), N, C, HW, float(ctx.slope), _ptr(g_gz), _ptr(g_x), _ptr(g_w), _ptr(_bn_ws(x)),
-            _stream()), "amk_bnact_bf16_bwd_bwd")
-        return (g_gz if ctx.needs_input_grad[0] else None, g_x if ctx.needs_input_grad[1] else None, g_w,
-                None, None, None, None)
+    ELEM = _BN_BF16
 
 
-class _BNActBF16(torch.autograd.Function):
+class _BNActBF16(_BNAct):
     """_BNAct on a bf16 x with f32 parameters: z bf16, rounded once; mean, rstd and the running statistics f32."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, running_mean, running_var, eps, momentum, slope):
-        N, C, HW = _bn_dims(x)
-        L = _lib.load()
-        z = torch.empty_like(x)
-        mean = torch.empty(C, device=x.device, dtype=torch.float32)
-        rstd = torch.empty(C, device=x.device, dtype=torch.float32)
-        _lib.check(L.amk_bnact_bf16_fwd(_ptr(x), _ptr(weight), _ptr(bias), N, C, HW, float(eps), float(momentum),
-                                        float(slope), _ptr(z), _ptr(mean), _ptr(rstd), _ptr(running_mean),
-                                        _ptr(running_var), _ptr(_bn_ws(x)), _stream()), "amk_bnact_bf16_fwd")
-        ctx.save_for_backward(x, weight, bias, mean, rstd)
-        ctx.slope = slope
-        ctx.set_materialize_grads(False)
-        return z
-
-    @staticmethod
-    def backward(ctx, gz):
-        if gz is None:
-            return (None,) * 8
-        x, weight, bias, mean, rstd = ctx.saved_tensors
-        from .models.discriminator import input_grad_only_active   # (lazy: the models package imports this module)
-
-        gx, dw, db = _BNActGradBF16.apply(gz, x, weight, bias, mean, rstd, ctx.slope)
-        if input_grad_only_active():
-            dw = db = None
-        return (gx if ctx.needs_input_grad[0] else None, dw if ctx.needs_input_grad[1] else None,
-                db if ctx.needs_input_grad[2] else None, None, None, None, None, None)
+    GRAD = _BNActGradBF16
 
 
 def bn_leaky_relu_bf16_ok(bn, x):
@@ -2735,7 +2642,7 @@ def bn_leaky_relu_bf16(x, bn, slope):
         raise RuntimeError(f"bn_leaky_relu_bf16 takes a bf16 HIP tensor; got {x.dtype} on {x.device}")
     if bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
-    return _BNActBF16.apply(_bn_aligned(x), bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum,
+    return _BNActBF16.apply(_c16(x), bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum,
                             float(slope))
 
 
@@ -2747,23 +2654,34 @@ def bn_leaky_relu_bf16(x, bn, slope):
 GN_ACT = os.environ.get("AMK_GN_ACT", "1") != "0"
 
 
-def _gn_ws(x, G):
+# The op's two element types: (dtype of x, z, gz and gx, forward, backward, workspace query); an entry point's name less
+# its "amk_" is its event's.  mean, rstd, the parameters and their gradients are f32 in both.
+_GN_F32 = (torch.float32, "amk_gnact_fwd", "amk_gnact_bwd", "amk_gnact_ws_floats")
+_GN_BF16 = (torch.bfloat16, "amk_gnact_bf16_fwd", "amk_gnact_bf16_bwd", "amk_gnact_bf16_ws_floats")
+
+
+def _gn_ws(x, G, ws_floats):
     N, C, HW = _bn_dims(x)
-    return torch.empty(int(_lib.load().amk_gnact_ws_floats(N, C, HW, G)), device=x.device, dtype=torch.float32)
+    return torch.empty(int(getattr(_lib.load(), ws_floats)(N, C, HW, G)), device=x.device, dtype=torch.float32)
 
 
 class _GNAct(torch.autograd.Function):
-    """z = act(group_norm(x)), act 0 identity, 1 swish.  Saves x, mean and rstd (N, G); y and sigma are recomputed."""
+    """z = act(group_norm(x)), act 0 identity, 1 swish.  Saves x, mean and rstd (N, G); y and sigma are recomputed.  A
+    subclass sets ELEM."""
+    ELEM = _GN_F32
 
-    @staticmethod
-    def forward(ctx, x, weight, bias, G, eps, act):
+    @classmethod
+    def forward(cls, ctx, x, weight, bias, G, eps, act):
+        ctx.elem = cls.ELEM
+        _, fwd, _, ws_floats = cls.ELEM
         N, C, HW = _bn_dims(x)
         z = torch.empty_like(x)
         mean = torch.empty((N, G), device=x.device, dtype=torch.float32)
         rstd = torch.empty((N, G), device=x.device, dtype=torch.float32)
-        with _timed("gnact_fwd"):
-            _lib.check(_lib.load().amk_gnact_fwd(_ptr(x), _ptr(weight), _ptr(bias), N, C, HW, G, float(eps), act, _ptr(z),
-                                                 _ptr(mean), _ptr(rstd), _ptr(_gn_ws(x, G)), _stream()), "amk_gnact_fwd")
+        ws = _gn_ws(x, G, ws_floats)
+        with _timed(fwd[4:]):
+            _lib.check(getattr(_lib.load(), fwd)(_ptr(x), _ptr(weight), _ptr(bias), N, C, HW, G, float(eps), act, _ptr(z),
+                                                 _ptr(mean), _ptr(rstd), _ptr(ws), _stream()), fwd)
         ctx.save_for_backward(x, weight, bias, mean, rstd)
         ctx.G, ctx.act = G, act
         return z
@@ -2772,15 +2690,16 @@ class _GNAct(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, gz):
         x, weight, bias, mean, rstd = ctx.saved_tensors
-        gz = _bn_aligned(gz)
+        dtype, _, bwd, ws_floats = ctx.elem
+        gz = _c16(gz.to(dtype))
         N, C, HW = _bn_dims(x)
         gx = torch.empty_like(x)
         dw = torch.empty_like(weight)
         db = torch.empty_like(bias)
-        with _timed("gnact_bwd"):
-            _lib.check(_lib.load().amk_gnact_bwd(_ptr(gz), _ptr(x), _ptr(weight), _ptr(bias), _ptr(mean), _ptr(rstd), N, C,
-                                                 HW, ctx.G, ctx.act, _ptr(gx), _ptr(dw), _ptr(db), _ptr(_gn_ws(x, ctx.G)),
-                                                 _stream()), "amk_gnact_bwd")
+        ws = _gn_ws(x, ctx.G, ws_floats)
+        with _timed(bwd[4:]):
+            _lib.check(getattr(_lib.load(), bwd)(_ptr(gz), _ptr(x), _ptr(weight), _ptr(bias), _ptr(mean), _ptr(rstd), N, C, HW,
+                                                 ctx.G, ctx.act, _ptr(gx), _ptr(dw), _ptr(db), _ptr(ws), _stream()), bwd)
         return (gx if ctx.needs_input_grad[0] else None, dw if ctx.needs_input_grad[1] else None,
                 db if ctx.needs_input_grad[2] else None, None, None, None)
 
@@ -2796,42 +2715,10 @@ class _GNAct(torch.autograd.Function):
 GN_ACT_BF16 = os.environ.get("AMK_GN_ACT_BF16", "1") != "0"
 
 
-class _GNActBF16(torch.autograd.Function):
+class _GNActBF16(_GNAct):
     """_GNAct on bf16 x under bf16 autocast: z and gx bf16, rounded once; mean, rstd (N, G), dgamma and dbeta f32.  Saves the
     bf16 x, mean and rstd."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, G, eps, act):
-        N, C, HW = _bn_dims(x)
-        L = _lib.load()
-        z = torch.empty_like(x)
-        mean = torch.empty((N, G), device=x.device, dtype=torch.float32)
-        rstd = torch.empty((N, G), device=x.device, dtype=torch.float32)
-        ws = torch.empty(int(L.amk_gnact_bf16_ws_floats(N, C, HW, G)), device=x.device, dtype=torch.float32)
-        with _timed("gnact_bf16_fwd"):
-            _lib.check(L.amk_gnact_bf16_fwd(_ptr(x), _ptr(weight), _ptr(bias), N, C, HW, G, float(eps), act, _ptr(z),
-                                            _ptr(mean), _ptr(rstd), _ptr(ws), _stream()), "amk_gnact_bf16_fwd")
-        ctx.save_for_backward(x, weight, bias, mean, rstd)
-        ctx.G, ctx.act = G, act
-        return z
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gz):
-        x, weight, bias, mean, rstd = ctx.saved_tensors
-        gz = _bn_aligned(gz.to(torch.bfloat16))
-        N, C, HW = _bn_dims(x)
-        L = _lib.load()
-        gx = torch.empty_like(x)
-        dw = torch.empty_like(weight)
-        db = torch.empty_like(bias)
-        ws = torch.empty(int(L.amk_gnact_bf16_ws_floats(N, C, HW, ctx.G)), device=x.device, dtype=torch.float32)
-        with _timed("gnact_bf16_bwd"):
-            _lib.check(L.amk_gnact_bf16_bwd(_ptr(gz), _ptr(x), _ptr(weight), _ptr(bias), _ptr(mean), _ptr(rstd), N, C, HW,
-                                            ctx.G, ctx.act, _ptr(gx), _ptr(dw), _ptr(db), _ptr(ws), _stream()),
-                       "amk_gnact_bf16_bwd")
-        return (gx if ctx.needs_input_grad[0] else None, dw if ctx.needs_input_grad[1] else None,
-                db if ctx.needs_input_grad[2] else None, None, None, None)
+    ELEM = _GN_BF16
 
 
 def group_norm_act_bf16_ok(gn, x):
@@ -2862,13 +2749,11 @@ def group_norm_act(x, gn, act):
     if act not in (0, 1):
         raise ValueError(f"group_norm_act: act must be 0 (identity) or 1 (swish), got {act}")
     if group_norm_act_bf16_ok(gn, x):
-        x = x if x.data_ptr() % 16 == 0 else x.clone()
-        return _GNActBF16.apply(x, gn.weight, gn.bias, gn.num_groups, gn.eps, act)
+        return _GNActBF16.apply(_c16(x), gn.weight, gn.bias, gn.num_groups, gn.eps, act)
     if not group_norm_act_ok(gn, x):
         y = gn(x)
         return y * torch.sigmoid(y) if act == 1 else y
-    x = x if x.data_ptr() % 16 == 0 else x.clone()
-    return _GNAct.apply(x, gn.weight, gn.bias, gn.num_groups, gn.eps, act)
+    return _GNAct.apply(_c16(x), gn.weight, gn.bias, gn.num_groups, gn.eps, act)
 
 
 # ---------------------------------------------------------------------------- LPIPS distance head
@@ -2955,9 +2840,7 @@ def lpips_distance(a, b, w, eps=1e-10):
     autograd gives NaN.  Everything the kernels do not take runs the torch chain."""
     if not lpips_distance_ok(a, b, w):
         return _lpips_chain(a, b, w, eps)
-    a = a if a.data_ptr() % 16 == 0 else a.clone()
-    b = b if b.data_ptr() % 16 == 0 else b.clone()
-    return _LpipsDist.apply(a, b, w.detach().reshape(-1).contiguous(), eps)
+    return _LpipsDist.apply(_c16(a), _c16(b), w.detach().reshape(-1).contiguous(), eps)
 
 
 # ---------------------------------------------------------------------------- masked-token loss head

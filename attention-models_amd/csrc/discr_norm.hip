@@ -22,12 +22,11 @@
 // the f32 arithmetic of the f32 kernels: gamma, beta, mean, rstd, the running statistics, dgamma, dbeta, the kept
 // sums, gg_gamma, gg_beta, g_gamma and every partial stay f32; y is recomputed from x in every pass and s is taken from
 // that f32 y, never from a rounded z.  SEG stays 4096 elements, so S, Q and the workspace are those of f32.
-#include "amk_bf16.h"
+#include "amk_planes.h"
 
 namespace amk_bn {
 
-constexpr int BLOCK = 256;
-constexpr int WAVES = BLOCK / 64;
+using namespace amk_planes;  // BLOCK, WAVES, Width, Vec, ld, st, Sum, Chan, block_reduce
 constexpr int64_t SEG = 4096;  // target elements per workgroup segment
 
 struct Geo {
@@ -80,52 +79,6 @@ __device__ __forceinline__ float seg_count(const Geo& g, int s) {
   return (float)((int64_t)(r.p1 - r.p0) * (r.e1 - r.e0));
 }
 
-template <int W> struct Width { static constexpr int value = W; };
-
-template <int W>
-__device__ __forceinline__ void ld(const float* p, float (&v)[W]) {
-  if constexpr (W == 4) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-    v[0] = *p;
-  }
-}
-
-template <int W>
-__device__ __forceinline__ void st(float* p, const float (&v)[W]) {
-  if constexpr (W == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  else *p = v[0];
-}
-
-template <int W>
-__device__ __forceinline__ void ld(const __bf16* p, float (&v)[W]) {
-  if constexpr (W == 8) {
-    const bf16x8 t = *reinterpret_cast<const bf16x8*>(p);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = (float)t[k];
-  } else {
-    v[0] = (float)*p;
-  }
-}
-
-// the one rounding of a bf16 output: f32 -> bf16, to nearest even
-template <int W>
-__device__ __forceinline__ void st(__bf16* p, const float (&v)[W]) {
-  if constexpr (W == 8) {
-    bf16x8 t;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) t[k] = (__bf16)v[k];
-    *reinterpret_cast<bf16x8*>(p) = t;
-  } else {
-    *p = (__bf16)v[0];
-  }
-}
-
-// elements per 16-byte access and its log2
-template <class T> struct Vec { static constexpr int W = 4, SH = 2; };
-template <> struct Vec<__bf16> { static constexpr int W = 8, SH = 3; };
-
 // Calls f(Width<VW>, off) for every aligned VW-element run (VW = 4 for f32, 8 for bf16) and f(Width<1>, off) for every
 // edge element of segment s of channel c; `off` indexes the (N, C, HW) tensor of T.  Tensor bases are 16-byte aligned.
 template <class T, class F>
@@ -143,56 +96,6 @@ __device__ __forceinline__ void seg_walk(const Geo& g, int c, int s, F&& f) {
     if (t < head) f(Width<1>{}, base + t);
     else if (t < head + tail) f(Width<1>{}, base + VW * nv + t);
   }
-}
-
-struct Sum {
-  template <int K>
-  __device__ __forceinline__ void operator()(float (&a)[K], const float (&b)[K]) const {
-#pragma unroll
-    for (int k = 0; k < K; ++k) a[k] += b[k];
-  }
-};
-
-// Chan's merge of (count, mean, M2) triples
-struct Chan {
-  __device__ __forceinline__ void operator()(float (&a)[3], const float (&b)[3]) const {
-    const float n = a[0] + b[0];
-    if (b[0] == 0.f) return;
-    if (a[0] == 0.f) { a[0] = b[0]; a[1] = b[1]; a[2] = b[2]; return; }
-    const float d = b[1] - a[1], f = b[0] / n;
-    a[1] += d * f;
-    a[2] += b[2] + d * d * a[0] * f;
-    a[0] = n;
-  }
-};
-
-// Fixed-order block reduction: a butterfly inside each wave (lane 0's result is used), then every
-// thread folds the WAVES wave results in order, so all threads return the same value.
-template <int K, class Op>
-__device__ __forceinline__ void block_reduce(float (&v)[K], Op op, float* lds) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    float w[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) w[k] = __shfl_xor(v[k], o, 64);
-    op(v, w);
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) lds[wave * K + k] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) v[k] = lds[k];
-#pragma unroll
-  for (int w = 1; w < WAVES; ++w) {
-    float u[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) u[k] = lds[w * K + k];
-    op(v, u);
-  }
-  __syncthreads();
 }
 
 // Sum of the S per-segment partials part[(c S + j) K + k] in a fixed order.

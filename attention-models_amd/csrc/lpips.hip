@@ -36,7 +36,7 @@
 //
 // bf16: T = __bf16 widens a and b to f32 on the load and rounds ga once, to nearest even, on the store; w, the rows, the
 // partials and out are f32, as is everything between.
-#include "amk_bf16.h"
+#include "amk_planes.h"
 
 // Identical inputs must give out == 0 and ga == 0 exactly: ah - bv * ib contracted to fma(-bv, ib, ah) would leave the
 // rounding error of ah behind.  So no contraction in this file; the sums say fmaf where they mean it.
@@ -44,8 +44,7 @@
 
 namespace amk_lpips {
 
-constexpr int BLOCK = 256;
-constexpr int WAVES = BLOCK / 64;
+using namespace amk_planes;  // BLOCK, WAVES, Width, Vec, ld, st, Sum, Chan, block_reduce
 constexpr int MIN_TILES = 64;  // per sample, while a smaller PL can still give them
 
 struct Geo {
@@ -70,54 +69,6 @@ static Geo make_geo(int N, int C, int64_t HW, int VW) {
   g.TP = (int64_t)g.PL * g.W;
   g.tiles = (HW + g.TP - 1) / g.TP;
   return g;
-}
-
-template <int W>
-__device__ __forceinline__ void ld(const float* p, float (&v)[W]) {
-  if constexpr (W == 4) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else if constexpr (W == 8) {  // the f32 rows of a bf16 thread's 8 pixels
-    const float4 t = *reinterpret_cast<const float4*>(p), u = *reinterpret_cast<const float4*>(p + 4);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    v[4] = u.x; v[5] = u.y; v[6] = u.z; v[7] = u.w;
-  } else {
-    v[0] = *p;
-  }
-}
-
-template <int W>
-__device__ __forceinline__ void st(float* p, const float (&v)[W]) {
-  if constexpr (W == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  else if constexpr (W == 8) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    *reinterpret_cast<float4*>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
-  } else *p = v[0];
-}
-
-template <int W>
-__device__ __forceinline__ void ld(const __bf16* p, float (&v)[W]) {
-  if constexpr (W == 8) {
-    const bf16x8 t = *reinterpret_cast<const bf16x8*>(p);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = (float)t[k];
-  } else {
-    static_assert(W == 1);
-    v[0] = (float)*p;
-  }
-}
-
-// the one rounding of ga: f32 -> bf16, to nearest even
-template <int W>
-__device__ __forceinline__ void st(__bf16* p, const float (&v)[W]) {
-  if constexpr (W == 8) {
-    bf16x8 t;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) t[k] = (__bf16)v[k];
-    *reinterpret_cast<bf16x8*>(p) = t;
-  } else {
-    *p = (__bf16)v[0];
-  }
 }
 
 // Sum of v over the channel slices of the workgroup, in a fixed order; every thread returns the total of its pixels.

@@ -177,6 +177,30 @@ def test_autograd_within_bounds(device, family, shape, full):
         assert torch.equal(v, direct[name]), name
 
 
+@pytest.mark.parametrize("gg", ["null", "given"])
+@pytest.mark.parametrize("shape", [(5, 4, 31, 31), (1, 2, 67, 67)])
+def test_ops_give_the_bits_of_the_abi(device, shape, gg):
+    """ops.bn_leaky_relu_bf16 through autograd -- the first-order gradients with create_graph, then the second grad with a
+    given ggx and gg_gamma / gg_beta absent ("null") or given -- gives, bit for bit, what _abi's sequence gives: z, the
+    updated running statistics, gx, dgamma, dbeta, g_gz, g_x and g_gamma."""
+    from amk import ops
+
+    inp, _ = _case("diffuse", shape)
+    bn = _bn(inp, device)
+    t = _dev(inp, device)
+    x, gz = t["x"].requires_grad_(), t["gz"].requires_grad_()
+    z = ops.bn_leaky_relu_bf16(x, bn, bref.SLOPE)
+    got = dict(z=z.detach(), run_mean=bn.running_mean.clone(), run_var=bn.running_var.clone())
+    gx, gw, gb = torch.autograd.grad(z, (x, bn.weight, bn.bias), gz, create_graph=True)
+    got.update(gx=gx.detach(), dgamma=gw.detach(), dbeta=gb.detach())
+    outs, cots = ((gx,), (t["ggx"],)) if gg == "null" else ((gx, gw, gb), (t["ggx"], t["gg_gamma"], t["gg_beta"]))
+    got["g_gz"], got["g_x"], got["g_gamma"] = torch.autograd.grad(outs, (gz, x, bn.weight), cots)
+    torch.cuda.synchronize()
+    want = _abi(inp, device, gg=gg)
+    for name, v in got.items():
+        assert v.dtype == want[name].dtype and torch.equal(v, want[name]), name
+
+
 def test_dtypes_and_running_statistics(device):
     """bf16: z, gx, g_gz, g_x.  f32: dgamma, dbeta, g_gamma, the running statistics.  One update of the running statistics and
     of num_batches_tracked per call.  An f32 cotangent is brought to bf16 and gives the bits of the bf16 one."""

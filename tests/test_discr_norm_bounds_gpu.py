@@ -210,6 +210,29 @@ def test_autograd_within_bounds(device, family, shape, full):
         assert torch.equal(v, direct[name]), name
 
 
+@pytest.mark.parametrize("gg", ["null", "given"])
+@pytest.mark.parametrize("shape", [(5, 4, 31, 31), (2, 3, 65, 65)])
+def test_ops_give_the_bits_of_the_abi(device, shape, gg):
+    """ops.bn_leaky_relu through autograd -- the first-order gradients with create_graph, then the second grad with a given
+    ggx and gg_gamma / gg_beta absent ("null") or given -- gives, bit for bit, what _abi's sequence gives: z, the updated
+    running statistics, gx, dgamma, dbeta, g_gz, g_x and g_gamma."""
+    from amk import ops
+
+    inp, _ = _case("diffuse", shape)
+    bn = _bn(inp, device)
+    x, gz = inp["x"].to(device).requires_grad_(), inp["gz"].to(device).requires_grad_()
+    z = ops.bn_leaky_relu(x, bn, ref.SLOPE)
+    got = dict(z=z.detach(), run_mean=bn.running_mean.clone(), run_var=bn.running_var.clone())
+    gx, gw, gb = torch.autograd.grad(z, (x, bn.weight, bn.bias), gz, create_graph=True)
+    got.update(gx=gx.detach(), dgamma=gw.detach(), dbeta=gb.detach())
+    outs, cots = ((gx,), (inp["ggx"],)) if gg == "null" else ((gx, gw, gb), (inp["ggx"], inp["gg_gamma"], inp["gg_beta"]))
+    got["g_gz"], got["g_x"], got["g_gamma"] = torch.autograd.grad(outs, (gz, x, bn.weight), [c.to(device) for c in cots])
+    torch.cuda.synchronize()
+    want = _abi(inp, device, gg=gg)
+    for name, v in got.items():
+        assert v.dtype == want[name].dtype and torch.equal(v, want[name]), name
+
+
 @pytest.mark.parametrize("shift", [("x",), ("gz",), ("ggx",), ("x", "gz", "ggx")], ids=lambda s: "+".join(s))
 def test_storage_4_bytes_off_alignment_gives_the_same_bits(device, shift):
     inp, _ = _case("diffuse", (2, 3, 65, 65))

@@ -112,6 +112,8 @@ SIGNATURES = {
     "amk_geglu_ln_bf16_bwd": (_I, [_P, _L, _P, _P, _P, _P, _L, _I, _P, _P, _P]),
     "amk_gemm_bf16": (_I, [_I, _I, _P, _L, _P, _L, _P, _P, _L, _P, _L, _L, _I, _I, _P]),
     "amk_gemm_bf16_swiglu_bwd": (_I, [_P, _L, _P, _L, _P, _L, _P, _L, _L, _I, _I, _P]),
+    "amk_cfg_layernorm_bf16": (_I, [_P, _I, _P, _I, _P, _P, _F, _L, _I, _F, _P, _P]),
+    "amk_gemm_bf16_f32out": (_I, [_P, _L, _P, _L, _P, _P, _L, _L, _I, _I, _P]),
     "amk_gemm_tn_bf16_ws_bytes": (_L, [_L, _I, _I]),
     "amk_gemm_tn_bf16": (_I, [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _P, _L, _P]),
     "amk_sample_step": (_I, [_P, _P, _F, _P, _c.c_uint64, _c.c_uint64, _F, _L, _I, _I, _P, _F, _P, _P, _P]),

@@ -94,12 +94,20 @@ class MaskGitTransformer(nn.Module):
         return F.cross_entropy(output.transpose(1, 2), tgt, ignore_index=-1)
 
     @torch.no_grad()
-    def generate(self, batch=1, timesteps=18, device=None):
+    def generate(self, batch=1, timesteps=18, device=None, trace=None, logits_trace=None):
         """Confidence-based parallel decode from an all-mask canvas (models/maskgit.py:193-287 without the
         in-painting / JPEG-dump branches): per step re-mask the least confident tokens (cosine schedule),
-        one transformer pass, top-(1-p) filtered Gumbel sampling at an annealed temperature."""
+        one transformer pass, top-(1-p) filtered Gumbel sampling at an annealed temperature.
+        Under bf16 autocast with fused_sampling (ops.guided_logits_ok) the logits are f32, from the hidden states by
+        ops.guided_logits (final_norm to bf16 + one bf16 product with f32 output).  trace / logits_trace: lists that
+        receive the ids entering the transformer at every step / each step's f32 logits on that path."""
         n = self.vq.num_patches
-        dev = device or self.bidirectional_transformer.pos_enc.device
+        bt = self.bidirectional_transformer
+        dev = device or bt.pos_enc.device
+        head = bt.linear.weight
+        guided = self.fused_sampling and ops.guided_logits_ok(bt.pos_enc, head)
+        w16 = ops._w16(head) if guided else None                         # the head's bf16 weight, taken once
+        sampler_ok = head.shape[0] % 4 == 0 and head.shape[0] <= 36864   # amk_sample_step's range of V
         ids = torch.full((batch, n), self.mask_token_id, dtype=torch.long, device=dev)
         scores = torch.zeros(batch, n, device=dev)
         mask = torch.zeros(batch, n, dtype=torch.bool, device=dev)
@@ -109,9 +117,16 @@ class MaskGitTransformer(nn.Module):
             low = torch.argsort(scores, dim=-1)[:, :n_masked]
             mask.scatter_(1, low, True)
             x = ids.masked_fill(mask, self.mask_token_id)
-            logits = self.bidirectional_transformer(x)
+            if trace is not None:
+                trace.append(x.clone())
+            if guided:
+                logits = ops.guided_logits(bt.hidden(x), bt.final_norm.gamma, bt.final_norm.beta, head, w16=w16)
+                if logits_trace is not None:
+                    logits_trace.append(logits)
+            else:
+                logits = self.bidirectional_transformer(x)
             temperature = 1 * (steps_until_x0 / timesteps)
-            if self.fused_sampling:
+            if self.fused_sampling and (sampler_ok or not guided):
                 scores = ops.sample_step(logits, ids, mask=mask, tau=temperature, p=0.9, unmasked_score=1.0)
             else:
                 probs = F.softmax(logits, dim=-1)

@@ -118,17 +118,27 @@ class MUSE(nn.Module):
 
 
 @torch.no_grad()
-def parallel_decode(decoder, ctx, mask_token_id, n, timesteps=18, fused_sampling=True, gumbel=None, trace=None):
+def parallel_decode(decoder, ctx, mask_token_id, n, timesteps=18, fused_sampling=True, gumbel=None, trace=None,
+                    logits_trace=None):
     """The masked-token parallel decode of MUSE.generate (models/muse.py:180-236): per step, re-mask the least
     confident tokens (cosine schedule), run the decoder with and without the text context, sample every masked
     token.  gumbel: explicit noise (timesteps, B, n, V) in place of the sampler's own (tests replay the reference's
-    draw); trace: a list that receives the ids entering the decoder at every step.  Returns the final ids (B, n)."""
+    draw); trace: a list that receives the ids entering the decoder at every step.  Returns the final ids (B, n).
+
+    Under bf16 autocast with fused_sampling (ops.guided_logits_ok): the two passes stop at the decoder's hidden states
+    and ops.guided_logits applies the guidance to the normalised activations -- one bf16 logits product per step, f32
+    guided logits, the sampler on those (null_logits=None).  logits_trace: a list that receives each step's guided f32
+    logits on that path."""
     dev = ctx.device
     B = ctx.shape[0]
     ids = torch.full((B, n), mask_token_id, dtype=torch.long, device=dev)
     scores = torch.zeros(B, n, device=dev)
     mask = torch.zeros(B, n, dtype=torch.bool, device=dev)
     null_ctx = torch.zeros_like(ctx)
+    head = decoder.linear.weight
+    guided = fused_sampling and ops.guided_logits_ok(decoder.pos_enc, head)
+    w16 = ops._w16(head) if guided else None                         # the head's bf16 weight, taken once
+    sampler_ok = head.shape[0] % 4 == 0 and head.shape[0] <= 36864   # amk_sample_step's range of V
     for step, t in enumerate(torch.linspace(0, 1, timesteps, device=dev)):
         steps_until_x0 = timesteps - 1 - step
         n_masked = max(int((cosine_schedule(t) * n).item()), 1)
@@ -137,17 +147,26 @@ def parallel_decode(decoder, ctx, mask_token_id, n, timesteps=18, fused_sampling
         ids = ids.masked_fill(mask, mask_token_id)
         if trace is not None:
             trace.append(ids.clone())
-        logits = decoder(ids, context=ctx)                          # two decoder passes per step:
-        null_logits = decoder(ids, context=null_ctx)                # conditional + unconditional
+        if guided:
+            fn = decoder.final_norm
+            logits = ops.guided_logits(decoder.hidden(ids, context=ctx), fn.gamma, fn.beta, head,
+                                       null_h=decoder.hidden(ids, context=null_ctx), cfg_scale=3.0, w16=w16)
+            null_logits = None                                      # the guidance is inside logits already
+            if logits_trace is not None:
+                logits_trace.append(logits)
+        else:
+            logits = decoder(ids, context=ctx)                      # two decoder passes per step:
+            null_logits = decoder(ids, context=null_ctx)            # conditional + unconditional
         temperature = 1 * (steps_until_x0 / timesteps)
         noise = gumbel[step] if gumbel is not None else None
-        if fused_sampling:
+        if fused_sampling and (sampler_ok or not guided):
             # CFG (scale 3) + softmax + top-(1-p) filter + Gumbel-argmax + score gather + masked write:
             # one pass over the logits (csrc/sample.hip) instead of the op chain below
             scores = ops.sample_step(logits, ids, mask=mask, null_logits=null_logits, cfg_scale=3.0,
                                      tau=temperature, p=0.9, gumbel=noise)
         else:
-            scaled = null_logits + 3 * (logits - null_logits)       # classifier-free guidance, scale 3
+            # classifier-free guidance, scale 3 (guided: done on the activations)
+            scaled = logits if guided else null_logits + 3 * (logits - null_logits)
             probs = F.softmax(scaled, dim=-1)
             filt = filter_logits(scaled, p=0.9)
             if noise is None:

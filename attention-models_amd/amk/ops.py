@@ -2473,6 +2473,71 @@ def geglu_ffn(x, w1, gamma, beta, w2, eps=1e-5):
     return torch.nn.functional.linear(layer_norm(g, gamma, beta, eps), w2)
 
 
+# ---------------------------------------------------------------------------- guided logits head of the parallel decode
+# AMK_GUIDED_HEAD (default 1): under bf16 autocast MUSE.generate, parallel_decode and MaskGitTransformer.generate take the
+# logits of each step from the decoder's hidden states by guided_logits below -- classifier-free guidance applied to the
+# normalised activations (the head's Linear has no bias and the guidance is linear in the logits), one bf16 product with
+# f32 logits, and the sampler on those.  0: the decode under autocast is what it was before this head existed: with
+# fused_sampling it raises ("amk kernels compute in fp32"), without it the torch chain runs on bf16 logits.  Measurements:
+# DESIGN.md section 4g.1, profiles/kbench_muse_generate.log.  Read once per process.
+GUIDED_HEAD = os.environ.get("AMK_GUIDED_HEAD", "1") != "0"
+
+
+def guided_logits_ok(h, weight):
+    """The models' gate for guided_logits: the switch and bf16 autocast are on, HIP tensors, hidden states in f32 or bf16,
+    an f32 master weight (V, dim) with dim and V multiples of 8, and a width the LayerNorm kernel takes."""
+    if not (GUIDED_HEAD and h.is_cuda and weight.is_cuda and _bf16_autocast()):
+        return False
+    dim = h.shape[-1]
+    return (weight.dtype == torch.float32 and h.dtype in (torch.float32, torch.bfloat16) and weight.dim() == 2
+            and weight.shape[1] == dim and dim % 8 == 0 and weight.shape[0] % 8 == 0 and _ln_supported(dim) and h.numel() > 0)
+
+
+def guided_logits(h, gamma, beta, weight, null_h=None, cfg_scale=3.0, eps=1e-5, w16=None):
+    """f32 logits (..., V) of the parallel decode's head from the decoder's hidden states h (..., dim), f32 or bf16:
+    weight @ (LN(null_h) + cfg_scale (LN(h) - LN(null_h))) with the LayerNorms and the combination in f32, rounded to bf16
+    once (amk_cfg_layernorm_bf16), then one bf16 product whose f32 accumulators are the result (amk_gemm_bf16_f32out).
+    null_h None: weight @ LN(h).  w16: a bf16 copy of weight the caller made once; else the optimizer's shadow if it is
+    current, else a cast.  Inference only, no autograd; runs with autocast disabled inside."""
+    if not (h.is_cuda and weight.is_cuda):
+        raise RuntimeError("amk ops run only on MI355X (HIP) tensors; got a CPU tensor. There is no CPU fallback.")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (h, null_h, gamma, beta, weight)):
+        raise RuntimeError("guided_logits is inference only: it has no backward; call it under torch.no_grad()")
+    V, dim = weight.shape
+    if h.shape[-1] != dim or dim % 8 or V % 8 or not _ln_supported(dim) or (null_h is not None and null_h.shape != h.shape):
+        raise RuntimeError(f"guided_logits: hidden {tuple(h.shape)}, weight {tuple(weight.shape)}: dim and V must be multiples "
+                           "of 8, dim at most 4096, and both hidden states of one shape")
+    with torch.autocast("cuda", enabled=False):
+        if w16 is None:
+            w16 = _w16(weight.detach())
+        if w16.dtype != torch.bfloat16 or tuple(w16.shape) != (V, dim):
+            raise RuntimeError(f"guided_logits: w16 must be the bf16 copy of weight; got {w16.dtype} {tuple(w16.shape)}")
+        w16 = _row_major_view(w16, 8)
+
+        def rows(t):
+            if t.dtype not in (torch.float32, torch.bfloat16):
+                raise RuntimeError(f"guided_logits: hidden states in f32 or bf16; got {t.dtype}")
+            t2 = t.detach().reshape(-1, dim)
+            return t2 if t2.is_contiguous() and t2.data_ptr() % 16 == 0 else t2.contiguous().clone()
+
+        hc = rows(h)
+        hn = rows(null_h) if null_h is not None else None
+        gm, bt = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
+        M = hc.shape[0]
+        L = _lib.load()
+        u = torch.empty((M, dim), device=h.device, dtype=torch.bfloat16)
+        with _timed(f"cfg_layernorm_bf16 M{M} D{dim}"):
+            rc = L.amk_cfg_layernorm_bf16(_ptr(hc), int(hc.dtype == torch.bfloat16), _ptr(hn),
+                                          int(hn is not None and hn.dtype == torch.bfloat16), _ptr(gm), _ptr(bt),
+                                          float(cfg_scale), M, dim, float(eps), _ptr(u), _stream())
+        _lib.check(rc, "amk_cfg_layernorm_bf16")
+        logits = torch.empty((M, V), device=h.device, dtype=torch.float32)
+        with _timed(f"gemm_bf16_f32out N{V} K{dim}"):
+            rc = L.amk_gemm_bf16_f32out(_ptr(u), dim, _ptr(w16), w16.stride(0), _NULL, _ptr(logits), V, M, V, dim, _stream())
+        _lib.check(rc, "amk_gemm_bf16_f32out")
+    return logits.view(*h.shape[:-1], V)
+
+
 # ---------------------------------------------------------------------------- discriminator BatchNorm + LeakyReLU
 # AMK_DISCR_NORM: "amk" (default) = the training-mode BatchNorm2d + LeakyReLU pairs of NLayerDiscriminator run on
 # csrc/discr_norm.hip (forward, backward and the gradient penalty's double backward); "aten" = the modules as they are

@@ -185,7 +185,9 @@ __global__ __launch_bounds__(256) void tn_bf16_reduce_kernel(Params p) {
 // the one rounding.  EPI 1 (NT only): the SwiGLU gate folded in -- the tile holds 64 gate columns j and the matching 64
 // value columns H + j, and G[m, j] = silu(a) b leaves with (or instead of) the (a | b) tile.  EPI 2 (NN only): the
 // gate's backward folded in -- the product is dG (M, H), and what leaves is (dA | dB) (M, 2 H) from the forward's (a | b):
-// dG is rounded to bf16 as the unfused pair of launches would hand it over, then combined in the row pass.
+// dG is rounded to bf16 as the unfused pair of launches would hand it over, then combined in the row pass.  EPI 3 / 4 (NT
+// only): C in f32, the accumulators (bias added) stored as they are -- through the LDS tile in two passes of 64 columns
+// (3), or 16 bytes per lane straight from the registers (4); amk_gemm_bf16_f32out below.
 //   tile 128 x 128, four waves as 2 x 2 of 64 x 64, contraction in steps of 32, two tiles of the step stream in flight
 //   in registers beside the one in LDS, four workgroups per CU (K is 256 for most of these products: a tile is eight
 //   steps, so its prologue and epilogue are hidden by the CU's other workgroups, not by its own loop).
@@ -198,6 +200,7 @@ constexpr int FSTR = 32;            // bf16 per LDS row of a [128 rows][32 k] op
                                     // chunks of row r sit at chunk ^ ((r >> 2) & 3) (writes and b128 reads conflict-free)
 constexpr int FT = 32 * STR;        // elements per operand tile buffer (the [32 k][128 n] tile of the NN form; >= 128 * FSTR)
 constexpr int OSTR = 136;           // bf16 per row of the output tile in LDS
+constexpr int OSTRF = 68;           // f32 per row of a 64-column half of the f32 output tile: the same 34816 bytes
 
 struct FParams {
   const __bf16 *a, *w, *ab;
@@ -382,6 +385,42 @@ __global__ __launch_bounds__(256, 4) void gemm_bf16_kernel(FParams p) {
       }
     }
   }
+  if (EPI == 3) {   // f32 out through LDS: n block i of every wave per pass -- tile columns 32 wn + (0..31) are local 64 wn + 32 i + (0..31)
+    float* cf = reinterpret_cast<float*>(p.c);
+    float* otf = reinterpret_cast<float*>(smem);   // [128][OSTRF] f32: the bf16 tile's bytes
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      if (i) lds_barrier();   // (pass 0 has been read out)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+          *reinterpret_cast<float4*>(&otf[(64 * wm + 32 * j + ln) * OSTRF + 32 * wn + 8 * g + 4 * hf]) =
+              make_float4(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]);
+      lds_barrier();
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int pc = tid + 256 * q, row = pc >> 4, lc = 4 * (pc & 15);
+        const int n = n0 + 64 * (lc >> 5) + 32 * i + (lc & 31);
+        if (row < mrows && n < p.N) *reinterpret_cast<float4*>(cf + (m0 + row) * p.ldc + n) = *reinterpret_cast<const float4*>(&otf[row * OSTRF + lc]);
+      }
+    }
+  }
+  if (EPI == 4) {   // f32 out straight from the accumulators: 16 bytes per lane, 32 contiguous bytes per row and half-wave pair
+    float* cf = reinterpret_cast<float*>(p.c);
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int row = 64 * wm + 32 * j + ln;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int n = n0 + 64 * wn + 32 * i + 8 * g + 4 * hf;
+          if (row < mrows && n < p.N)
+            *reinterpret_cast<float4*>(cf + (m0 + row) * p.ldc + n) = make_float4(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]);
+        }
+      }
+  }
   if (EPI == 1) {
     lds_barrier();
 #pragma unroll
@@ -524,6 +563,41 @@ extern "C" int amk_gemm_bf16(int op, int epi, const void* a, int64_t lda, const 
   else if (epi == 1) hipLaunchKernelGGL((gemm_bf16_kernel<false, 1>), dim3((unsigned)total), dim3(256), 0, st, p);
   else hipLaunchKernelGGL((gemm_bf16_kernel<false, 0>), dim3((unsigned)total), dim3(256), 0, st, p);
   AMK_CHECK_LAUNCH("amk_gemm_bf16");
+  return AMK_OK;
+}
+
+
+// c (M, N) f32 = a w^T (+ bias): op 0 with the accumulators stored as they are, no rounding to bf16 -- the logits head of
+// the masked-token decode, whose sampler takes f32.  The two output paths (through the LDS tile in two 64-column halves,
+// or 16 bytes per lane straight from the accumulators) are both built; AMK_GEMM16_F32OUT=direct|lds overrides the choice
+// (read at every call, so that one process can time both: tools/kbench_muse_generate.py).
+static bool f32out_direct() {
+  const char* e = getenv("AMK_GEMM16_F32OUT");
+  return e && e[0] == 'd';
+}
+
+extern "C" int amk_gemm_bf16_f32out(const void* a, int64_t lda, const void* w, int64_t ldw, const float* bias, float* c, int64_t ldc,
+                                    int64_t M, int N, int K, void* stream) {
+  AMK_CHECK_ARG(a && w && c, "amk_gemm_bf16_f32out: null operand");
+  AMK_CHECK_ARG(M > 0 && N > 0 && K > 0, "amk_gemm_bf16_f32out: non-positive size");
+  AMK_CHECK_SUPPORTED(N % 8 == 0 && K % 8 == 0 && lda % 8 == 0 && ldw % 8 == 0 && ldc % 4 == 0,
+                      "amk_gemm_bf16_f32out: N, K and the bf16 leading dimensions must be multiples of 8, ldc of 4");
+  AMK_CHECK_ARG(lda >= K && ldw >= K && ldc >= N, "amk_gemm_bf16_f32out: a leading dimension below its row length");
+  AMK_CHECK_ARG(((uintptr_t)a & 15) == 0 && ((uintptr_t)w & 15) == 0 && ((uintptr_t)c & 15) == 0 && ((uintptr_t)bias & 15) == 0,
+                "amk_gemm_bf16_f32out: pointers must be 16-byte aligned");
+  AMK_CHECK_SUPPORTED(128 * lda * 2 < (1ll << 30) && (int64_t)N * ldw * 2 < (1ll << 30), "amk_gemm_bf16_f32out: operand panel beyond 1 GiB");
+  FParams p = {};
+  p.a = static_cast<const __bf16*>(a); p.w = static_cast<const __bf16*>(w); p.bias = bias;
+  p.c = reinterpret_cast<__bf16*>(c);   // (the f32 epilogues read it back as float*)
+  p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.H = N / 2;
+  p.ntn = (N + 127) / 128;
+  const int64_t total = ((M + 127) / 128) * p.ntn;
+  AMK_CHECK_SUPPORTED(total < (1ll << 31), "amk_gemm_bf16_f32out: grid too large");
+  p.total = (int)total;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (f32out_direct()) hipLaunchKernelGGL((gemm_bf16_kernel<false, 4>), dim3((unsigned)total), dim3(256), 0, st, p);
+  else hipLaunchKernelGGL((gemm_bf16_kernel<false, 3>), dim3((unsigned)total), dim3(256), 0, st, p);
+  AMK_CHECK_LAUNCH("amk_gemm_bf16_f32out");
   return AMK_OK;
 }
 

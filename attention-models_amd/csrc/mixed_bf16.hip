@@ -8,6 +8,8 @@
 //   add_layernorm_mixed_fwd  h = x (+ res) with x f32 or bf16 (a branch output) and res f32 (the residual stream);
 //                            h f32, y = LN(h) * gamma + beta in bf16 (its consumers are bf16 GEMMs), mean / rstd f32
 //   add_layernorm_mixed_bwd  dy bf16 or f32, h f32 -> dh f32 (+ dh_in), and a bf16 copy of dh for the bf16 branch
+//   cfg_layernorm_bf16       the head of the masked-token decode (models/muse.py:211-217): two rows, each normalised with
+//                            its own statistics, combined as yn + s (yc - yn) in f32, one rounding to bf16
 // One wave per row, 4 elements per lane and chunk, two-pass statistics -- the structure of layernorm.hip.
 #include "amk_bf16.h"
 
@@ -112,6 +114,78 @@ __global__ __launch_bounds__(64 * WAVES) void ln_mixed_fwd_kernel(const void* __
                                               v[j].z * rstd * g[j].z + b[j].z, v[j].w * rstd * g[j].w + b[j].w));
     }
     if (lane == 0) { mean_out[row] = mean; rstd_out[row] = rstd; }
+  }
+}
+
+// The head of the masked-token decode under classifier-free guidance: rows c (conditional pass) and n (unconditional
+// pass) are each normalised with their own statistics, yc = xhat_c gamma + beta and yn likewise, and what leaves is
+// u = yn + s (yc - yn), combined in f32 and rounded to bf16 once -- the activation of ONE logits product, since the
+// head's Linear has no bias and the guidance is linear in the logits.  HAS_N false: u = yc (plain LayerNorm to bf16).
+// CB / NB: the rows are bf16.  Statistics exactly as ln_mixed_fwd_kernel: two passes over the registers, one wave per row.
+template <int NCH, bool CB, bool NB, bool HAS_N>
+__global__ __launch_bounds__(64 * WAVES) void cfg_ln_bf16_kernel(const void* __restrict__ cv, const void* __restrict__ nv,
+                                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                 float s, int64_t M, int D, float eps, __bf16* __restrict__ y) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int nch = D >> 2;
+  constexpr bool HOLD = !(HAS_N && NCH == 16);   // (two rows of 4096 and gamma, beta: 256 registers -- re-read those per row)
+  float4 g[NCH], b[NCH];   // (not held: never written, never read)
+  if (HOLD) {
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+      const int c = lane + 64 * j;
+      g[j] = c < nch ? ld4(gamma + 4 * c) : make_float4(0.f, 0.f, 0.f, 0.f);
+      b[j] = c < nch ? ld4(beta + 4 * c) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
+  const float inv_d = 1.f / (float)D;
+  for (int64_t row = (int64_t)blockIdx.x * WAVES + wave; row < M; row += (int64_t)gridDim.x * WAVES) {
+    float4 vc[NCH], vn[HAS_N ? NCH : 1];
+    float sc = 0.f, sn = 0.f;
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+      const int c = lane + 64 * j;
+      vc[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (HAS_N) vn[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (c < nch) {
+        vc[j] = CB ? ldb4(static_cast<const __bf16*>(cv) + row * D + 4 * c) : ld4(static_cast<const float*>(cv) + row * D + 4 * c);
+        sc += vc[j].x + vc[j].y + vc[j].z + vc[j].w;
+        if (HAS_N) {
+          vn[j] = NB ? ldb4(static_cast<const __bf16*>(nv) + row * D + 4 * c) : ld4(static_cast<const float*>(nv) + row * D + 4 * c);
+          sn += vn[j].x + vn[j].y + vn[j].z + vn[j].w;
+        }
+      }
+    }
+    const float mc = wave_sum(sc) * inv_d, mn = HAS_N ? wave_sum(sn) * inv_d : 0.f;
+    float qc = 0.f, qn = 0.f;
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+      const int c = lane + 64 * j;
+      if (c < nch) {
+        vc[j].x -= mc; vc[j].y -= mc; vc[j].z -= mc; vc[j].w -= mc;
+        qc += vc[j].x * vc[j].x + vc[j].y * vc[j].y + vc[j].z * vc[j].z + vc[j].w * vc[j].w;
+        if (HAS_N) {
+          vn[j].x -= mn; vn[j].y -= mn; vn[j].z -= mn; vn[j].w -= mn;
+          qn += vn[j].x * vn[j].x + vn[j].y * vn[j].y + vn[j].z * vn[j].z + vn[j].w * vn[j].w;
+        }
+      }
+    }
+    const float rc = rsqrtf(wave_sum(qc) * inv_d + eps), rn = HAS_N ? rsqrtf(wave_sum(qn) * inv_d + eps) : 0.f;
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+      const int c = lane + 64 * j;
+      if (c < nch) {
+        const float4 gj = HOLD ? g[j] : ld4(gamma + 4 * c), bj = HOLD ? b[j] : ld4(beta + 4 * c);
+        float4 u = make_float4(vc[j].x * rc * gj.x + bj.x, vc[j].y * rc * gj.y + bj.y,
+                               vc[j].z * rc * gj.z + bj.z, vc[j].w * rc * gj.w + bj.w);
+        if (HAS_N) {
+          const float4 n = make_float4(vn[j].x * rn * gj.x + bj.x, vn[j].y * rn * gj.y + bj.y,
+                                       vn[j].z * rn * gj.z + bj.z, vn[j].w * rn * gj.w + bj.w);
+          u = make_float4(n.x + s * (u.x - n.x), n.y + s * (u.y - n.y), n.z + s * (u.z - n.z), n.w + s * (u.w - n.w));
+        }
+        stb4(y + row * D + 4 * c, u);
+      }
+    }
   }
 }
 
@@ -252,6 +326,32 @@ extern "C" int amk_add_layernorm_mixed_fwd(const void* x, int x_is_bf16, const f
   AMK_MX_DISPATCH(D, CALL);
 #undef CALL
   AMK_CHECK_LAUNCH("amk_add_layernorm_mixed_fwd");
+  return AMK_OK;
+}
+
+extern "C" int amk_cfg_layernorm_bf16(const void* hc, int hc_is_bf16, const void* hn, int hn_is_bf16, const float* gamma,
+                                      const float* beta, float cfg_scale, int64_t M, int D, float eps, void* y_bf16, void* stream) {
+  AMK_CHECK_ARG(hc && gamma && beta && y_bf16, "amk_cfg_layernorm_bf16: null pointer");
+  AMK_CHECK_ARG(M > 0 && D > 0, "amk_cfg_layernorm_bf16: non-positive size");
+  AMK_CHECK_SUPPORTED(D % 4 == 0 && D <= 4096, "amk_cfg_layernorm_bf16: width %d not supported (multiple of 4, <= 4096)", D);
+  AMK_CHECK_ARG(a16(hc) && a16(hn) && a16(gamma) && a16(beta) && a16(y_bf16), "amk_cfg_layernorm_bf16: misaligned pointer");
+  // scale 1 is the conditional row alone: yn + 1 (yc - yn) rounds twice on the way to yc, the one-input kernel not at all
+  if (cfg_scale == 1.f) hn = nullptr;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int64_t wg = (M + WAVES - 1) / WAVES;
+  const dim3 grid((unsigned)(wg < 16384 ? wg : 16384)), block(64 * WAVES);
+  __bf16* y = static_cast<__bf16*>(y_bf16);
+  const bool cb = hc_is_bf16 != 0, nb = hn_is_bf16 != 0;
+#define CALL(NCH)                                                                                                                                      \
+  if (!hn && cb) hipLaunchKernelGGL((cfg_ln_bf16_kernel<NCH, true, false, false>), grid, block, 0, st, hc, hn, gamma, beta, cfg_scale, M, D, eps, y);  \
+  else if (!hn) hipLaunchKernelGGL((cfg_ln_bf16_kernel<NCH, false, false, false>), grid, block, 0, st, hc, hn, gamma, beta, cfg_scale, M, D, eps, y);  \
+  else if (cb && nb) hipLaunchKernelGGL((cfg_ln_bf16_kernel<NCH, true, true, true>), grid, block, 0, st, hc, hn, gamma, beta, cfg_scale, M, D, eps, y); \
+  else if (cb) hipLaunchKernelGGL((cfg_ln_bf16_kernel<NCH, true, false, true>), grid, block, 0, st, hc, hn, gamma, beta, cfg_scale, M, D, eps, y);      \
+  else if (nb) hipLaunchKernelGGL((cfg_ln_bf16_kernel<NCH, false, true, true>), grid, block, 0, st, hc, hn, gamma, beta, cfg_scale, M, D, eps, y);      \
+  else hipLaunchKernelGGL((cfg_ln_bf16_kernel<NCH, false, false, true>), grid, block, 0, st, hc, hn, gamma, beta, cfg_scale, M, D, eps, y)
+  AMK_MX_DISPATCH(D, CALL);
+#undef CALL
+  AMK_CHECK_LAUNCH("amk_cfg_layernorm_bf16");
   return AMK_OK;
 }
 

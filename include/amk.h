@@ -837,6 +837,29 @@ int amk_gemm_bf16(int op, int epi, const void* a, int64_t lda, const void* w, in
 int amk_gemm_bf16_swiglu_bwd(const void* dy, int64_t lddy, const void* w3, int64_t ldw, const void* ab, int64_t ldab,
                              void* dab, int64_t lddab, int64_t M, int H, int K, void* stream);
 
+/* ----------------------------------------------------------------------------
+ * The logits head of the masked-token decode under bf16 autocast (models/muse.py:211-217: two decoder passes, each ending
+ * in final_norm + a bias-free Linear, combined as null + s (logits - null); models/maskgit.py:248: the same head, one pass,
+ * no guidance).  The Linear has no bias and the guidance is linear, so the combination is taken on the normalised
+ * activations and ONE product gives the guided logits:  null + s (cond - null) = W (LN(h_null) + s (LN(h_cond) - LN(h_null))).
+ *
+ * amk_cfg_layernorm_bf16 (csrc/mixed_bf16.hip): row m of hc and of hn (M, D), each f32 or bf16 (hc_is_bf16 / hn_is_bf16),
+ *   is normalised with its own f32 two-pass mean and rstd, y = xhat gamma + beta; the rows are combined in f32 as
+ *   u = yn + cfg_scale (yc - yn) and u is rounded to bf16 once (nearest even) into y (M, D).  hn NULL: u = yc, a plain
+ *   LayerNorm to bf16; cfg_scale == 1 takes that path too (u = yc exactly).  No atomics, no workspace; row m is bitwise
+ *   independent of M.  D a multiple of 4 up to 4096, else AMK_EUNSUPPORTED; AMK_EINVAL: a null hc / gamma / beta / y,
+ *   M <= 0 or D <= 0, a pointer off 16-byte alignment.  A refused call launches nothing and writes nothing.
+ *
+ * amk_gemm_bf16_f32out (csrc/gemm_bf16.hip): c (M, N) f32 = a (M, K) w (N, K)^T (+ f32 bias), bf16 operands, accumulation on
+ *   v_mfma_f32_32x32x16_bf16 exactly as amk_gemm_bf16 op 0, the accumulator stored as it is: the logits are never rounded
+ *   to bf16.  N, K, lda, ldw multiples of 8, ldc of 4, operand panels below 1 GiB (AMK_EUNSUPPORTED); pointers 16-byte
+ *   aligned, leading dimensions no shorter than their rows (AMK_EINVAL); bias may be NULL.
+ * -------------------------------------------------------------------------- */
+int amk_cfg_layernorm_bf16(const void* hc, int hc_is_bf16, const void* hn, int hn_is_bf16, const float* gamma,
+                           const float* beta, float cfg_scale, int64_t M, int D, float eps, void* y_bf16, void* stream);
+int amk_gemm_bf16_f32out(const void* a, int64_t lda, const void* w, int64_t ldw, const float* bias, float* c, int64_t ldc,
+                         int64_t M, int N, int K, void* stream);
+
 /* --------------------------------------------------------------------------
  * Training-mode BatchNorm2d + LeakyReLU(slope) of the PatchGAN discriminator (csrc/discr_norm.hip), f32, contiguous
  * NCHW x (N, C, HW); reference: models/utils/discriminator.py:34-35,42-43 (BatchNorm2d followed by LeakyReLU(0.2)).

@@ -862,12 +862,33 @@ def _moe_dense_z(width, depth, fan, E):
     return MOE_DENSE_Z and E <= 2 * fan and width >= 256 and width >= 4 * depth and depth % 4 == 0
 
 
-def _expert_sums(a2, a_div, ids, scale, G, fan, E, d):
-    """Z (G, E*d): per output row and expert, the (scaled) sum of the rows of a2 its pairs read."""
-    Z = torch.empty((G, E * d), device=a2.device, dtype=torch.float32)
-    with _timed(f"moe_expert_sums G{G} fan{fan} E{E} d{d}"):
-        rc = _lib.load().amk_moe_expert_sums(_ptr(a2), a2.stride(0), a_div, _ptr(ids), scale, G, fan, E, d, _ptr(Z), _stream())
-    _lib.check(rc, "amk_moe_expert_sums")
+class _MoeElem:
+    """The element type of a Function's expert products: label prefix, dtype of the operands and of Z, and the names of its
+    entry points, put together once.  Routing, combine and gate gradient are the f32 kernels for every element type."""
+
+    def __init__(self, prefix, suffix, dtype, wgrad_db):
+        self.prefix, self.dtype, self.f32 = prefix, dtype, dtype == torch.float32
+        self.nt, self.nn, self.wgrad = (f"amk_grouped_gemm_{kind}{suffix}" for kind in ("nt", "nn", "wgrad"))
+        self.wgrad_db = wgrad_db   # the weight gradient's entry point takes a bias gradient
+        self.sums = "amk_moe_expert_sums" if self.f32 else "amk_moe_expert_sums_bf16"
+
+
+_MOE_F32 = _MoeElem("", "", torch.float32, True)                     # csrc/moe.hip
+_MOE_BF16 = _MoeElem("bf16_", "_bf16", torch.bfloat16, True)         # csrc/moe_bf16.hip, 256-output tiles (MoELayer)
+_MOE_BF16_64 = _MoeElem("bf16_", "64_bf16", torch.bfloat16, False)   # its 64-output tiles (SwitchHead, d <= 64)
+
+
+def _expert_sums(a2, a_div, ids, scale, G, fan, E, d, elem=_MOE_F32):
+    """Z (G, E*d): per output row and expert, the (scaled) sum of the rows of a2 its pairs read.  scale: a pointer.  bf16
+    elements: the same f32 sums rounded once into a bf16 Z; a2 f32 or bf16."""
+    Z = torch.empty((G, E * d), device=a2.device, dtype=elem.dtype)
+    fn = getattr(_lib.load(), elem.sums)
+    with _timed(f"{elem.prefix}moe_expert_sums G{G} fan{fan} E{E} d{d}"):
+        if elem.f32:
+            rc = fn(_ptr(a2), a2.stride(0), a_div, _ptr(ids), scale, G, fan, E, d, _ptr(Z), _stream())
+        else:
+            rc = fn(_ptr(a2), int(a2.dtype == torch.bfloat16), a2.stride(0), a_div, _ptr(ids), scale, G, fan, E, d, _ptr(Z), _stream())
+    _lib.check(rc, elem.sums)
     return Z
 
 
@@ -876,6 +897,164 @@ def _moe_sum_in_gemm(width, depth, fan):
     if not MOE_SUM_IN_GEMM or DETERMINISTIC_ATTENTION_BACKWARD or torch.are_deterministic_algorithms_enabled():
         return False
     return fan >= 4 and width >= 128 and depth % 32 == 0
+
+
+_DISTINCT = " (distinct rows)"   # label of a launch on amk_moe_route_distinct's lists: it stands for `pairs` routed pairs
+
+
+def _grouped(nn, elem, A, lda, a_div, W, vec, offsets, perm, P, pairs=None, note=""):
+    """One expert product for ALL experts, f32 result: pair p reads row p // a_div of A (row stride lda) and the matrix W[e]
+    (N, Kd) of its expert.  nt: Y (P, N) = row x W[e]^T + vec[e] (bias (E, N)); nn: Y (P, Kd) = vec[p] (scale (P,)) x row
+    x W[e]; vec may be None."""
+    E, N, Kd = W.shape
+    name = elem.nn if nn else elem.nt
+    Y = torch.empty((P, Kd if nn else N), device=A.device, dtype=torch.float32)
+    with _timed(f"{elem.prefix}grouped_{'nn' if nn else 'nt'} P{pairs or P} N{N} K{Kd}{note}"):
+        rc = getattr(_lib.load(), name)(_ptr(A), lda, a_div, _ptr(W), _ptr(vec), _ptr(offsets), _ptr(perm), P, E, N, Kd, _ptr(Y),
+                                        _stream())
+    _lib.check(rc, name)
+    return Y
+
+
+def _grouped_acc(nn, A, lda, a_div, W, vec, offsets, perm, P, y_div):
+    """_grouped on f32 (the f32 kernels alone have the form) with the pairs p // y_div summed by f32 atomics in the GEMM's
+    epilogue, into a zeroed (P // y_div, width) result."""
+    E, N, Kd = W.shape
+    kind = "nn" if nn else "nt"
+    name = f"amk_grouped_gemm_{kind}_acc"
+    Y = torch.zeros((P // y_div, Kd if nn else N), device=A.device, dtype=torch.float32)
+    with _timed(f"grouped_{kind}_acc P{P} N{N} K{Kd}"):
+        rc = getattr(_lib.load(), name)(_ptr(A), lda, a_div, _ptr(W), _ptr(vec), _ptr(offsets), _ptr(perm), P, E, N, Kd, _ptr(Y),
+                                        y_div, _stream())
+    _lib.check(rc, name)
+    return Y
+
+
+def _grouped_wgrad(elem, Gm, ldg, g_div, X, ldx, x_div, scale, offsets, perm, P, shape, has_bias=False, pairs=None, note=""):
+    """(dW (E, N, Kd), db (E, N) or None), f32: per expert, the sum over its pairs of scale[p] x (Gm row p // g_div)^T x
+    (X row p // x_div)."""
+    E, N, Kd = shape
+    dW = torch.empty((E, N, Kd), device=X.device, dtype=torch.float32)
+    db = torch.empty((E, N), device=X.device, dtype=torch.float32) if has_bias else None
+    fn = getattr(_lib.load(), elem.wgrad)
+    with _timed(f"{elem.prefix}grouped_wgrad P{pairs or P} N{N} K{Kd}{note}"):
+        if elem.wgrad_db:
+            rc = fn(_ptr(Gm), ldg, g_div, _ptr(X), ldx, x_div, _ptr(scale), _ptr(offsets), _ptr(perm), P, E, N, Kd, _ptr(dW), _ptr(db),
+                    _stream())
+        else:
+            rc = fn(_ptr(Gm), ldg, g_div, _ptr(X), ldx, x_div, _ptr(scale), _ptr(offsets), _ptr(perm), P, E, N, Kd, _ptr(dW), _stream())
+    _lib.check(rc, elem.wgrad)
+    return dW, db
+
+
+def _combine(Y, ids, gate, G, outer, k):
+    """out (G, N): row g is the sum of Y's rows of its outer*k pairs in ascending expert id, gated (gate (U, k)) or plain."""
+    N = Y.shape[1]
+    out = torch.empty((G, N), device=Y.device, dtype=torch.float32)
+    _lib.check(_lib.load().amk_moe_combine(_ptr(Y), _ptr(ids), _ptr(gate), G, outer, k, N, _ptr(out), _stream()), "amk_moe_combine")
+    return out
+
+
+def _combine_rows(V, ids, gate, U, k, fan, E):
+    """_combine over the distinct rows V (G*E, N): unit u's k pairs read the rows (u // (fan // k)) * E + e."""
+    N = V.shape[1]
+    out = torch.empty((U, N), device=V.device, dtype=torch.float32)
+    _lib.check(_lib.load().amk_moe_combine_rows(_ptr(V), _ptr(ids), _ptr(gate), U, 1, k, N, fan, E, _ptr(out), _stream()),
+               "amk_moe_combine_rows")
+    return out
+
+
+def _gate_grad(d_out, Y, ids, gate, k, E, g_div, fan=None):
+    """dlogits (U, E) f32 from d_out (pair p's row p // g_div) and the pairs' outputs Y; fan: Y holds the distinct rows."""
+    P, N = ids.numel(), Y.shape[1]
+    dlogits = torch.empty((P // k, E), device=Y.device, dtype=torch.float32)
+    L = _lib.load()
+    if fan is None:
+        _lib.check(L.amk_moe_gate_grad(_ptr(d_out), _ptr(Y), _ptr(ids), _ptr(gate), P, k, E, N, g_div, _ptr(dlogits), _stream()),
+                   "amk_moe_gate_grad")
+    else:
+        _lib.check(L.amk_moe_gate_grad_rows(_ptr(d_out), _ptr(Y), _ptr(ids), _ptr(gate), P, k, E, N, g_div, fan, _ptr(dlogits),
+                                            _stream()), "amk_moe_gate_grad_rows")
+    return dlogits
+
+
+def _done(ctx, elem, saved, cfg, out, ids):
+    ctx.elem = elem
+    ctx.save_for_backward(*saved)
+    ctx.cfg = cfg
+    ctx.mark_non_differentiable(ids)
+    ctx.set_materialize_grads(False)   # no zero-filled "gradient" of the ids handed to backward
+    return out, ids
+
+
+def _routed_dims(x2, logits2, W, k, x_div, outer):
+    U = logits2.shape[0]
+    if x2.shape != (U * k // x_div, W.shape[2]) or U % outer:
+        raise RuntimeError(f"routed linear shapes disagree: x {tuple(x2.shape)} U {U} k {k} x_div {x_div} W {tuple(W.shape)}")
+
+
+def _routed_fwd(ctx, elem, x, logits32, W, bias, k, x_div, weighted, outer, dtypes):
+    """x (rows, Kd) and W (E, N, Kd) in elem's dtype, f32 logits and bias; dtypes: those of the caller's x and logits."""
+    U, E = logits32.shape
+    N, Kd = W.shape[1], W.shape[2]
+    P, G, fan = U * k, U // outer, outer * k
+    f32 = elem.f32   # the bf16 kernels have the routed form alone
+    ldx = Kd if f32 else x.stride(0)
+    with _timed(f"moe_route U{U} E{E} k{k}"):
+        r = moe_route(logits32, k)
+    Y = None
+    if f32 and not weighted and bias is None and _moe_dense_z(N, Kd, fan, E):
+        Z = _expert_sums(x, x_div, r["ids"], _NULL, G, fan, E, Kd)
+        with _timed(f"dense_z_gemm M{G} N{N} K{E * Kd}"):
+            out = Z @ W.permute(0, 2, 1).reshape(E * Kd, N)   # (E, N, Kd) -> (E*Kd, N): an 8 MB copy at the ViTMoE layer
+    elif f32 and not weighted and _moe_sum_in_gemm(N, Kd, fan):
+        # un-weighted sum over the pairs of an output row (SwitchHead's output experts): folded into the GEMM's
+        # epilogue -- the (P, N) per-pair intermediate (272 MB at the ViTMoE layer) is never written
+        out = _grouped_acc(False, x, ldx, x_div, W, bias, r["offsets"], r["perm"], P, fan)
+    else:
+        Y = _grouped(False, elem, x, ldx, x_div, W, bias, r["offsets"], r["perm"], P)
+        out = torch.empty((G, N), device=x.device, dtype=torch.float32)
+        with _timed(f"moe_combine G{G} N{N} x{fan}"):   # (the forward's combine has a label, so not _combine)
+            rc = _lib.load().amk_moe_combine(_ptr(Y), _ptr(r["ids"]), _ptr(r["gate"] if weighted else None), G, outer, k, N,
+                                             _ptr(out), _stream())
+        _lib.check(rc, "amk_moe_combine")
+    return _done(ctx, elem, (x, W, Y, r["ids"], r["gate"], r["offsets"], r["perm"]),
+                 (k, x_div, weighted, outer, E, bias is not None) + dtypes, out, r["ids"])
+
+
+def _routed_bwd(ctx, d_out):
+    """(dx, dlogits, dW, db); the bf16 kernels have the routed form of dx alone."""
+    elem = ctx.elem
+    f32 = elem.f32
+    x, W, Y, ids, gate, offsets, perm = ctx.saved_tensors
+    k, x_div, weighted, outer, E, has_bias, x_dtype, l_dtype = ctx.cfg
+    N, Kd = W.shape[1], W.shape[2]
+    P, rows, g_div = ids.numel(), x.shape[0], outer * k
+    if f32:
+        dA = d_out = d_out.contiguous()
+    else:
+        d_out = d_out.to(torch.float32).contiguous()
+        dA = d_out.to(torch.bfloat16)   # once, for both products
+    scale = gate if weighted else None
+    dlogits = _gate_grad(d_out, Y, ids, gate, k, E, g_div) if weighted else None
+    if not ctx.needs_input_grad[0]:
+        dx = None
+    elif f32 and _moe_dense_z(Kd, N, x_div, E):
+        # dx[r] = sum over the x_div pairs of input row r of scale * dOut-row x W[e] (N, Kd): per-expert sums of the
+        # dOut rows, then one product with W viewed as (E*N, Kd) -- no copy
+        Z = _expert_sums(d_out, g_div, ids, _ptr(scale), rows, x_div, E, N)
+        with _timed(f"dense_z_gemm M{rows} N{Kd} K{E * N}"):
+            dx = Z @ W.view(E * N, Kd)
+    elif f32 and _moe_sum_in_gemm(Kd, N, x_div):
+        # the input rows' gradients are sums over the x_div pairs that read them: folded into the GEMM's epilogue
+        dx = _grouped_acc(True, d_out, N, g_div, W, scale, offsets, perm, P, x_div)
+    else:
+        dxp = _grouped(True, elem, dA, N, g_div, W, scale, offsets, perm, P)
+        dx = _combine(dxp, ids, None, rows, x_div // k, k)
+    dW, db = _grouped_wgrad(elem, dA, N, g_div, x, Kd if f32 else x.stride(0), x_div, scale, offsets, perm, P, W.shape, has_bias)
+    if not f32:   # back in the dtypes of the caller's x and logits
+        dx, dlogits = dx if dx is None else dx.to(x_dtype), dlogits.to(l_dtype)
+    return dx, dlogits, dW, db
 
 
 class _RoutedLinear(torch.autograd.Function):
@@ -890,101 +1069,15 @@ class _RoutedLinear(torch.autograd.Function):
     @_amp_fwd
     def forward(ctx, x2, logits2, W, bias, k, x_div, weighted, outer):
         _require_device(x2, logits2, W, bias)
-        x2 = x2.contiguous()
-        W = W.contiguous()
-        U, E = logits2.shape
-        N, Kd = W.shape[1], W.shape[2]
-        P = U * k
-        dev = x2.device
-        if x2.shape != (P // x_div, Kd) or U % outer:
-            raise RuntimeError(f"routed linear shapes disagree: x {tuple(x2.shape)} U {U} k {k} x_div {x_div} W {tuple(W.shape)}")
-        with _timed(f"moe_route U{U} E{E} k{k}"):
-            r = moe_route(logits2.detach(), k)
-        L = _lib.load()
-        G = U // outer
-        if not weighted and bias is None and _moe_dense_z(N, Kd, outer * k, E):
-            Y = None
-            Z = _expert_sums(x2, x_div, r["ids"], _NULL, G, outer * k, E, Kd)
-            with _timed(f"dense_z_gemm M{G} N{N} K{E * Kd}"):
-                out = Z @ W.permute(0, 2, 1).reshape(E * Kd, N)   # (E, N, Kd) -> (E*Kd, N): an 8 MB copy at the ViTMoE layer
-        elif not weighted and _moe_sum_in_gemm(N, Kd, outer * k):
-            # un-weighted sum over the pairs of an output row (SwitchHead's output experts): folded into the GEMM's
-            # epilogue -- the (P, N) per-pair intermediate (272 MB at the ViTMoE layer) is never written
-            Y = None
-            out = torch.zeros((G, N), device=dev, dtype=torch.float32)
-            with _timed(f"grouped_nt_acc P{P} N{N} K{Kd}"):
-                rc = L.amk_grouped_gemm_nt_acc(_ptr(x2), Kd, x_div, _ptr(W), _ptr(bias), _ptr(r["offsets"]), _ptr(r["perm"]),
-                                               P, E, N, Kd, _ptr(out), outer * k, _stream())
-            _lib.check(rc, "amk_grouped_gemm_nt_acc")
-        else:
-            Y = torch.empty((P, N), device=dev, dtype=torch.float32)
-            with _timed(f"grouped_nt P{P} N{N} K{Kd}"):
-                rc = L.amk_grouped_gemm_nt(_ptr(x2), Kd, x_div, _ptr(W), _ptr(bias), _ptr(r["offsets"]), _ptr(r["perm"]),
-                                           P, E, N, Kd, _ptr(Y), _stream())
-            _lib.check(rc, "amk_grouped_gemm_nt")
-            out = torch.empty((G, N), device=dev, dtype=torch.float32)
-            with _timed(f"moe_combine G{G} N{N} x{outer * k}"):
-                rc = L.amk_moe_combine(_ptr(Y), _ptr(r["ids"]), _ptr(r["gate"]) if weighted else _NULL, G, outer, k, N,
-                                       _ptr(out), _stream())
-            _lib.check(rc, "amk_moe_combine")
-        ctx.save_for_backward(x2, W, Y, r["ids"], r["gate"], r["offsets"], r["perm"])
-        ctx.cfg = (k, x_div, weighted, outer, E, bias is not None)
-        ctx.mark_non_differentiable(r["ids"])
-        ctx.set_materialize_grads(False)   # no zero-filled "gradient" of the ids handed to backward
-        return out, r["ids"]
+        x2, W = x2.contiguous(), W.contiguous()
+        _routed_dims(x2, logits2, W, k, x_div, outer)
+        return _routed_fwd(ctx, _MOE_F32, x2, logits2.detach(), W, bias, k, x_div, weighted, outer, (torch.float32,) * 2)
 
     @staticmethod
     @once_differentiable
     @_amp_bwd
     def backward(ctx, d_out, _d_ids):
-        if d_out is None:
-            return (None,) * 8
-        x2, W, Y, ids, gate, offsets, perm = ctx.saved_tensors
-        k, x_div, weighted, outer, E, has_bias = ctx.cfg
-        N, Kd = W.shape[1], W.shape[2]
-        P = ids.numel()
-        U = P // k
-        dev = x2.device
-        d_out = d_out.contiguous()
-        g_div = outer * k
-        scale = _ptr(gate) if weighted else _NULL
-        L = _lib.load()
-        dlogits = None
-        if weighted:
-            dlogits = torch.empty((U, E), device=dev, dtype=torch.float32)
-            rc = L.amk_moe_gate_grad(_ptr(d_out), _ptr(Y), _ptr(ids), _ptr(gate), P, k, E, N, g_div, _ptr(dlogits), _stream())
-            _lib.check(rc, "amk_moe_gate_grad")
-        if not ctx.needs_input_grad[0]:
-            dx = None
-        elif _moe_dense_z(Kd, N, x_div, E):
-            # dx[r] = sum over the x_div pairs of input row r of scale * dOut-row x W[e] (N, Kd): per-expert sums of the
-            # dOut rows, then one product with W viewed as (E*N, Kd) -- no copy
-            Z = _expert_sums(d_out, g_div, ids, scale, x2.shape[0], x_div, E, N)
-            with _timed(f"dense_z_gemm M{x2.shape[0]} N{Kd} K{E * N}"):
-                dx = Z @ W.view(E * N, Kd)
-        elif _moe_sum_in_gemm(Kd, N, x_div):
-            # the input rows' gradients are sums over the x_div pairs that read them: folded into the GEMM's epilogue
-            dx = torch.zeros_like(x2)
-            with _timed(f"grouped_nn_acc P{P} N{N} K{Kd}"):
-                rc = L.amk_grouped_gemm_nn_acc(_ptr(d_out), N, g_div, _ptr(W), scale, _ptr(offsets), _ptr(perm), P, E, N, Kd,
-                                               _ptr(dx), x_div, _stream())
-            _lib.check(rc, "amk_grouped_gemm_nn_acc")
-        else:
-            dxp = torch.empty((P, Kd), device=dev, dtype=torch.float32)
-            with _timed(f"grouped_nn P{P} N{N} K{Kd}"):
-                rc = L.amk_grouped_gemm_nn(_ptr(d_out), N, g_div, _ptr(W), scale, _ptr(offsets), _ptr(perm), P, E, N, Kd,
-                                           _ptr(dxp), _stream())
-            _lib.check(rc, "amk_grouped_gemm_nn")
-            dx = torch.empty_like(x2)
-            rc = L.amk_moe_combine(_ptr(dxp), _ptr(ids), _NULL, x2.shape[0], x_div // k, k, Kd, _ptr(dx), _stream())
-            _lib.check(rc, "amk_moe_combine")
-        dW = torch.empty_like(W)
-        db = torch.empty((E, N), device=dev, dtype=torch.float32) if has_bias else None
-        with _timed(f"grouped_wgrad P{P} N{N} K{Kd}"):
-            rc = L.amk_grouped_gemm_wgrad(_ptr(d_out), N, g_div, _ptr(x2), Kd, x_div, scale, _ptr(offsets), _ptr(perm),
-                                          P, E, N, Kd, _ptr(dW), _ptr(db), _stream())
-        _lib.check(rc, "amk_grouped_gemm_wgrad")
-        return dx, dlogits, dW, db, None, None, None, None
+        return (None,) * 8 if d_out is None else _routed_bwd(ctx, d_out) + (None,) * 4
 
 
 # AMK_MOE_BF16: MoELayer's routed expert products under bf16 autocast on bf16 operands (csrc/moe_bf16.hip,
@@ -1003,76 +1096,23 @@ class _RoutedLinearBF16(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x2, logits2, W, bias, k, x_div):
         _require_device(W, bias)
-        U, E = logits2.shape
-        N, Kd = W.shape[1], W.shape[2]
-        P = U * k
-        if x2.shape != (P // x_div, Kd):
-            raise RuntimeError(f"routed linear shapes disagree: x {tuple(x2.shape)} U {U} k {k} x_div {x_div} W {tuple(W.shape)}")
+        _routed_dims(x2, logits2, W, k, x_div, 1)
         if not (x2.is_cuda and logits2.is_cuda):
             raise RuntimeError("amk ops run only on MI355X (HIP) tensors; got a CPU tensor. There is no CPU fallback.")
-        dev = x2.device
         x16 = _row_major_view(x2.to(torch.bfloat16), 8)
         w16 = _w16(W).contiguous()
-        with _timed(f"moe_route U{U} E{E} k{k}"):
-            r = moe_route(logits2.detach().float(), k)
-        L = _lib.load()
         b32 = bias.detach().contiguous() if bias is not None else None
-        Y = torch.empty((P, N), device=dev, dtype=torch.float32)
-        with _timed(f"bf16_grouped_nt P{P} N{N} K{Kd}"):
-            rc = L.amk_grouped_gemm_nt_bf16(_ptr(x16), x16.stride(0), x_div, _ptr(w16), _ptr(b32), _ptr(r["offsets"]), _ptr(r["perm"]),
-                                            P, E, N, Kd, _ptr(Y), _stream())
-        _lib.check(rc, "amk_grouped_gemm_nt_bf16")
-        out = torch.empty((U, N), device=dev, dtype=torch.float32)
-        with _timed(f"moe_combine G{U} N{N} x{k}"):
-            rc = L.amk_moe_combine(_ptr(Y), _ptr(r["ids"]), _ptr(r["gate"]), U, 1, k, N, _ptr(out), _stream())
-        _lib.check(rc, "amk_moe_combine")
-        ctx.save_for_backward(x16, w16, Y, r["ids"], r["gate"], r["offsets"], r["perm"])
-        ctx.cfg = (k, x_div, E, bias is not None, x2.dtype, logits2.dtype)
-        ctx.mark_non_differentiable(r["ids"])
-        ctx.set_materialize_grads(False)
-        return out, r["ids"]
+        return _routed_fwd(ctx, _MOE_BF16, x16, logits2.detach().float(), w16, b32, k, x_div, True, 1, (x2.dtype, logits2.dtype))
 
     @staticmethod
     @once_differentiable
     def backward(ctx, d_out, _d_ids):
-        if d_out is None:
-            return (None,) * 6
-        x16, w16, Y, ids, gate, offsets, perm = ctx.saved_tensors
-        k, x_div, E, has_bias, x_dtype, l_dtype = ctx.cfg
-        N, Kd = w16.shape[1], w16.shape[2]
-        P = ids.numel()
-        U = P // k
-        dev = x16.device
-        d_out = d_out.to(torch.float32).contiguous()
-        d16 = d_out.to(torch.bfloat16)   # once, for both products
-        L = _lib.load()
-        dlogits = torch.empty((U, E), device=dev, dtype=torch.float32)
-        rc = L.amk_moe_gate_grad(_ptr(d_out), _ptr(Y), _ptr(ids), _ptr(gate), P, k, E, N, k, _ptr(dlogits), _stream())
-        _lib.check(rc, "amk_moe_gate_grad")
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dxp = torch.empty((P, Kd), device=dev, dtype=torch.float32)
-            with _timed(f"bf16_grouped_nn P{P} N{N} K{Kd}"):
-                rc = L.amk_grouped_gemm_nn_bf16(_ptr(d16), N, k, _ptr(w16), _ptr(gate), _ptr(offsets), _ptr(perm), P, E, N, Kd,
-                                                _ptr(dxp), _stream())
-            _lib.check(rc, "amk_grouped_gemm_nn_bf16")
-            dx = torch.empty(x16.shape, device=dev, dtype=torch.float32)
-            rc = L.amk_moe_combine(_ptr(dxp), _ptr(ids), _NULL, x16.shape[0], x_div // k, k, Kd, _ptr(dx), _stream())
-            _lib.check(rc, "amk_moe_combine")
-            dx = dx.to(x_dtype)
-        dW = torch.empty((E, N, Kd), device=dev, dtype=torch.float32)
-        db = torch.empty((E, N), device=dev, dtype=torch.float32) if has_bias else None
-        with _timed(f"bf16_grouped_wgrad P{P} N{N} K{Kd}"):
-            rc = L.amk_grouped_gemm_wgrad_bf16(_ptr(d16), N, k, _ptr(x16), x16.stride(0), x_div, _ptr(gate), _ptr(offsets), _ptr(perm),
-                                               P, E, N, Kd, _ptr(dW), _ptr(db), _stream())
-        _lib.check(rc, "amk_grouped_gemm_wgrad_bf16")
-        return dx, dlogits.to(l_dtype), dW, db, None, None
+        return (None,) * 6 if d_out is None else _routed_bwd(ctx, d_out) + (None,) * 2
 
 
 def _moe_bf16_ok(x2, logits2, W, bias, weighted, outer):
     """MoELayer's form under bf16 autocast on HIP tensors, an f32 master weight, N and Kd multiples of 8."""
-    return (MOE_BF16 and weighted and outer == 1 and torch.is_autocast_enabled()
-            and torch.get_autocast_dtype("cuda") == torch.bfloat16 and x2.is_cuda and logits2.is_cuda and W.is_cuda
+    return (MOE_BF16 and weighted and outer == 1 and _bf16_autocast() and x2.is_cuda and logits2.is_cuda and W.is_cuda
             and W.dtype == torch.float32 and W.dim() == 3 and W.shape[1] % 8 == 0 and W.shape[2] % 8 == 0
             and x2.dtype in (torch.float32, torch.bfloat16) and logits2.dtype in (torch.float32, torch.bfloat16)
             and (bias is None or bias.dtype == torch.float32))
@@ -1110,6 +1150,50 @@ def distinct_experts_ok(dim, d, fan, E, *weights):
     return E <= 64 and _moe_dense_z(dim, d, fan, E) and dim % 4 == 0 and all(w.is_cuda for w in weights)
 
 
+def _switchhead_dims(what, name, a2, rows, logits2, W, H):
+    U = logits2.shape[0]
+    if a2.shape != (rows, W.shape[2]) or U % H:
+        raise RuntimeError(f"{what}: shapes disagree: {name} {tuple(a2.shape)} U {U} H {H} W {tuple(W.shape)}")
+
+
+def _shared_rows_fwd(ctx, elem, x, logits32, W, k, H, dtypes):
+    U, E = logits32.shape
+    N, Kd = W.shape[1], W.shape[2]
+    G, fan = U // H, H * k
+    with _timed(f"moe_topk U{U} E{E} k{k} + distinct lists"):
+        ids, gate = _topk(logits32, k)
+        offsets, perm = _route_distinct(ids, G, fan, E)
+    # V (G*E, N): rows of chosen (token, expert) only
+    V = _grouped(False, elem, x, Kd if elem.f32 else x.stride(0), E, W, None, offsets, perm, G * E, U * k, _DISTINCT)
+    out = _combine_rows(V, ids, gate, U, k, fan, E)
+    return _done(ctx, elem, (x, W, V, ids, gate, offsets, perm), (k, H) + dtypes, out, ids)
+
+
+def _shared_rows_bwd(ctx, d_out):
+    elem = ctx.elem
+    x, W, V, ids, gate, offsets, perm = ctx.saved_tensors
+    k, H, x_dtype, l_dtype = ctx.cfg
+    E, N, Kd = W.shape
+    G, fan = x.shape[0], H * k
+    f32 = elem.f32
+    if f32:
+        d_in = d32 = d_out.contiguous()
+    else:
+        d32 = d_out.to(torch.float32).contiguous()   # the gate gradient reads f32 rows
+        d_in = _row_major_view(d_out, 8) if d_out.dtype == torch.bfloat16 else d32   # the sums read bf16 rows as they are
+    dlogits = _gate_grad(d32, V, ids, gate, k, E, k, fan)
+    Z = _expert_sums(d_in, k, ids, _ptr(gate), G, fan, E, N, elem)   # (G, E*N): gated output gradients per (token, expert)
+    dx = None
+    if ctx.needs_input_grad[0]:
+        with _timed(f"{elem.prefix}dense_z_gemm M{G} N{Kd} K{E * N}"):
+            dx = Z @ W.view(E * N, Kd)
+            if not f32:
+                dx = dx.to(x_dtype)
+    dW, _ = _grouped_wgrad(elem, Z, N, 1, x, Kd if f32 else x.stride(0), E, None, offsets, perm, G * E, W.shape, False, G * fan,
+                           _DISTINCT)
+    return dx, dlogits if f32 else dlogits.to(l_dtype), dW, None, None
+
+
 class _SharedRowExperts(torch.autograd.Function):
     """SwitchHead's V experts (reference switchhead_attention.py:58-73): U = G*H units, the H units (heads) of group g
     (token) all read x row g; out[u] = sum over the unit's k slots of gate * x[g] W[e]^T.  The product x[g] W[e]^T does not
@@ -1122,54 +1206,48 @@ class _SharedRowExperts(torch.autograd.Function):
     def forward(ctx, x2, logits2, W, k, H):
         _require_device(x2, logits2, W)
         x2, W = x2.contiguous(), W.contiguous()
-        U, E = logits2.shape
-        N, Kd = W.shape[1], W.shape[2]
-        G, fan = U // H, H * k
-        if x2.shape != (G, Kd) or U % H:
-            raise RuntimeError(f"shared-row experts: shapes disagree: x {tuple(x2.shape)} U {U} H {H} W {tuple(W.shape)}")
-        L = _lib.load()
-        with _timed(f"moe_topk U{U} E{E} k{k} + distinct lists"):
-            ids, gate = _topk(logits2.detach(), k)
-            offsets, perm = _route_distinct(ids, G, fan, E)
-        V = torch.empty((G * E, N), device=x2.device, dtype=torch.float32)   # rows of chosen (token, expert) only
-        with _timed(f"grouped_nt P{U * k} N{N} K{Kd} (distinct rows)"):
-            _lib.check(L.amk_grouped_gemm_nt(_ptr(x2), Kd, E, _ptr(W), _NULL, _ptr(offsets), _ptr(perm), G * E, E, N, Kd, _ptr(V),
-                                             _stream()), "amk_grouped_gemm_nt")
-        out = torch.empty((U, N), device=x2.device, dtype=torch.float32)
-        _lib.check(L.amk_moe_combine_rows(_ptr(V), _ptr(ids), _ptr(gate), U, 1, k, N, fan, E, _ptr(out), _stream()),
-                   "amk_moe_combine_rows")
-        ctx.save_for_backward(x2, W, V, ids, gate, offsets, perm)
-        ctx.cfg = (k, H)
-        ctx.mark_non_differentiable(ids)
-        ctx.set_materialize_grads(False)
-        return out, ids
+        _switchhead_dims("shared-row experts", "x", x2, logits2.shape[0] // H, logits2, W, H)
+        return _shared_rows_fwd(ctx, _MOE_F32, x2, logits2.detach(), W, k, H, (torch.float32,) * 2)
 
     @staticmethod
     @once_differentiable
     @_amp_bwd
     def backward(ctx, d_out, _d_ids):
-        if d_out is None:
-            return (None,) * 5
-        x2, W, V, ids, gate, offsets, perm = ctx.saved_tensors
-        k, H = ctx.cfg
-        E, N, Kd = W.shape
-        G, fan = x2.shape[0], H * k
-        U = G * H
-        d_out = d_out.contiguous()
-        L = _lib.load()
-        dlogits = torch.empty((U, E), device=x2.device, dtype=torch.float32)
-        _lib.check(L.amk_moe_gate_grad_rows(_ptr(d_out), _ptr(V), _ptr(ids), _ptr(gate), U * k, k, E, N, k, fan, _ptr(dlogits),
-                                            _stream()), "amk_moe_gate_grad_rows")
-        Z = _expert_sums(d_out, k, ids, _ptr(gate), G, fan, E, N)      # (G, E*N): gated output gradients per (token, expert)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            with _timed(f"dense_z_gemm M{G} N{Kd} K{E * N}"):
-                dx = Z @ W.view(E * N, Kd)
-        dW = torch.empty_like(W)
-        with _timed(f"grouped_wgrad P{U * k} N{N} K{Kd} (distinct rows)"):
-            _lib.check(L.amk_grouped_gemm_wgrad(_ptr(Z), N, 1, _ptr(x2), Kd, E, _NULL, _ptr(offsets), _ptr(perm), G * E, E, N, Kd,
-                                                _ptr(dW), _NULL, _stream()), "amk_grouped_gemm_wgrad")
-        return dx, dlogits, dW, None, None
+        return (None,) * 5 if d_out is None else _shared_rows_bwd(ctx, d_out)
+
+
+def _summed_fwd(ctx, elem, a2, logits32, W, k, H):
+    U, E = logits32.shape
+    N, Kd = W.shape[1], W.shape[2]
+    G, fan = U // H, H * k
+    with _timed(f"moe_topk U{U} E{E} k{k}"):
+        ids, _gate = _topk(logits32, k)
+    Z = _expert_sums(a2, k, ids, _NULL, G, fan, E, Kd, elem)
+    with _timed(f"{elem.prefix}dense_z_gemm M{G} N{N} K{E * Kd}"):
+        out = Z @ W.permute(0, 2, 1).reshape(E * Kd, N)
+    return _done(ctx, elem, (W, Z, ids), (k, H, a2.dtype), out, ids)
+
+
+def _summed_bwd(ctx, d_out):
+    elem = ctx.elem
+    W, Z, ids = ctx.saved_tensors
+    k, H, a_dtype = ctx.cfg
+    E, N, Kd = W.shape
+    G, fan = Z.shape[0], H * k
+    if elem.f32:
+        d, ldd = d_out.contiguous(), N
+    else:
+        d = _row_major_view(d_out.to(torch.bfloat16), 8)   # once, for both products
+        ldd = d.stride(0)
+    offsets, perm = _route_distinct(ids, G, fan, E)
+    da = None
+    if ctx.needs_input_grad[0]:
+        D = _grouped(True, elem, d, ldd, E, W, None, offsets, perm, G * E, G * fan, _DISTINCT)
+        da = _combine_rows(D, ids, None, G * H, k, fan, E)
+        if not elem.f32:
+            da = da.to(a_dtype)
+    dW, _ = _grouped_wgrad(elem, d, ldd, E, Z, Kd, 1, None, offsets, perm, G * E, W.shape, False, G * fan, _DISTINCT)
+    return da, None, dW, None, None
 
 
 class _SummedExperts(torch.autograd.Function):
@@ -1183,50 +1261,14 @@ class _SummedExperts(torch.autograd.Function):
     def forward(ctx, a2, logits2, W, k, H):
         _require_device(a2, logits2, W)
         a2, W = a2.contiguous(), W.contiguous()
-        U, E = logits2.shape
-        N, Kd = W.shape[1], W.shape[2]
-        G, fan = U // H, H * k
-        if a2.shape != (U, Kd) or U % H:
-            raise RuntimeError(f"summed experts: shapes disagree: a {tuple(a2.shape)} U {U} H {H} W {tuple(W.shape)}")
-        with _timed(f"moe_topk U{U} E{E} k{k}"):
-            ids, _gate = _topk(logits2.detach(), k)
-        Z = _expert_sums(a2, k, ids, _NULL, G, fan, E, Kd)
-        with _timed(f"dense_z_gemm M{G} N{N} K{E * Kd}"):
-            out = Z @ W.permute(0, 2, 1).reshape(E * Kd, N)
-        ctx.save_for_backward(W, Z, ids)
-        ctx.cfg = (k, H)
-        ctx.mark_non_differentiable(ids)
-        ctx.set_materialize_grads(False)
-        return out, ids
+        _switchhead_dims("summed experts", "a", a2, logits2.shape[0], logits2, W, H)
+        return _summed_fwd(ctx, _MOE_F32, a2, logits2.detach(), W, k, H)
 
     @staticmethod
     @once_differentiable
     @_amp_bwd
     def backward(ctx, d_out, _d_ids):
-        if d_out is None:
-            return (None,) * 5
-        W, Z, ids = ctx.saved_tensors
-        k, H = ctx.cfg
-        E, N, Kd = W.shape
-        G, fan = Z.shape[0], H * k
-        U = G * H
-        d_out = d_out.contiguous()
-        L = _lib.load()
-        offsets, perm = _route_distinct(ids, G, fan, E)
-        da = None
-        if ctx.needs_input_grad[0]:
-            D = torch.empty((G * E, Kd), device=W.device, dtype=torch.float32)
-            with _timed(f"grouped_nn P{U * k} N{N} K{Kd} (distinct rows)"):
-                _lib.check(L.amk_grouped_gemm_nn(_ptr(d_out), N, E, _ptr(W), _NULL, _ptr(offsets), _ptr(perm), G * E, E, N, Kd, _ptr(D),
-                                                 _stream()), "amk_grouped_gemm_nn")
-            da = torch.empty((U, Kd), device=W.device, dtype=torch.float32)
-            _lib.check(L.amk_moe_combine_rows(_ptr(D), _ptr(ids), _NULL, U, 1, k, Kd, fan, E, _ptr(da), _stream()),
-                       "amk_moe_combine_rows")
-        dW = torch.empty_like(W)
-        with _timed(f"grouped_wgrad P{U * k} N{N} K{Kd} (distinct rows)"):
-            _lib.check(L.amk_grouped_gemm_wgrad(_ptr(d_out), N, E, _ptr(Z), Kd, 1, _NULL, _ptr(offsets), _ptr(perm), G * E, E, N, Kd,
-                                                _ptr(dW), _NULL, _stream()), "amk_grouped_gemm_wgrad")
-        return da, None, dW, None, None
+        return (None,) * 5 if d_out is None else _summed_bwd(ctx, d_out)
 
 
 # AMK_SWITCHHEAD_BF16: SwitchHeadAttention's experts under bf16 autocast on bf16 operands -- the narrow grouped kernels
@@ -1234,16 +1276,6 @@ class _SummedExperts(torch.autograd.Function):
 # upcasting what autocast hands over and running the f32 kernels.  0: the path before.  Measurements: README,
 # "Switches".  Read once per process.
 SWITCHHEAD_BF16 = os.environ.get("AMK_SWITCHHEAD_BF16", "1") != "0"
-
-
-def _expert_sums_bf16(a2, a_div, ids, scale, G, fan, E, d):
-    """_expert_sums with Z (G, E*d) in bf16 (the same f32 sums, rounded once); a2 f32 or bf16."""
-    Z = torch.empty((G, E * d), device=a2.device, dtype=torch.bfloat16)
-    with _timed(f"bf16_moe_expert_sums G{G} fan{fan} E{E} d{d}"):
-        rc = _lib.load().amk_moe_expert_sums_bf16(_ptr(a2), int(a2.dtype == torch.bfloat16), a2.stride(0), a_div, _ptr(ids), scale,
-                                                  G, fan, E, d, _ptr(Z), _stream())
-    _lib.check(rc, "amk_moe_expert_sums_bf16")
-    return Z
 
 
 class _SharedRowExpertsBF16(torch.autograd.Function):
@@ -1255,58 +1287,15 @@ class _SharedRowExpertsBF16(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x2, logits2, W, k, H):
         _require_device(W)
-        U, E = logits2.shape
-        N, Kd = W.shape[1], W.shape[2]
-        G, fan = U // H, H * k
-        if x2.shape != (G, Kd) or U % H:
-            raise RuntimeError(f"shared-row experts: shapes disagree: x {tuple(x2.shape)} U {U} H {H} W {tuple(W.shape)}")
-        dev = x2.device
+        _switchhead_dims("shared-row experts", "x", x2, logits2.shape[0] // H, logits2, W, H)
         x16 = _row_major_view(x2.detach().to(torch.bfloat16), 8)
         w16 = _w16(W).detach().contiguous()
-        L = _lib.load()
-        with _timed(f"moe_topk U{U} E{E} k{k} + distinct lists"):
-            ids, gate = _topk(logits2.detach().float(), k)
-            offsets, perm = _route_distinct(ids, G, fan, E)
-        V = torch.empty((G * E, N), device=dev, dtype=torch.float32)   # rows of chosen (token, expert) only
-        with _timed(f"bf16_grouped_nt P{U * k} N{N} K{Kd} (distinct rows)"):
-            _lib.check(L.amk_grouped_gemm_nt64_bf16(_ptr(x16), x16.stride(0), E, _ptr(w16), _NULL, _ptr(offsets), _ptr(perm),
-                                                    G * E, E, N, Kd, _ptr(V), _stream()), "amk_grouped_gemm_nt64_bf16")
-        out = torch.empty((U, N), device=dev, dtype=torch.float32)
-        _lib.check(L.amk_moe_combine_rows(_ptr(V), _ptr(ids), _ptr(gate), U, 1, k, N, fan, E, _ptr(out), _stream()),
-                   "amk_moe_combine_rows")
-        ctx.save_for_backward(x16, w16, V, ids, gate, offsets, perm)
-        ctx.cfg = (k, H, x2.dtype, logits2.dtype)
-        ctx.mark_non_differentiable(ids)
-        ctx.set_materialize_grads(False)
-        return out, ids
+        return _shared_rows_fwd(ctx, _MOE_BF16_64, x16, logits2.detach().float(), w16, k, H, (x2.dtype, logits2.dtype))
 
     @staticmethod
     @once_differentiable
     def backward(ctx, d_out, _d_ids):
-        if d_out is None:
-            return (None,) * 5
-        x16, w16, V, ids, gate, offsets, perm = ctx.saved_tensors
-        k, H, x_dtype, l_dtype = ctx.cfg
-        E, N, Kd = w16.shape
-        G, fan = x16.shape[0], H * k
-        U = G * H
-        dev = x16.device
-        L = _lib.load()
-        d32 = d_out.to(torch.float32).contiguous()   # the gate gradient reads f32 rows
-        dlogits = torch.empty((U, E), device=dev, dtype=torch.float32)
-        _lib.check(L.amk_moe_gate_grad_rows(_ptr(d32), _ptr(V), _ptr(ids), _ptr(gate), U * k, k, E, N, k, fan, _ptr(dlogits),
-                                            _stream()), "amk_moe_gate_grad_rows")
-        d_in = _row_major_view(d_out, 8) if d_out.dtype == torch.bfloat16 else d32
-        Z16 = _expert_sums_bf16(d_in, k, ids, _ptr(gate), G, fan, E, N)   # (G, E*N): gated output gradients per (token, expert)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            with _timed(f"bf16_dense_z_gemm M{G} N{Kd} K{E * N}"):
-                dx = (Z16 @ w16.view(E * N, Kd)).to(x_dtype)
-        dW = torch.empty((E, N, Kd), device=dev, dtype=torch.float32)
-        with _timed(f"bf16_grouped_wgrad P{U * k} N{N} K{Kd} (distinct rows)"):
-            _lib.check(L.amk_grouped_gemm_wgrad64_bf16(_ptr(Z16), N, 1, _ptr(x16), x16.stride(0), E, _NULL, _ptr(offsets), _ptr(perm),
-                                                       G * E, E, N, Kd, _ptr(dW), _stream()), "amk_grouped_gemm_wgrad64_bf16")
-        return dx, dlogits.to(l_dtype), dW, None, None
+        return (None,) * 5 if d_out is None else _shared_rows_bwd(ctx, d_out)
 
 
 class _SummedExpertsBF16(torch.autograd.Function):
@@ -1318,59 +1307,21 @@ class _SummedExpertsBF16(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a2, logits2, W, k, H):
         _require_device(W)
-        U, E = logits2.shape
-        N, Kd = W.shape[1], W.shape[2]
-        G, fan = U // H, H * k
-        if a2.shape != (U, Kd) or U % H:
-            raise RuntimeError(f"summed experts: shapes disagree: a {tuple(a2.shape)} U {U} H {H} W {tuple(W.shape)}")
+        _switchhead_dims("summed experts", "a", a2, logits2.shape[0], logits2, W, H)
         a2 = _row_major_view(a2.detach(), 8)
         w16 = _w16(W).detach().contiguous()
-        with _timed(f"moe_topk U{U} E{E} k{k}"):
-            ids, _gate = _topk(logits2.detach().float(), k)
-        Z16 = _expert_sums_bf16(a2, k, ids, _NULL, G, fan, E, Kd)
-        with _timed(f"bf16_dense_z_gemm M{G} N{N} K{E * Kd}"):
-            out = Z16 @ w16.permute(0, 2, 1).reshape(E * Kd, N)
-        ctx.save_for_backward(w16, Z16, ids)
-        ctx.cfg = (k, H, a2.dtype)
-        ctx.mark_non_differentiable(ids)
-        ctx.set_materialize_grads(False)
-        return out, ids
+        return _summed_fwd(ctx, _MOE_BF16_64, a2, logits2.detach().float(), w16, k, H)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, d_out, _d_ids):
-        if d_out is None:
-            return (None,) * 5
-        w16, Z16, ids = ctx.saved_tensors
-        k, H, a_dtype = ctx.cfg
-        E, N, Kd = w16.shape
-        G, fan = Z16.shape[0], H * k
-        U = G * H
-        dev = w16.device
-        d16 = _row_major_view(d_out.to(torch.bfloat16), 8)   # once, for both products
-        L = _lib.load()
-        offsets, perm = _route_distinct(ids, G, fan, E)
-        da = None
-        if ctx.needs_input_grad[0]:
-            D = torch.empty((G * E, Kd), device=dev, dtype=torch.float32)
-            with _timed(f"bf16_grouped_nn P{U * k} N{N} K{Kd} (distinct rows)"):
-                _lib.check(L.amk_grouped_gemm_nn64_bf16(_ptr(d16), d16.stride(0), E, _ptr(w16), _NULL, _ptr(offsets), _ptr(perm),
-                                                        G * E, E, N, Kd, _ptr(D), _stream()), "amk_grouped_gemm_nn64_bf16")
-            da = torch.empty((U, Kd), device=dev, dtype=torch.float32)
-            _lib.check(L.amk_moe_combine_rows(_ptr(D), _ptr(ids), _NULL, U, 1, k, Kd, fan, E, _ptr(da), _stream()),
-                       "amk_moe_combine_rows")
-            da = da.to(a_dtype)
-        dW = torch.empty((E, N, Kd), device=dev, dtype=torch.float32)
-        with _timed(f"bf16_grouped_wgrad P{U * k} N{N} K{Kd} (distinct rows)"):
-            _lib.check(L.amk_grouped_gemm_wgrad64_bf16(_ptr(d16), d16.stride(0), E, _ptr(Z16), Kd, 1, _NULL, _ptr(offsets), _ptr(perm),
-                                                       G * E, E, N, Kd, _ptr(dW), _stream()), "amk_grouped_gemm_wgrad64_bf16")
-        return da, None, dW, None, None
+        return (None,) * 5 if d_out is None else _summed_bwd(ctx, d_out)
 
 
 def _switchhead_bf16_ok(a2, logits2, W, d):
     """bf16 autocast on HIP tensors, an f32 master weight with d <= 64 and both sides multiples of 8, and either the
     weight trains or nothing does (a frozen weight under a trainable input keeps the f32 Functions)."""
-    return (SWITCHHEAD_BF16 and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16
+    return (SWITCHHEAD_BF16 and _bf16_autocast()
             and a2.is_cuda and logits2.is_cuda and W.is_cuda and W.dtype == torch.float32 and W.dim() == 3
             and d <= 64 and W.shape[1] % 8 == 0 and W.shape[2] % 8 == 0
             and a2.dtype in (torch.float32, torch.bfloat16) and logits2.dtype in (torch.float32, torch.bfloat16)

@@ -44,6 +44,13 @@ void amk_set_error(const char* fmt, ...);
 // what the float4 paths ask of a pointer
 static inline bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// the shift that divides by d when d is a power of two, else -1 (the kernels then divide)
+static inline int log2_of(int d) {
+  int s = 0;
+  while ((1 << s) < d) ++s;
+  return (1 << s) == d ? s : -1;
+}
+
 // Opt-in of KERNEL to `bytes` of dynamic LDS (more than 64 KiB needs it) on the current device.  The attribute is per
 // device, so there is one flag per (kernel, device ordinal): each device gets the HIP call once, on first use.
 // false: no current device (or an ordinal past the table), or the device refused -- nothing is recorded, the next call asks again.
@@ -93,6 +100,15 @@ __device__ __forceinline__ float wave_sum(float s) {
 __device__ __forceinline__ int wave_sum(int v) {
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// inclusive prefix sum over the wave's lanes
+__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int t = __shfl_up(v, o, 64);
+    if (lane >= o) v += t;
+  }
   return v;
 }
 

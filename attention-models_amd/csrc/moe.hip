@@ -355,14 +355,6 @@ __global__ __launch_bounds__(256, 2) void grouped_nt_kernel(GemmParams g) {
 // share its B (weight) fragment: 32 RB MFMAs per wave between barrier pairs.  Operands are staged through buffer
 // descriptors (pairs beyond the tile and rows beyond N read as zeros: no compares or selects) and the tile loop
 // has no branch around a vector-memory instruction, so every wait is a counted one.
-__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(v, o, 64);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
 
 // Every wave decodes the unit by itself: lane j holds expert j's tile count, one scan, one ballot (a serial
 // walk over the offsets is 2 E dependent scalar loads, microseconds before the first useful load).
@@ -566,26 +558,32 @@ __device__ __forceinline__ void nt_panel_body(const GemmParams& g, int e, int ct
   }
 }
 
+// One workgroup of a wide kernel, after its __shared__ smem and prow: decode the unit, then PANEL (nt_panel_body or
+// nn_panel_body) of its tile height and width.  A macro and not a template over the two bodies: behind a function layer
+// the compiler commutes the operands of sixteen s_mul_i32 in grouped_nn_wide_kernel, and the device code stays as it is.
+#define AMK_WIDE_UNIT(PANEL)                                                                                              \
+  int e, ct, m0, rb, cnt, half;                                                                                           \
+  if (!find_unit_rb(g.offsets, g.E, g.ncol, g.slots, true, blockIdx.x, e, ct, m0, rb, cnt, half)) return;                 \
+  /* (wave-uniform by construction; said again here, or the weight panel's buffer descriptor counts as divergent */       \
+  /* and every load through it is wrapped in a waterfall loop) */                                                         \
+  e = __builtin_amdgcn_readfirstlane(e); ct = __builtin_amdgcn_readfirstlane(ct); m0 = __builtin_amdgcn_readfirstlane(m0); \
+  rb = __builtin_amdgcn_readfirstlane(rb); cnt = __builtin_amdgcn_readfirstlane(cnt); half = __builtin_amdgcn_readfirstlane(half); \
+  if (half < 0) {                                                                                                         \
+    if (rb == 4) PANEL<4, false>(g, e, ct, m0, cnt, 0, smem, prow);                                                       \
+    else if (rb == 3) PANEL<3, false>(g, e, ct, m0, cnt, 0, smem, prow);                                                  \
+    else if (rb == 2) PANEL<2, false>(g, e, ct, m0, cnt, 0, smem, prow);                                                  \
+    else PANEL<1, false>(g, e, ct, m0, cnt, 0, smem, prow);                                                               \
+  } else {                                                                                                                \
+    if (rb == 4) PANEL<4, true>(g, e, ct, m0, cnt, half, smem, prow);                                                     \
+    else if (rb == 3) PANEL<3, true>(g, e, ct, m0, cnt, half, smem, prow);                                                \
+    else if (rb == 2) PANEL<2, true>(g, e, ct, m0, cnt, half, smem, prow);                                                \
+    else PANEL<1, true>(g, e, ct, m0, cnt, half, smem, prow);                                                             \
+  }
+
 __global__ __launch_bounds__(256, 2) void grouped_nt_wide_kernel(GemmParams g) {
   __shared__ __attribute__((aligned(16))) float smem[2 * (128 + 128) * 36];
   __shared__ int prow[256];
-  int e, ct, m0, rb, cnt, half;
-  if (!find_unit_rb(g.offsets, g.E, g.ncol, g.slots, true, blockIdx.x, e, ct, m0, rb, cnt, half)) return;
-  // (wave-uniform by construction; said again here, or the weight panel's buffer descriptor counts as divergent
-  // and every load through it is wrapped in a waterfall loop)
-  e = __builtin_amdgcn_readfirstlane(e); ct = __builtin_amdgcn_readfirstlane(ct); m0 = __builtin_amdgcn_readfirstlane(m0);
-  rb = __builtin_amdgcn_readfirstlane(rb); cnt = __builtin_amdgcn_readfirstlane(cnt); half = __builtin_amdgcn_readfirstlane(half);
-  if (half < 0) {
-    if (rb == 4) nt_panel_body<4, false>(g, e, ct, m0, cnt, 0, smem, prow);
-    else if (rb == 3) nt_panel_body<3, false>(g, e, ct, m0, cnt, 0, smem, prow);
-    else if (rb == 2) nt_panel_body<2, false>(g, e, ct, m0, cnt, 0, smem, prow);
-    else nt_panel_body<1, false>(g, e, ct, m0, cnt, 0, smem, prow);
-  } else {
-    if (rb == 4) nt_panel_body<4, true>(g, e, ct, m0, cnt, half, smem, prow);
-    else if (rb == 3) nt_panel_body<3, true>(g, e, ct, m0, cnt, half, smem, prow);
-    else if (rb == 2) nt_panel_body<2, true>(g, e, ct, m0, cnt, half, smem, prow);
-    else nt_panel_body<1, true>(g, e, ct, m0, cnt, half, smem, prow);
-  }
+  AMK_WIDE_UNIT(nt_panel_body)
 }
 
 // The input-gradient product Y[p, kk] = scale[p] * sum_n A[arow(p), n] * W[e, n, kk] on the same pipeline: tiles of
@@ -727,22 +725,9 @@ __device__ __forceinline__ void nn_panel_body(const GemmParams& g, int e, int ct
 __global__ __launch_bounds__(256, 2) void grouped_nn_wide_kernel(GemmParams g) {
   __shared__ __attribute__((aligned(16))) float smem[2 * (128 * 36 + 32 * 132)];
   __shared__ int prow[384];
-  int e, ct, m0, rb, cnt, half;
-  if (!find_unit_rb(g.offsets, g.E, g.ncol, g.slots, true, blockIdx.x, e, ct, m0, rb, cnt, half)) return;
-  e = __builtin_amdgcn_readfirstlane(e); ct = __builtin_amdgcn_readfirstlane(ct); m0 = __builtin_amdgcn_readfirstlane(m0);
-  rb = __builtin_amdgcn_readfirstlane(rb); cnt = __builtin_amdgcn_readfirstlane(cnt); half = __builtin_amdgcn_readfirstlane(half);
-  if (half < 0) {
-    if (rb == 4) nn_panel_body<4, false>(g, e, ct, m0, cnt, 0, smem, prow);
-    else if (rb == 3) nn_panel_body<3, false>(g, e, ct, m0, cnt, 0, smem, prow);
-    else if (rb == 2) nn_panel_body<2, false>(g, e, ct, m0, cnt, 0, smem, prow);
-    else nn_panel_body<1, false>(g, e, ct, m0, cnt, 0, smem, prow);
-  } else {
-    if (rb == 4) nn_panel_body<4, true>(g, e, ct, m0, cnt, half, smem, prow);
-    else if (rb == 3) nn_panel_body<3, true>(g, e, ct, m0, cnt, half, smem, prow);
-    else if (rb == 2) nn_panel_body<2, true>(g, e, ct, m0, cnt, half, smem, prow);
-    else nn_panel_body<1, true>(g, e, ct, m0, cnt, half, smem, prow);
-  }
+  AMK_WIDE_UNIT(nn_panel_body)
 }
+#undef AMK_WIDE_UNIT
 
 // Y[p, kk] = scale[p] * sum_n A[arow(p), n] * W[e, n, kk]              tile: 64 pairs x 64*NB outputs
 // SHORT (NB 1): 32 pairs x 64 outputs, the waves as 2 output halves x 2 halves of every slab (see grouped_nt_kernel)
@@ -1433,32 +1418,52 @@ static int check_gemm(const char* who, const void* A, const void* W, const void*
   return AMK_OK;
 }
 
-static int grouped_nt_impl(const char* who, const float* A, int64_t lda, int a_div, const float* W, const float* bias,
-                           const int32_t* offsets, const int32_t* perm, int64_t P, int E, int N, int Kd,
-                           float* Y, int y_div, void* stream) {
+// AMK_MOE_SHORT, read once per form (nt, nn) at that form's first launch that could take the short tiles
+template <bool NN>
+static bool short_tiles_ok() {
+  static const bool ok = !(getenv("AMK_MOE_SHORT") && atoi(getenv("AMK_MOE_SHORT")) == 0);
+  return ok;
+}
+
+// nt: Y (P, N) = A rows x W[e]^T + bias.  nn: Y (P, Kd) = scale x A rows x W[e].  vec is nt's bias, nn's scale; a pair has
+// `out` outputs over a contraction of length L.
+static int grouped_impl(bool nn, const char* who, const float* A, int64_t lda, int a_div, const float* W, const float* vec,
+                        const int32_t* offsets, const int32_t* perm, int64_t P, int E, int N, int Kd,
+                        float* Y, int y_div, void* stream) {
   const int rc = check_gemm(who, A, W, Y, offsets, perm, P, E, N, Kd, a_div, lda);
   if (rc) return rc;
+  const int out = nn ? Kd : N, L = nn ? N : Kd;
   GemmParams g{};
-  g.A = A; g.W = W; g.bias = bias; g.Y = Y; g.offsets = offsets; g.perm = perm;
+  g.A = A; g.W = W; g.Y = Y; g.offsets = offsets; g.perm = perm;
+  if (nn) g.scale = vec; else g.bias = vec;
   g.E = E; g.N = N; g.Kd = Kd; g.a_div = a_div; g.b_div = 1; g.lda = lda; g.y_div = y_div;
   const unsigned mt = (unsigned)((P + 63) / 64 + E);
-  AMK_CHECK_SUPPORTED((uint64_t)mt * ((N + 63) / 64) < (1ull << 31), "%s: grid too large", who);
-  g.a_bytes = ((P - 1) / a_div * lda + Kd) * 4;   // rows 0 .. (P-1)/a_div of A
-  g.y_bytes = (y_div > 0 ? (P - 1) / y_div + 1 : P) * N * 4;
-  const bool wide = N >= 128 && Kd % 32 == 0 && g.a_bytes < (1ll << 31) && g.y_bytes < 0x7FFF0000ll && (int64_t)N * Kd * 4 < (1ll << 31);
-  AMK_CHECK_SUPPORTED(y_div == 0 || wide, "%s: the accumulating form needs N >= 128, Kd %% 32 == 0 and buffers below 2 GB", who);
-  if (wide && (y_div > 0 || !getenv("AMK_MOE_NARROW")))
-    { g.ncol = (N + 127) / 128; g.slots = wg_slots();  // grid: the bound for two-block tiles; the surplus workgroups leave at once
-      hipLaunchKernelGGL(grouped_nt_wide_kernel, dim3((unsigned)((P + 63) / 64 + E) * g.ncol + (unsigned)g.slots / 2), dim3(256), 0, static_cast<hipStream_t>(stream), g); }
-  else
-    { AMK_CHECK_SUPPORTED(g.a_bytes < 0x7fff0000ll && (int64_t)N * Kd * 4 < 0x7fff0000ll, "%s: A and one expert's weights must span < 2 GiB", who);
-      g.ncol = (N + 63) / 64;
-      // few tiles per CU (all resident at once): 32-pair tiles, twice as many workgroups half as long (AMK_MOE_SHORT=0: never)
-      static const bool short_ok = !(getenv("AMK_MOE_SHORT") && atoi(getenv("AMK_MOE_SHORT")) == 0);
-      if (short_ok && N <= 64 && Kd >= 256 && (P + 63) / 64 < 16 * wg_slots() / 2)
-        hipLaunchKernelGGL((grouped_nt_kernel<1, true>), dim3(2 * mt * g.ncol), dim3(256), 0, static_cast<hipStream_t>(stream), g);
-      else
-        hipLaunchKernelGGL(grouped_nt_kernel<1>, dim3(mt * g.ncol), dim3(256), 0, static_cast<hipStream_t>(stream), g); }
+  AMK_CHECK_SUPPORTED((uint64_t)mt * (nn ? (Kd + 127) / 128 : (N + 63) / 64) < (1ull << 31), "%s: grid too large", who);
+  g.a_bytes = ((P - 1) / a_div * lda + L) * 4;   // rows 0 .. (P-1)/a_div of A
+  g.y_bytes = (y_div > 0 ? (P - 1) / y_div + 1 : P) * out * 4;
+  const bool wide = out >= 128 && L % 32 == 0 && g.a_bytes < (1ll << 31) && g.y_bytes < 0x7FFF0000ll && (int64_t)N * Kd * 4 < (1ll << 31);
+  AMK_CHECK_SUPPORTED(y_div == 0 || wide, "%s: the accumulating form needs %s >= 128, %s %% 32 == 0 and buffers below 2 GB", who,
+                      nn ? "Kd" : "N", nn ? "N" : "Kd");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 block(256);
+  if (wide && (y_div > 0 || !getenv("AMK_MOE_NARROW"))) {
+    g.ncol = (out + 127) / 128; g.slots = wg_slots();
+    const dim3 grid(mt * g.ncol + (unsigned)g.slots / 2);   // the bound for two-block tiles; the surplus workgroups leave at once
+    if (nn) hipLaunchKernelGGL(grouped_nn_wide_kernel, grid, block, 0, st, g);
+    else hipLaunchKernelGGL(grouped_nt_wide_kernel, grid, block, 0, st, g);
+  } else {
+    AMK_CHECK_SUPPORTED(g.a_bytes < 0x7fff0000ll && (int64_t)N * Kd * 4 < 0x7fff0000ll, "%s: A and one expert's weights must span < 2 GiB", who);
+    const bool nn2 = nn && out > 64;   // nn alone has a 128-output tile; nt walks 64-output tiles at every width
+    g.ncol = nn2 ? (out + 127) / 128 : (out + 63) / 64;
+    // few tiles per CU (all resident at once): 32-pair tiles, twice as many workgroups half as long (AMK_MOE_SHORT=0: never)
+    const bool shrt = !nn2 && (nn ? short_tiles_ok<true>() : short_tiles_ok<false>()) && out <= 64 && L >= 256 && (P + 63) / 64 < 16 * wg_slots() / 2;
+    const dim3 grid((shrt ? 2 : 1) * mt * g.ncol);
+    // (nt's instances are named first: the kernels stand in the code object in the order of their first use)
+    if (!nn) { if (shrt) hipLaunchKernelGGL((grouped_nt_kernel<1, true>), grid, block, 0, st, g); else hipLaunchKernelGGL(grouped_nt_kernel<1>, grid, block, 0, st, g); }
+    else if (nn2) hipLaunchKernelGGL(grouped_nn_kernel<2>, grid, block, 0, st, g);
+    else if (shrt) hipLaunchKernelGGL((grouped_nn_kernel<1, true>), grid, block, 0, st, g);
+    else hipLaunchKernelGGL(grouped_nn_kernel<1>, grid, block, 0, st, g);
+  }
   AMK_CHECK_LAUNCH(who);
   return AMK_OK;
 }
@@ -1466,60 +1471,27 @@ static int grouped_nt_impl(const char* who, const float* A, int64_t lda, int a_d
 extern "C" int amk_grouped_gemm_nt(const float* A, int64_t lda, int a_div, const float* W, const float* bias,
                                    const int32_t* offsets, const int32_t* perm, int64_t P, int E, int N, int Kd,
                                    float* Y, void* stream) {
-  return grouped_nt_impl("amk_grouped_gemm_nt", A, lda, a_div, W, bias, offsets, perm, P, E, N, Kd, Y, 0, stream);
+  return grouped_impl(false, "amk_grouped_gemm_nt", A, lda, a_div, W, bias, offsets, perm, P, E, N, Kd, Y, 0, stream);
 }
 
 extern "C" int amk_grouped_gemm_nt_acc(const float* A, int64_t lda, int a_div, const float* W, const float* bias,
                                        const int32_t* offsets, const int32_t* perm, int64_t P, int E, int N, int Kd,
                                        float* Y, int y_div, void* stream) {
   AMK_CHECK_ARG(y_div > 0, "amk_grouped_gemm_nt_acc: y_div must be positive");
-  return grouped_nt_impl("amk_grouped_gemm_nt_acc", A, lda, a_div, W, bias, offsets, perm, P, E, N, Kd, Y, y_div, stream);
-}
-
-static int grouped_nn_impl(const char* who, const float* A, int64_t lda, int a_div, const float* W, const float* scale,
-                           const int32_t* offsets, const int32_t* perm, int64_t P, int E, int N, int Kd,
-                           float* Y, int y_div, void* stream) {
-  const int rc = check_gemm(who, A, W, Y, offsets, perm, P, E, N, Kd, a_div, lda);
-  if (rc) return rc;
-  GemmParams g{};
-  g.A = A; g.W = W; g.scale = scale; g.Y = Y; g.offsets = offsets; g.perm = perm;
-  g.E = E; g.N = N; g.Kd = Kd; g.a_div = a_div; g.b_div = 1; g.lda = lda; g.y_div = y_div;
-  const unsigned mt = (unsigned)((P + 63) / 64 + E);
-  AMK_CHECK_SUPPORTED((uint64_t)mt * ((Kd + 127) / 128) < (1ull << 31), "%s: grid too large", who);
-  g.a_bytes = ((P - 1) / a_div * lda + N) * 4;   // rows 0 .. (P-1)/a_div of A
-  g.y_bytes = (y_div > 0 ? (P - 1) / y_div + 1 : P) * Kd * 4;
-  const bool wide = Kd >= 128 && Kd % 4 == 0 && N % 32 == 0 && g.a_bytes < (1ll << 31) && g.y_bytes < 0x7FFF0000ll && (int64_t)N * Kd * 4 < (1ll << 31);
-  AMK_CHECK_SUPPORTED(y_div == 0 || wide, "%s: the accumulating form needs Kd >= 128, N %% 32 == 0 and buffers below 2 GB", who);
-  if (wide && (y_div > 0 || !getenv("AMK_MOE_NARROW"))) {
-    g.ncol = (Kd + 127) / 128; g.slots = wg_slots();
-    hipLaunchKernelGGL(grouped_nn_wide_kernel, dim3(mt * g.ncol + (unsigned)g.slots / 2), dim3(256), 0, static_cast<hipStream_t>(stream), g);
-  } else if (g.a_bytes >= 0x7fff0000ll || (int64_t)N * Kd * 4 >= 0x7fff0000ll) {
-    amk_set_error("%s: A and one expert's weights must span < 2 GiB", who);
-    return AMK_EUNSUPPORTED;
-  } else if (Kd > 64) { g.ncol = (Kd + 127) / 128; hipLaunchKernelGGL(grouped_nn_kernel<2>, dim3(mt * g.ncol), dim3(256), 0, static_cast<hipStream_t>(stream), g); }
-  else {
-    g.ncol = 1;
-    static const bool short_ok = !(getenv("AMK_MOE_SHORT") && atoi(getenv("AMK_MOE_SHORT")) == 0);
-    if (short_ok && N >= 256 && (P + 63) / 64 < 16 * wg_slots() / 2)
-      hipLaunchKernelGGL((grouped_nn_kernel<1, true>), dim3(2 * mt), dim3(256), 0, static_cast<hipStream_t>(stream), g);
-    else
-      hipLaunchKernelGGL(grouped_nn_kernel<1>, dim3(mt), dim3(256), 0, static_cast<hipStream_t>(stream), g);
-  }
-  AMK_CHECK_LAUNCH(who);
-  return AMK_OK;
+  return grouped_impl(false, "amk_grouped_gemm_nt_acc", A, lda, a_div, W, bias, offsets, perm, P, E, N, Kd, Y, y_div, stream);
 }
 
 extern "C" int amk_grouped_gemm_nn(const float* A, int64_t lda, int a_div, const float* W, const float* scale,
                                    const int32_t* offsets, const int32_t* perm, int64_t P, int E, int N, int Kd,
                                    float* Y, void* stream) {
-  return grouped_nn_impl("amk_grouped_gemm_nn", A, lda, a_div, W, scale, offsets, perm, P, E, N, Kd, Y, 0, stream);
+  return grouped_impl(true, "amk_grouped_gemm_nn", A, lda, a_div, W, scale, offsets, perm, P, E, N, Kd, Y, 0, stream);
 }
 
 extern "C" int amk_grouped_gemm_nn_acc(const float* A, int64_t lda, int a_div, const float* W, const float* scale,
                                        const int32_t* offsets, const int32_t* perm, int64_t P, int E, int N, int Kd,
                                        float* Y, int y_div, void* stream) {
   AMK_CHECK_ARG(y_div > 0, "amk_grouped_gemm_nn_acc: y_div must be positive");
-  return grouped_nn_impl("amk_grouped_gemm_nn_acc", A, lda, a_div, W, scale, offsets, perm, P, E, N, Kd, Y, y_div, stream);
+  return grouped_impl(true, "amk_grouped_gemm_nn_acc", A, lda, a_div, W, scale, offsets, perm, P, E, N, Kd, Y, y_div, stream);
 }
 
 extern "C" int amk_grouped_gemm_wgrad(const float* G, int64_t ldg, int g_div, const float* X, int64_t ldx, int x_div,
@@ -1535,7 +1507,6 @@ extern "C" int amk_grouped_gemm_wgrad(const float* G, int64_t ldg, int g_div, co
   g.a_bytes = ((P - 1) / g_div * ldg + N) * 4;   // G buffer
   g.b_bytes = ((P - 1) / x_div * ldx + Kd) * 4;  // X buffer
   g.s_bytes = P * 4;
-  auto log2_of = [](int d) { int sft = 0; while ((1 << sft) < d) ++sft; return (1 << sft) == d ? sft : -1; };
   g.a_shift = log2_of(g_div); g.b_shift = log2_of(x_div);
   if (N >= 64 && Kd >= 64 && N + Kd >= 192 && g.a_bytes < 0x7FFF0000ll && g.b_bytes < 0x7FFF0000ll && g.s_bytes < (1ll << 31) &&
       (int64_t)N * Kd * 4 < 0x7FFF0000ll && !getenv("AMK_MOE_NARROW")) {

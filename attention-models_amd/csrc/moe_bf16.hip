@@ -55,14 +55,6 @@ struct Params {
   unsigned a_bytes, x_bytes, s_bytes;
 };
 
-__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(v, o, 64);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
 __device__ __forceinline__ int div_by(int p, int d, int sh) { return sh >= 0 ? p >> sh : p / d; }
 
 // This workgroup's unit = (expert, output tile, TR-pair row tile), in the order [expert][output tile][row tile]: the row
@@ -416,12 +408,6 @@ __global__ __launch_bounds__(256) void expert_sums_bf16_kernel(const void* __res
 
 using namespace amk_moe16;
 
-static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static int log2_of(int d) {
-  int s = 0;
-  while ((1 << s) < d) ++s;
-  return (1 << s) == d ? s : -1;
-}
 constexpr int64_t TWO_GIB = 1ll << 31;
 
 // shared checks; `width` is the row length of the gathered operand (Kd for nt, N for nn)
@@ -431,7 +417,7 @@ static int check_common(const char* who, const void* A, const void* W, const voi
   AMK_CHECK_ARG(P > 0 && E > 0 && N > 0 && Kd > 0 && a_div > 0, "%s: non-positive size P=%lld E=%d N=%d Kd=%d", who, (long long)P, E, N, Kd);
   AMK_CHECK_SUPPORTED(N % 8 == 0 && Kd % 8 == 0, "%s: N=%d and Kd=%d must be multiples of 8", who, N, Kd);
   AMK_CHECK_SUPPORTED(E <= 1024, "%s: at most 1024 experts", who);
-  AMK_CHECK_ARG(al16(A) && al16(W) && al16(Y), "%s: pointers must be 16-byte aligned", who);
+  AMK_CHECK_ARG(a16(A) && a16(W) && a16(Y), "%s: pointers must be 16-byte aligned", who);
   AMK_CHECK_ARG(lda % 8 == 0 && lda >= width, "%s: row stride %lld must be a multiple of 8 and at least %d", who, (long long)lda, width);
   AMK_CHECK_SUPPORTED(P < TWO_GIB && (int64_t)N * Kd * 2 < TWO_GIB, "%s: too many pairs or one expert's weights beyond 2 GiB", who);
   return AMK_OK;
@@ -443,7 +429,7 @@ static int grouped_impl(bool nn, bool narrow, const char* who, const void* A, in
   const int rc = check_common(who, A, W, Y, offsets, perm, P, E, N, Kd, a_div, lda, width);
   if (rc) return rc;
   AMK_CHECK_SUPPORTED(!narrow || out <= 64, "%s: at most 64 outputs (%s=%d); the wide entry point takes more", who, nn ? "Kd" : "N", out);
-  AMK_CHECK_ARG(al16(vec), "%s: pointers must be 16-byte aligned", who);
+  AMK_CHECK_ARG(a16(vec), "%s: pointers must be 16-byte aligned", who);
   const int64_t a_bytes = ((P - 1) / a_div * lda + width) * 2;
   AMK_CHECK_SUPPORTED(a_bytes < TWO_GIB && P * out * 4 < TWO_GIB, "%s: every buffer must stay below 2 GiB", who);
   Params g{};
@@ -488,7 +474,7 @@ static int wgrad_impl(bool narrow, const char* who, const void* G, int64_t ldg, 
   AMK_CHECK_SUPPORTED(!narrow || N <= 64 || Kd <= 64, "%s: N=%d or Kd=%d must be at most 64; the wide entry point takes both wider", who, N, Kd);
   const int tile = !narrow ? 0 : N <= 64 ? 1 : 2;
   AMK_CHECK_ARG(x_div > 0, "%s: non-positive size x_div=%d", who, x_div);
-  AMK_CHECK_ARG(al16(scale) && al16(dbias), "%s: pointers must be 16-byte aligned", who);
+  AMK_CHECK_ARG(a16(scale) && a16(dbias), "%s: pointers must be 16-byte aligned", who);
   AMK_CHECK_ARG(ldx % 8 == 0 && ldx >= Kd, "%s: row stride %lld must be a multiple of 8 and at least %d", who, (long long)ldx, Kd);
   const int64_t g_bytes = ((P - 1) / g_div * ldg + N) * 2, x_bytes = ((P - 1) / x_div * ldx + Kd) * 2;
   AMK_CHECK_SUPPORTED(g_bytes < TWO_GIB && x_bytes < TWO_GIB && P * 4 < TWO_GIB, "%s: every buffer must stay below 2 GiB", who);
@@ -549,7 +535,7 @@ extern "C" int amk_moe_expert_sums_bf16(const void* A, int a_is_bf16, int64_t ld
   AMK_CHECK_ARG(G > 0 && fan > 0 && E > 0 && d > 0 && a_div > 0, "%s: non-positive size G=%lld fan=%d E=%d d=%d", who, (long long)G, fan, E, d);
   AMK_CHECK_SUPPORTED(d % 8 == 0, "%s: d=%d must be multiples of 8", who, d);
   AMK_CHECK_SUPPORTED(E <= 1024 && fan <= 4096, "%s: at most 1024 experts and 4096 pairs per row", who);
-  AMK_CHECK_ARG(al16(A) && al16(Z) && al16(scale), "%s: pointers must be 16-byte aligned", who);
+  AMK_CHECK_ARG(a16(A) && a16(Z) && a16(scale), "%s: pointers must be 16-byte aligned", who);
   AMK_CHECK_ARG(lda % 8 == 0 && lda >= d, "%s: row stride %lld must be a multiple of 8 and at least %d", who, (long long)lda, d);
   AMK_CHECK_SUPPORTED(G < TWO_GIB, "%s: grid too large", who);
   const size_t lds = ((size_t)fan * 3 + E + 1) * 4;

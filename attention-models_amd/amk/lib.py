@@ -50,6 +50,9 @@ SIGNATURES = {
     "amk_attn_decode_ws_floats": (_L, [_I, _I, _I, _I]),
     "amk_attn_decode": (_I, [_P] * 9 + [_I] * 4 + [_L] * 9 + [_F, _P]),
     "amk_attn_decode_bf16": (_I, [_P] * 9 + [_I] * 4 + [_L] * 9 + [_F, _P]),
+    "amk_attn_prefill_ws_floats": (_L, [_I, _I, _I, _I, _I]),
+    "amk_attn_prefill": (_I, [_P] * 9 + [_I] * 5 + [_L] * 12 + [_F, _P]),
+    "amk_attn_prefill_bf16": (_I, [_P] * 9 + [_I] * 5 + [_L] * 12 + [_F, _P]),
     "amk_gemm_rows_bf16": (_I, [_P, _L, _P, _L, _P, _P, _L, _I, _I, _I, _I, _P]),
     "amk_attn_bwd_ws_floats": (_L, [_I, _I, _I, _I, _I]),
     "amk_attn_bwd": (_I, [_P] * 12 + [_I] * 5 + [_L] * 24 + [_F, _I, _P]),

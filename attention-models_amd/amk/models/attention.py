@@ -68,6 +68,18 @@ class SoftmaxAttention(nn.Module):
                                      key_mask=context_mask, ws=ws)
         return self.W_o(o)
 
+    def prefill_rows(self, x, cache, n_dev=None, context_mask=None, append=True, ws=None):
+        """decode_step for n rows x (B, n, dim) in one pass (ops.attention_prefill).  append: the rows' K|V become cache
+        rows ``n_dev`` .. ``n_dev + n - 1`` and row i attends rows 0 .. n_dev + i.  Otherwise cross-attention over the
+        whole ``cache`` from project_context, with its key mask."""
+        if append:
+            q, kv = ops.linear2(x, self.q[0].weight, self.kv[0].weight)
+            o = ops.attention_prefill(q, kv, cache, n_dev, self.num_heads, self.dim_head, self.scale, ws=ws)
+        else:
+            o = ops.attention_prefill(self.q(x), None, cache, None, self.num_heads, self.dim_head, self.scale,
+                                      key_mask=context_mask, ws=ws)
+        return self.W_o(o)
+
 
 class SwitchHeadAttention(StackedExpertsMixin, nn.Module):
     """SwitchHead attention (reference: models/switchhead_attention.py:18-116).

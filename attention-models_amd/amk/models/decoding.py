@@ -6,6 +6,7 @@ one row per step by the decode kernel itself (csrc/attn_decode.hip, append mode)
 context (B, L, 2*h*d), projected ONCE.  The position is a device int32: the kernel reads the number of valid rows on
 the device, so a captured step can be replayed for every position.  ``host_pos`` mirrors it on the host for the eager
 loop's capacity check only; a graph replay advances the device position alone (see ``Parti.sample``).
+``Decoder.prefill`` fills n rows of every cache in one pass (csrc/attn_prefill.hip) from the same position.
 
 A bf16 state (``Decoder.init_state`` under bf16 autocast, AMK_DECODE_BF16) holds bf16 caches and cross K|V and its own
 bf16 copies of the Linear weights the step reads, so that a captured step reads state-owned and parameter memory only
@@ -37,9 +38,10 @@ class DecoderState:
         self.pos.zero_()
         self.host_pos = 0
 
-    def advance(self):
-        self.pos.add_(1)
-        self.host_pos += 1
+    def advance(self, n=1):
+        """n more rows are valid: one after a step, the whole chunk after ``Decoder.prefill``."""
+        self.pos.add_(int(n))
+        self.host_pos += int(n)
 
     def set_position(self, n):
         self.pos.fill_(int(n))

@@ -132,6 +132,44 @@ class Parti(nn.Module):
         state.advance()
         return logits
 
+    @torch.no_grad()
+    def prefill(self, state, tokens, all_logits=False):
+        """The decode conditioned on tokens the caller already has, in ONE pass (``Decoder.prefill``, the many-row kernel
+        of csrc/attn_prefill.hip): what ``next_logits(state, None)`` followed by ``next_logits(state, tokens[:, i])`` in
+        turn compute and leave in the caches.  tokens (B, n) are the image tokens from the state's position on.  At
+        position 0 the start-token row is prepended, so n + 1 rows go through and the last one is the row of token n;
+        at position p > 0 the rows are token_emb(tokens) + pe[p - 1 ...], as ``next_logits`` feeds them.  Returns the
+        last row's logits (B, V), or every row's (B, rows, V) with ``all_logits``; f32.  The position advances by the
+        number of rows."""
+        if tokens.dim() != 2 or tokens.shape[0] != state.batch:
+            raise ValueError(f"prefill takes tokens (B={state.batch}, n); got {tuple(tokens.shape)}")
+        p, n = state.host_pos, tokens.shape[1]
+        rows = n + 1 if p == 0 else n
+        if rows < 1:
+            raise ValueError("prefill needs at least one token after position 0")
+        if p + rows > state.capacity:
+            raise RuntimeError(f"the decode state has no room for {rows} rows: {p} of {state.capacity} are taken")
+        x = self.token_emb(tokens) + self.pos_enc.pe[max(p - 1, 0):max(p - 1, 0) + n]
+        x = self.pos_enc.dropout(x)
+        if p == 0:
+            x = torch.cat((self.start_token.expand(state.batch, 1, -1), x), dim=1)
+        out = self.transformer_decoder.prefill(self.init_norm(x), state)
+        if all_logits:
+            logits = self.transformer_decoder.logits_rows(out, state, self.final_norm, self.to_logits)
+        else:
+            logits = self.transformer_decoder.logits(out[:, -1:], state, self.final_norm, self.to_logits)
+        state.advance(rows)
+        return logits
+
+    def _prefill_prefix(self, state, prefix_ids, trace):
+        """``prefill`` of a sample's given tokens from position 0: the logits of the first token to draw, with every
+        earlier step's logits appended to ``trace`` so that it stays indexed by the absolute step."""
+        if trace is None:
+            return self.prefill(state, prefix_ids)
+        logits = self.prefill(state, prefix_ids, all_logits=True)
+        trace.extend(logits[:, i].clone() for i in range(logits.shape[1] - 1))
+        return logits[:, -1].contiguous()
+
     def _draw(self, logits, ids, noise, tau, p):
         """generate's sampler on (B, V) logits into ids (B, 1) int64, in place: top-ceil((1 - p) V) filter, then the
         argmax of logits + Gumbel noise (= the argmax of the Gumbel-softmax at any temperature tau > 0).  noise None:
@@ -148,29 +186,45 @@ class Parti(nn.Module):
         ids.copy_((filter_logits(logits.unsqueeze(1), p=p)[:, 0, :] + noise).argmax(dim=-1, keepdim=True))
 
     @torch.no_grad()
-    def sample(self, text_hidden, gumbel=None, trace=None, tau=1.0, p=0.9, graph=False):
+    def sample(self, text_hidden, gumbel=None, trace=None, tau=1.0, p=0.9, graph=False, prefix_ids=None):
         """Sample ``vq.num_patches`` tokens from the model as trained -- context_norm, init_norm, causal self-attention,
         final_norm -- one token per step against cached keys and values, with ``generate``'s sampler; returns
         ``vq.decode_indices(ids)``.  gumbel: explicit noise (steps, B, V); trace: a list that receives every step's
         unfiltered logits (B, V).  graph=True: the step from the previous ids on the device to the next ids on the
         device is captured once as a HIP graph and replayed ``num_patches - 1`` times (the start-token step stays
         eager); without explicit noise the noise is then drawn inside the graph by torch's capture-aware generator.  The
-        captured step and its caches stay alive with the module until ``drop_decode_graph()`` (see ``_sample_graphed``)."""
+        captured step and its caches stay alive with the module until ``drop_decode_graph()`` (see ``_sample_graphed``).
+
+        prefix_ids (B, k), k < num_patches: the sample's first k tokens, given (the first rows of an image from
+        ``vq.encode_imgs``, say).  They are kept as they are and go through the decoder in one ``prefill`` pass; the
+        loop starts at step k.  ``gumbel`` and ``trace`` stay indexed by the absolute step (the trace receives the given
+        steps' logits too).  With graph=True the prefill runs eagerly and the captured step is replayed after it: that
+        step reads the position on the device, so nothing new is captured."""
         if not tau > 0:
             raise ValueError("sample needs a temperature tau > 0")
         steps = self.vq.num_patches
         text_hidden = self._context(text_hidden)
         if gumbel is not None and gumbel.shape[0] < steps:
             raise ValueError(f"gumbel holds {gumbel.shape[0]} steps of noise, the sample has {steps}")
+        k = 0
+        if prefix_ids is not None:
+            if prefix_ids.dim() != 2 or prefix_ids.shape[0] != text_hidden.shape[0] or prefix_ids.shape[1] >= steps:
+                raise ValueError(f"prefix_ids must be (B={text_hidden.shape[0]}, k < {steps}); got {tuple(prefix_ids.shape)}")
+            k = prefix_ids.shape[1]
         if graph:
-            indices = self._sample_graphed(text_hidden, gumbel, trace, tau, p)
+            indices = self._sample_graphed(text_hidden, gumbel, trace, tau, p, prefix_ids if k else None)
             return self.vq.decode_indices(indices)
         state = self.begin_decode(text_hidden)
         b = state.batch
         indices = torch.empty((b, steps), dtype=torch.long, device=state.device)
         token = torch.zeros((b, 1), dtype=torch.long, device=state.device)
-        for i in range(steps):
-            logits = self.next_logits(state, token if i else None)
+        if k:
+            indices[:, :k] = prefix_ids
+        for i in range(k, steps):
+            if i == k and k:
+                logits = self._prefill_prefix(state, prefix_ids, trace)   # the start token and the k given tokens
+            else:
+                logits = self.next_logits(state, token if i else None)
             if trace is not None:
                 trace.append(logits.clone())
             self._draw(logits, token, None if gumbel is None else gumbel[i], tau, p)
@@ -181,15 +235,20 @@ class Parti(nn.Module):
         """Free the captured step of ``sample(graph=True)`` with its caches and noise buffer (see ``_sample_graphed``)."""
         _DECODE_GRAPHS.pop(self, None)
 
-    def _sample_graphed(self, text_hidden, gumbel, trace, tau, p):
+    def _sample_graphed(self, text_hidden, gumbel, trace, tau, p, prefix_ids=None):
         """One captured step per module, kept in a table outside the module (weakly keyed: it goes with the module, is
         not part of its attributes or state_dict, and copy.deepcopy does not meet it) until ``drop_decode_graph()`` or
         a call whose key differs: it holds the DecoderState -- every layer's (B, capacity, 2*h*d) cache -- and the
         noise buffer.  A captured graph replays against the ADDRESSES it was captured with, so the key holds, besides
         the shapes and the sampler's settings, the train / eval mode, ops.GEMM_MODE and the data pointer of every
         parameter and buffer: a module moved, cast or re-flattened is captured anew instead of replayed on stale
-        memory.  Parameter VALUES may change between calls (the graph reads them where they are)."""
+        memory.  Parameter VALUES may change between calls (the graph reads them where they are).
+
+        prefix_ids: the sample's given tokens.  They are no part of the key: the capture is the one-row step, taken
+        after an eager start-token step as without a prefix; the prefill then runs eagerly from position 0 again and
+        rewrites every cache row the start step and the warm-up wrote, and the replays go on from position k + 1."""
         steps = self.vq.num_patches
+        k = 0 if prefix_ids is None else prefix_ids.shape[1]
         key = (tuple(text_hidden.shape), text_hidden.device, None if gumbel is None else tuple(gumbel.shape),
                float(tau), float(p), steps, self.training, ops.GEMM_MODE,
                self.transformer_decoder.decode_dtype(text_hidden.device), ops.DECODE_BF16,
@@ -207,14 +266,15 @@ class Parti(nn.Module):
         if noise is not None:
             noise.copy_(gumbel)
         indices = torch.empty((state.batch, steps), dtype=torch.long, device=state.device)
-        # the start-token step, eager
-        logits = self.next_logits(state, None)
-        if trace is not None:
-            trace.append(logits.clone())
-        self._draw(logits, token, None if noise is None else noise[0], tau, p)
-        indices[:, 0] = token[:, 0]
-        if steps == 1:
-            return indices
+        if k == 0 or cached["graph"] is None:
+            # the start-token step, eager (with a prefix: only as the ground the capture below warms up on)
+            logits = self.next_logits(state, None)
+            if trace is not None and k == 0:
+                trace.append(logits.clone())
+            self._draw(logits, token, None if noise is None else noise[0], tau, p)
+            indices[:, 0] = token[:, 0]
+            if steps == 1:
+                return indices
 
         def step():
             # previous ids (token) -> next ids (token, in place); position, pe row and noise row by the device position
@@ -252,7 +312,15 @@ class Parti(nn.Module):
             # the warm-up runs moved the position and the ids; the cache row they wrote is rewritten before it is read
             state.set_position(1)
             token.copy_(first)
-        for i in range(1, steps):
+        if k:
+            state.reset()
+            logits = self._prefill_prefix(state, prefix_ids, trace)
+            if trace is not None:
+                trace.append(logits.clone())
+            self._draw(logits, token, None if noise is None else noise[k], tau, p)
+            indices[:, :k] = prefix_ids
+            indices[:, k] = token[:, 0]
+        for i in range(k + 1, steps):
             cached["graph"].replay()
             if trace is not None:
                 trace.append(cached["logits"].clone())

@@ -5,6 +5,7 @@ Plain PyTorch except for the attention cores, the LayerNorms and the Linear laye
 ``Decoder.init_state`` / ``Decoder.step`` are the causal forward one row at a time against cached keys and values
 (models/decoding.py, the single-token kernel of csrc/attn_decode.hip); ``Transformer.begin_decode`` / ``next_logits`` /
 ``sample`` build the trained model's sampling loop on them.  ``Transformer.generate`` stays the reference's loop.
+``Decoder.prefill`` / ``Transformer.prefill`` put n given rows through in one pass (csrc/attn_prefill.hip) and fill the caches.
 """
 import torch
 import torch.nn as nn
@@ -233,8 +234,10 @@ class Decoder(nn.Module):
             x = layer.feed_forward(y) + x
         return x
 
-    def _step_bf16(self, x, state):
-        """The step on a bf16 state.  The residual stream x stays f32; every LayerNorm that only feeds projections
+    def _step_bf16(self, x, state, prefill_ws=None):
+        """The step on a bf16 state, or -- with ``prefill_ws``, a workspace of ops.attention_prefill -- the same arithmetic
+        on the n rows of x (B, n, dim) in one pass (``prefill``; above ops.ROWS_GEMM_MAX_M rows ``linear_rows`` goes to
+        the library's bf16 GEMM).  The residual stream x stays f32; every LayerNorm that only feeds projections
         writes bf16 directly (amk_add_layernorm_mixed_fwd, the bf16 branch output as its bf16 operand and the f32
         stream as the residual); projections, W_o and the FFN's two Linear layers run on the row GEMM
         (amk_gemm_rows_bf16) with bf16 output, q and kv of self-attention as ONE product whose column slices the
@@ -242,7 +245,11 @@ class Decoder(nn.Module):
         width is no multiple of 8 or above 4096, as int(dim * 8 / 3) is at dim 64 and 512 -- gelu(val) * gate and the
         LayerNorm as f32 torch ops on the bf16 pre-activations.  A layer's FFN output joins the stream inside the
         next layer's first LayerNorm."""
-        b = state.batch
+        b, n = state.batch, x.shape[1]
+        if prefill_ws is None:
+            attend, ws = ops.attention_decode, state.ws
+        else:
+            attend, ws = ops.attention_prefill, prefill_ws
         branch = None                       # the bf16 branch output not yet added to the stream
         for layer, w, self_kv, cross_kv in zip(self.layers, state.weights, state.self_kv, state.cross_kv):
             sa, ca = layer.self_attn, layer.cross_attn
@@ -251,27 +258,67 @@ class Decoder(nn.Module):
                 y = ops.layer_norm_to_bf16(x, None, layer.norm1.gamma, layer.norm1.beta)[1]
             else:
                 x, y = ops.layer_norm_to_bf16(branch, x, layer.norm1.gamma, layer.norm1.beta)
-            qkv = ops.linear_rows(y.view(b, -1), w["qkv"]).view(b, 1, 3 * hd)
-            o = ops.attention_decode(qkv[:, :, :hd], qkv[:, :, hd:], self_kv, state.pos, sa.num_heads, sa.dim_head, sa.scale,
-                                     ws=state.ws)
-            o = ops.linear_rows(o.view(b, hd), w["wo"], sa.W_o.bias)
-            x, y = ops.layer_norm_to_bf16(o.view(b, 1, -1), x, layer.norm2.gamma, layer.norm2.beta)
-            q = ops.linear_rows(y.view(b, -1), w["cq"]).view(b, 1, hd)
-            o = ops.attention_decode(q, None, cross_kv, None, ca.num_heads, ca.dim_head, ca.scale,
-                                     key_mask=state.context_mask, ws=state.ws)
-            o = ops.linear_rows(o.view(b, hd), w["cwo"], ca.W_o.bias)
-            x, y = ops.layer_norm_to_bf16(o.view(b, 1, -1), x, layer.norm3.gamma, layer.norm3.beta)
+            qkv = ops.linear_rows(y.view(b * n, -1), w["qkv"]).view(b, n, 3 * hd)
+            o = attend(qkv[:, :, :hd], qkv[:, :, hd:], self_kv, state.pos, sa.num_heads, sa.dim_head, sa.scale, ws=ws)
+            o = ops.linear_rows(o.view(b * n, hd), w["wo"], sa.W_o.bias)
+            x, y = ops.layer_norm_to_bf16(o.view(b, n, -1), x, layer.norm2.gamma, layer.norm2.beta)
+            q = ops.linear_rows(y.view(b * n, -1), w["cq"]).view(b, n, hd)
+            o = attend(q, None, cross_kv, None, ca.num_heads, ca.dim_head, ca.scale, key_mask=state.context_mask, ws=ws)
+            o = ops.linear_rows(o.view(b * n, hd), w["cwo"], ca.W_o.bias)
+            x, y = ops.layer_norm_to_bf16(o.view(b, n, -1), x, layer.norm3.gamma, layer.norm3.beta)
             norm = layer.feed_forward.ff[2]
-            ab = ops.linear_rows(y.view(b, -1), w["ff1"])
+            ab = ops.linear_rows(y.view(b * n, -1), w["ff1"])
             inner = ab.shape[1] // 2
             if inner % 8 == 0 and inner <= 4096 and ab.stride(0) % 8 == 0:
                 g = ops.geglu_ln_bf16_fwd(ab, norm.gamma, norm.beta)[0]
             else:
                 val, gate = ab.float().chunk(2, dim=-1)
-                g = torch.empty((b, (inner + 7) // 8 * 8), device=ab.device, dtype=torch.bfloat16)[:, :inner]
+                g = torch.empty((b * n, (inner + 7) // 8 * 8), device=ab.device, dtype=torch.bfloat16)[:, :inner]
                 g.copy_(F.layer_norm(gate * F.gelu(val), (inner,), norm.gamma, norm.beta))   # rows at a stride of 8
-            branch = ops.linear_rows(g, w["ff2"]).view(b, 1, -1)
+            branch = ops.linear_rows(g, w["ff2"]).view(b, n, -1)
         return x + branch.float() if branch is not None else x
+
+    @torch.no_grad()
+    def prefill(self, x, state):
+        """``forward`` with the causal mask for n new rows x (B, n, dim) at the state's position, in one pass: the rows'
+        keys and values become cache rows pos .. pos + n - 1 and row i attends rows 0 .. pos + i (ops.attention_prefill,
+        append mode for self-attention, read mode for cross-attention: no tile kernel and no mask tensor in either
+        dtype).  Returns (B, n, dim); the caller advances the position (``state.advance(n)``).  The refusals are those of
+        ``step``; a bf16 state runs ``_step_bf16``'s arithmetic on the n rows with autocast disabled inside.  Eager
+        only: the launch's grid depends on n, so a prefill is never captured."""
+        if x.dim() != 3 or x.shape[1] < 1 or x.shape[0] != state.batch:
+            raise ValueError(f"prefill takes n >= 1 rows per sequence, (B={state.batch}, n, dim); got {tuple(x.shape)}")
+        n = x.shape[1]
+        if state.host_pos + n > state.capacity:
+            raise RuntimeError(f"the decode state has no room for {n} rows: {state.host_pos} of {state.capacity} are taken")
+        attn = self.layers[0].self_attn
+        need = max(ops.attention_prefill_ws_floats(state.batch, attn.num_heads, attn.dim_head, rows, n)
+                   for rows in (state.capacity, state.cross_kv[0].shape[1]))
+        ws = torch.empty((need,), device=x.device, dtype=torch.float32)   # one for every call: ordered on the stream
+        if state.dtype == torch.bfloat16:
+            with torch.autocast("cuda", enabled=False):
+                return self._step_bf16(x.float(), state, prefill_ws=ws)
+        if x.is_cuda and torch.is_autocast_enabled():
+            raise RuntimeError(ops.DECODE_AUTOCAST_REFUSAL)
+        for layer, self_kv, cross_kv in zip(self.layers, state.self_kv, state.cross_kv):
+            x, y = layer.norm2(x, layer.self_attn.prefill_rows(layer.norm1(x), self_kv, state.pos, ws=ws))
+            x, y = layer.norm3(x, layer.cross_attn.prefill_rows(y, cross_kv, context_mask=state.context_mask, append=False,
+                                                                  ws=ws))
+            x = layer.feed_forward(y) + x
+        return x
+
+    @torch.no_grad()
+    def logits_rows(self, out, state, norm, linear):
+        """``logits`` for every row of ``out`` (B, n, dim): (B, n, classes) f32."""
+        if state.dtype != torch.bfloat16:
+            return linear(norm(out))
+        if state.head is None:
+            raise RuntimeError("this decode state was made without a head: pass init_state(head=...)")
+        with torch.autocast("cuda", enabled=False):
+            gamma, beta = (norm.gamma, norm.beta) if hasattr(norm, "gamma") else (norm.weight, norm.bias)
+            y = ops.layer_norm_to_bf16(out.float(), None, gamma, beta)[1]
+            lg = ops.linear_rows(y.view(-1, y.shape[-1]), state.head["head"], linear.bias, torch.float32, w32=linear.weight)
+            return lg.reshape(out.shape[0], out.shape[1], -1)
 
     @torch.no_grad()
     def logits(self, out, state, norm, linear):
@@ -363,16 +410,46 @@ class Transformer(nn.Module):
         return logits
 
     @torch.no_grad()
-    def sample(self, src_seq, max_len, gumbel=None):
+    def prefill(self, state, tokens, all_logits=False):
+        """``next_logits`` for the n target tokens ``tokens`` (B, n) at positions pos .. pos + n - 1 in ONE pass
+        (``Decoder.prefill``): what n calls of ``next_logits(state, tokens[:, i])`` compute and leave in the caches.
+        Returns the last row's logits (B, n_classes), or every row's (B, n, n_classes) with ``all_logits``; f32.  The
+        position advances by n."""
+        if tokens.dim() != 2 or tokens.shape[0] != state.batch or tokens.shape[1] < 1:
+            raise ValueError(f"prefill takes tokens (B={state.batch}, n >= 1); got {tuple(tokens.shape)}")
+        p, n = state.host_pos, tokens.shape[1]
+        if p + n > state.capacity:
+            raise RuntimeError(f"the decode state has no room for {n} rows: {p} of {state.capacity} are taken")
+        x = self.pos_enc.dropout(self.dec_input_proj(tokens) + self.pos_enc.pe[p:p + n])
+        out = self.decoder.prefill(self.dec_init_norm(x), state)
+        if all_logits:
+            logits = self.decoder.logits_rows(out, state, self.dec_final_norm, self.linear)
+        else:
+            logits = self.decoder.logits(out[:, -1:], state, self.dec_final_norm, self.linear)
+        state.advance(n)
+        return logits
+
+    @torch.no_grad()
+    def sample(self, src_seq, max_len, gumbel=None, prefix=None):
         """``generate``'s loop on the trained (causal, normed) model with cached keys and values: start token 1,
         Gumbel-argmax over the unfiltered logits, stop when the FIRST sequence draws the end token 2 (one host read per
-        step) or after ``max_len`` tokens.  gumbel: explicit noise (steps, B, n_classes)."""
+        step) or after ``max_len`` tokens.  gumbel: explicit noise (steps, B, n_classes), indexed by the absolute step.
+        prefix (B, k), k < max_len: target tokens the caller already has; they follow the start token, go through the
+        decoder in one ``prefill`` pass and are kept in the result, and the loop starts at step k."""
         if max_len is None or max_len < 1:
             raise ValueError("Transformer.sample needs a positive max_len: it sizes the key / value cache")
         end_token = 2
         out_seq = torch.ones((src_seq.shape[0], 1), dtype=torch.long, device=src_seq.device)
         state = self.begin_decode(src_seq, capacity=max_len)
-        for i in range(max_len):
+        first = 0
+        if prefix is not None:
+            if prefix.dim() != 2 or prefix.shape[0] != src_seq.shape[0] or prefix.shape[1] >= max_len:
+                raise ValueError(f"prefix must be (B={src_seq.shape[0]}, k < max_len={max_len}); got {tuple(prefix.shape)}")
+        if prefix is not None and prefix.shape[1] > 0:
+            first = prefix.shape[1]
+            out_seq = torch.cat((out_seq, prefix.to(out_seq)), dim=1)
+            self.prefill(state, out_seq[:, :-1])      # rows 0 .. k - 1; the loop feeds the prefix's last token
+        for i in range(first, max_len):
             logits = self.next_logits(state, out_seq[:, -1])
             noise = gumbel[i] if gumbel is not None else -torch.empty_like(logits).exponential_().log()
             last_token = (logits + noise).argmax(dim=-1)

@@ -566,6 +566,82 @@ def attention_decode_ws_floats(B, num_heads, dim_head, capacity):
     return int(_lib.load().amk_attn_decode_ws_floats(int(B), int(num_heads), int(dim_head), int(capacity)))
 
 
+def attention_prefill(q2, kv_new2, cache, n_dev, num_heads, dim_head, scale, key_mask=None, ws=None):
+    """n new query rows per (batch, head) against a key / value cache in one pass (csrc/attn_prefill.hip), inference
+    only: the n-row twin of attention_decode, for a decode that starts from tokens the caller already has.
+
+    q2 (B, n, h*d); cache (B, capacity, 2*h*d); n_dev: int32 device tensor holding p0, the number of valid cache rows.
+    kv_new2 (B, n, 2*h*d): append mode -- cache rows p0 .. p0 + n - 1 become kv_new2 and row i attends rows 0 .. p0 + i
+    (the causal mask's rows, from indices: no mask tensor).  kv_new2 None: read mode -- every row attends rows
+    0 .. p0 - 1, all `capacity` rows when n_dev is None.  key_mask: bool / uint8 (B, capacity), True = keep.  Returns
+    (B, n, h*d) in the cache's dtype.  Dtypes, strides, alignment and ws follow attention_decode (ws: at least
+    attention_prefill_ws_floats(B, h, d, capacity, n) float32 elements; None allocates one).  Never captured: its grid
+    depends on n."""
+    if any(t is not None and t.requires_grad for t in (q2, kv_new2, cache)):
+        raise RuntimeError("attention_prefill is inference only: it has no backward; call it under torch.no_grad() "
+                           "on tensors that do not require grad")
+    if cache.dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError(f"attention_prefill runs on a float32 or a bfloat16 cache; got {cache.dtype}")
+    for t in (q2, kv_new2, cache):
+        if t is not None and not t.is_cuda:
+            raise RuntimeError("amk ops run only on MI355X (HIP) tensors; got a CPU tensor. There is no CPU fallback.")
+    if q2.dtype != cache.dtype or (kv_new2 is not None and kv_new2.dtype != cache.dtype):
+        raise RuntimeError(f"attention_prefill: q ({q2.dtype}) and kv_new ({None if kv_new2 is None else kv_new2.dtype}) "
+                           f"must have the cache's dtype ({cache.dtype})")
+    b16 = cache.dtype == torch.bfloat16
+    H, D = int(num_heads), int(dim_head)
+    B, capacity = cache.shape[0], cache.shape[1]
+    hd = H * D
+    if (q2.dim() != 3 or q2.shape[0] != B or q2.shape[1] < 1 or q2.shape[2] != hd or cache.dim() != 3
+            or cache.shape[2] != 2 * hd or not cache.is_contiguous()):
+        raise RuntimeError(f"attention_prefill: q {tuple(q2.shape)} / cache {tuple(cache.shape)} do not fit "
+                           f"B={B}, heads={H}, dim_head={D} (q (B, n >= 1, h*d); cache: contiguous (B, capacity, 2*h*d))")
+    n = q2.shape[1]
+    if kv_new2 is not None and tuple(kv_new2.shape) != (B, n, 2 * hd):
+        raise RuntimeError(f"attention_prefill: kv_new {tuple(kv_new2.shape)} is not n={n} (kv h d) rows per batch")
+    if n_dev is not None and (n_dev.dtype != torch.int32 or not n_dev.is_cuda or n_dev.numel() != 1):
+        raise RuntimeError("attention_prefill: n_dev must be a one-element int32 device tensor")
+    if kv_new2 is not None and n_dev is None:
+        raise RuntimeError("attention_prefill: append mode needs n_dev")
+    unit = 8 if b16 else 4
+    for t, what in ((q2, "q"), (kv_new2, "kv_new")):
+        if t is not None and (t.stride(2) != 1 or (B > 1 and t.stride(0) % unit) or (n > 1 and t.stride(1) % unit)
+                              or t.data_ptr() % 16):
+            raise RuntimeError(f"attention_prefill consumes {what} in place: unit last stride, row strides that are multiples "
+                               f"of {unit} elements and a 16-byte aligned start (a contiguous tensor or a column slice of one)")
+    km = _mask_u8(key_mask, (B, capacity), "key_mask")
+    L = _lib.load()
+    o = torch.empty((B, n, hd), device=q2.device, dtype=cache.dtype)
+    need = L.amk_attn_prefill_ws_floats(B, H, D, capacity, n)
+    if ws is None:
+        ws = torch.empty((need,), device=q2.device, dtype=torch.float32)
+    elif ws.dtype != torch.float32 or not ws.is_cuda or not ws.is_contiguous() or ws.numel() < need:
+        raise RuntimeError(f"attention_prefill: ws must be a contiguous float32 device tensor of at least {need} elements")
+    esz = 2 if b16 else 4
+
+    def strides(t, width):   # (sb, st) of a (B, n, width) tensor; a size-1 axis may carry any stride
+        if t is None:
+            return n * width, width
+        st = t.stride(1) if n > 1 else width
+        return (t.stride(0) if B > 1 else n * st), st
+
+    q_sb, q_st = strides(q2, hd)
+    n_sb, n_st = strides(kv_new2, 2 * hd)
+    fn, name = (L.amk_attn_prefill_bf16, "amk_attn_prefill_bf16") if b16 else (L.amk_attn_prefill, "amk_attn_prefill")
+    with _timed("attn_prefill"):
+        rc = fn(_ptr(q2), _ptr(kv_new2), ctypes.c_void_p(kv_new2.data_ptr() + esz * hd) if kv_new2 is not None else _NULL,
+                _ptr(cache), ctypes.c_void_p(cache.data_ptr() + esz * hd), _ptr(o), _ptr(ws), _ptr(n_dev), _ptr(km),
+                B, H, D, capacity, n, q_sb, q_st, D, n_sb, n_st, D, capacity * 2 * hd, 2 * hd, D, n * hd, hd, D,
+                float(scale), _stream())
+    _lib.check(rc, name)
+    return o
+
+
+def attention_prefill_ws_floats(B, num_heads, dim_head, capacity, n):
+    """Elements of the float32 workspace attention_prefill needs at these sizes (amk_attn_prefill_ws_floats)."""
+    return int(_lib.load().amk_attn_prefill_ws_floats(int(B), int(num_heads), int(dim_head), int(capacity), int(n)))
+
+
 # AMK_DECODE_BF16 (default 1): under bf16 autocast Decoder.init_state builds a bf16 decode state -- bf16 caches, the state's
 # own bf16 weight copies, the step on amk_attn_decode_bf16 and amk_gemm_rows_bf16 (models/transformer.py).  0: the decode
 # refuses to run under autocast, as it did before that path existed.  Read once per process.

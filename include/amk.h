@@ -190,6 +190,53 @@ int amk_attn_decode_bf16(const void* q, const void* k_new, const void* v_new, vo
                          int64_t c_sb, int64_t c_st, int64_t c_sh, int64_t o_sb, int64_t o_sh,
                          float scale, void* stream);
 
+/* --------------------------------------------------------------------------
+ * The many-row form of amk_attn_decode: n new query rows per (batch, head) in one pass, for a decode that starts from
+ * tokens the caller already has (csrc/attn_prefill.hip).  Replaces, for the n rows of a prompt, the core of
+ * models/softmax_attention.py:62-76 as the sampling loop of models/parti.py:135-152 needs it on a cache that holds
+ * p0 rows.  Inference only.  (Added within 0.4.0, same library version: an addition only.)
+ *
+ *   q, k_new, v_new  n rows per (b, h), addressed  base + b*sb + i*st + h*sh + d: the (B, n, h*D) and (B, n, 2*h*D)
+ *                    projection outputs in place, or column slices of one; k_new and v_new share their strides.
+ *   k_cache, v_cache, key_mask, scale, stream: as for amk_attn_decode.
+ *   n_dev            DEVICE int32 holding p0, the number of rows already valid.  Never written.
+ *   o                (B, n, h*D) under (o_sb, o_st, o_sh).
+ *
+ * Append mode (k_new, v_new non-null; causal self-attention): with p0 = *n_dev and p0 + n <= capacity, cache row
+ * p0 + i becomes row i of k_new / v_new, bitwise, for every i < n, and row i of o is the softmax attention of q_i over
+ * rows 0 .. p0 + i.  The causal predicate is computed from the indices; there is no mask tensor.  Keys j >= p0 are
+ * taken from k_new / v_new, never from the cache, and every new cache row has exactly one writer in the launch, so no
+ * workgroup reads a row that another writes.
+ * Read mode (k_new, v_new NULL; the cross-attention of a prefill pass): all n rows attend rows 0 .. p0 - 1, all
+ * `capacity` rows with n_dev NULL; masked keys are filled with -1e9.  The caches are not written.
+ * Out of range (append: p0 < 0 or p0 + n > capacity; read: p0 < 1 or p0 > capacity): nothing is read or written.
+ *
+ * Row i runs the chain of amk_attn_decode at J = p0 + i + 1 keys (read mode: J = p0) with 64 keys per chunk: f32
+ * scores in the exp2 domain, one maximum and one exp2 per key and chunk, the key groups added in order, and for a row
+ * with more than one chunk (m, l, o[D]) per chunk in ws and a second launch on `stream` that adds them in chunk order.
+ * A workgroup loads its chunk's K and V once for a block of 16 rows.  No f32 atomics on data and no hand-off between
+ * workgroups: bitwise reproducible, and a row's result depends neither on B nor on how the rows are blocked.
+ * amk_attn_prefill_bf16: q, k_new, v_new, the caches and o are bf16, the strides multiples of 8 elements; scores,
+ * softmax and sums stay f32 and o is rounded ONCE, to nearest even, as amk_attn_decode_bf16 does.
+ * ws: amk_attn_prefill_ws_floats(B, H, D, capacity, n) floats, 16-byte aligned, contents undefined on entry and return.
+ * AMK_EUNSUPPORTED before any device work: D not a multiple of 32 from 32 to 256, B or H above 65535, a grid beyond
+ * 2^31 - 1 workgroups.  AMK_EINVAL: a null q, cache, o or ws, only one of k_new / v_new, append mode without n_dev, a
+ * non-positive size (n = 0 included), a pointer not 16-byte aligned (n_dev: 4), a stride off its multiple (f32: 4).
+ * -------------------------------------------------------------------------- */
+int64_t amk_attn_prefill_ws_floats(int B, int H, int D, int capacity, int n);
+int amk_attn_prefill(const float* q, const float* k_new, const float* v_new, float* k_cache, float* v_cache,
+                     float* o, float* ws, const int32_t* n_dev, const uint8_t* key_mask,
+                     int B, int H, int D, int capacity, int n,
+                     int64_t q_sb, int64_t q_st, int64_t q_sh, int64_t new_sb, int64_t new_st, int64_t new_sh,
+                     int64_t c_sb, int64_t c_st, int64_t c_sh, int64_t o_sb, int64_t o_st, int64_t o_sh,
+                     float scale, void* stream);
+int amk_attn_prefill_bf16(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache,
+                          void* o, float* ws, const int32_t* n_dev, const uint8_t* key_mask,
+                          int B, int H, int D, int capacity, int n,
+                          int64_t q_sb, int64_t q_st, int64_t q_sh, int64_t new_sb, int64_t new_st, int64_t new_sh,
+                          int64_t c_sb, int64_t c_st, int64_t c_sh, int64_t o_sb, int64_t o_st, int64_t o_sh,
+                          float scale, void* stream);
+
 /* A few rows times a weight matrix on bf16 MFMA (csrc/gemm_rows_bf16.hip):  y (M, N) = x (M, K) . w (N, K)^T + bias.
  * Replaces nn.Linear under torch.autocast where M is the batch of a decode step: the projections of
  * models/softmax_attention.py:30-44 and :78-81, the two Linear layers of models/transformer.py:22-43 and the logits of

@@ -273,28 +273,32 @@ def ref_swiglu_mixed(ab, cot):
     return {"g": g, "bound_g": bg, "dab": torch.cat([da, db], 1), "bound_dab": torch.cat([bda, bdb], 1)}
 
 
-def tn_tile_k(N, K):
-    """The K width of the weight-gradient tile, as tile_k() in csrc/gemm_bf16.hip picks it (default settings)."""
+def tn_tile_k(N, K, tk=None):
+    """The K width of the weight-gradient tile, as tile_k() in csrc/gemm_bf16.hip picks it (default settings).  tk: the
+    width AMK_TN16_TK forces (128 or 256; anything else is ignored there and here)."""
+    if tk in (128, 256):
+        return tk
     return 256 if K >= 256 and ((N + 127) // 128) * ((K + 255) // 256) >= 12 else 128
 
 
-def tn_chunks(M, N, K, cus=256):
-    """(steps per chunk, chunks) as chunks_for() in csrc/gemm_bf16.hip picks them (default settings)."""
-    TK = tn_tile_k(N, K)
+def tn_chunks(M, N, K, cus=256, tk=None, wgs=1):
+    """(steps per chunk, chunks) as chunks_for() in csrc/gemm_bf16.hip picks them (default settings).  tk, wgs: what
+    AMK_TN16_TK and AMK_TN16_WGS force (workgroups per CU the grid aims at)."""
+    TK = tn_tile_k(N, K, tk)
     tiles = ((N + 127) // 128) * ((K + TK - 1) // TK)
     steps = (M + 63) // 64
-    chunks = max(1, cus // tiles)
+    chunks = max(1, wgs * cus // tiles)
     if chunks > steps // 8:
         chunks = max(1, steps // 8)
     s = (steps + chunks - 1) // chunks
     return s, (steps + s - 1) // s
 
 
-def ref_tn(y, x, cus=256):
+def ref_tn(y, x, cus=256, tk=None, wgs=1):
     """{"dw", "db", "bound_dw", "bound_db"} of amk_gemm_tn_bf16: dW = y^T x, db = column sums of y."""
     Y, X = _d(y), _d(x)
     M, N = Y.shape
-    spc, nch = tn_chunks(M, N, X.shape[1], cus)
+    spc, nch = tn_chunks(M, N, X.shape[1], cus, tk, wgs)
     n = 64 * spc + nch
     return {"dw": Y.t() @ X, "bound_dw": n * U32 * (Y.abs().t() @ X.abs()),
             "db": Y.sum(0), "bound_db": (n + 32) * U32 * Y.abs().sum(0)}

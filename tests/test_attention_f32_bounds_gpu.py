@@ -239,6 +239,46 @@ def test_every_element_within_its_bound(device, monkeypatch, switches, case):
     _bound_case(device, monkeypatch, switches, *case)
 
 
+@pytest.mark.parametrize("D,mask", [(32, "none"), (32, "causal"), (128, "causal")], ids=lambda x: str(x))
+def test_kept_scores_backward_that_ops_never_asks_for(device, switches, D, mask):
+    """The library keeps scores at head dims 32 and 128 where the call has no mask (csrc/attn_fwd.hip:541-544; launch_fwd_gen_dh,
+    csrc/attn_generic.h:852: attn_fwd_gen_plain_kernel<D, true>), and its one-pass backward reads kept scores at those head
+    dims with or without a causal mask (csrc/attn_bwd_fused.hip:497 and :511-512).  amk/ops.py keeps none at head dim 32
+    and none under a mask (`keepable` in ops._attn_forward), so attn_fwd_gen_plain_kernel<32, true> and
+    attn_bwd_fused_kernel<32, 8, 2, true, 0, false / true> and <128, 4, 1, true, 0, true> run through the C ABI only.
+    Kept scores are the raw scores, before any mask, so the scores of the unmasked forward serve the masked problem: o
+    and the row statistics come from amk_attn_fwd under the case's own mask, the backward from amk_attn_bwd_kept on both,
+    and every element is held to the family's bounds (attn_f32_ref, model f32)."""
+    from amk import lib, ops
+
+    switches(_path(D, keep=False))
+    L, nan = lib.load(), float("nan")
+    B, H, I, J = BIG
+    c, R = _reference("diffuse", BIG, mask, D, "f32")
+    bthd = lambda t: t.to(device).permute(0, 2, 1, 3).contiguous().permute(0, 2, 1, 3)   # noqa: E731  (the dense dq layout)
+    q, k, v, d_o = (bthd(t) for t in c["inputs"])
+    cm = ops._mask_u8(None if c["cm"] is None else c["cm"].to(device), (I, J), "causal_mask")
+    assert c["km"] is None and (cm is not None) == (mask == "causal")
+    qv, kv, vv = (ops._as_kernel_view(t) for t in (q, k, v))
+    o0, stats0 = ops._new_bthd(B, H, I, D, qv), torch.full((B, H, I, 2), nan, device=device)
+    scores = torch.full((L.amk_attn_scores_bytes(B, H, I, J) // 4,), nan, device=device)
+    rc = L.amk_attn_fwd_keep(ops._ptr(qv), ops._ptr(kv), ops._ptr(vv), ops._ptr(o0), ops._ptr(stats0), ops._ptr(scores),
+                             ops._NULL, ops._NULL, B, H, I, J, D, *ops._strides4(qv), *ops._strides4(kv), *ops._strides4(vv),
+                             *ops._strides4(o0), float(c["scale"]), ops._stream())
+    lib.check(rc, "amk_attn_fwd_keep")
+    qv, kv, vv, o, stats, kept = ops._attn_forward(q, k, v, None, cm, c["scale"])      # the case's own mask; nothing kept
+    assert kept is None
+    if mask == "none":      # the keeping forward's own o and statistics (it subtracts a running maximum, the plain one a lazy
+        o, stats = o0, stats0      # reference, csrc/attn_fwd.hip:287-296: the two differ in the last bits)
+    dq, dk, dv = (torch.full_like(t, nan) for t in (qv, kv, vv))
+    assert dq.stride() == (I * H * D, D, H * D, 1)
+    ops._attn_backward(qv, kv, vv, o, stats, d_o, dq, dk, dv, None, cm, c["scale"], stages=ops.ATTN_BWD_FAST, scores=scores)
+    torch.cuda.synchronize()
+    got = dict(o=o, lse=ref.lse_of(stats), dq=dq, dk=dk, dv=dv)
+    res = ref.assert_within(got, R, path=f"d{D}-kept-abi", what=f"diffuse/{mask}/{BIG}")
+    print(D, mask, {n: f"{w:.3f}" for n, (_, w) in res.items()})
+
+
 # one attention_fused_kv case per forward flavour: f32 and split-bf16 x masked and plain x kept and not, the generic
 # forward masked and plain, and head dim 128's keeping forward; its backward writes dk and dv into one buffer
 FUSED_KV = [("f32-kept-128", "none"), ("f32-kept-128", "both"), ("f32-recompute-256", "none"), ("f32-recompute-256", "both"),

@@ -12,7 +12,8 @@ import attn_decode_bf16_ref as R16
 pytestmark = pytest.mark.gpu
 
 B, H, CAP = 2, 3, 200
-HEAD_DIMS = [32, 64, 96, 128, 160, 256]
+# every instance of the bf16 chunk kernel (csrc/attn_decode.hip:421-432, launch_chunks_bf16 over D / 32): 1 .. 8
+HEAD_DIMS = [32, 64, 96, 128, 160, 192, 224, 256]
 APPEND_N = [0, 1, 31, 32, 33, 63, 64, 65, 127, 128, 129, 191, 192, 193, 199]
 READ_N = [1, 7, 77, 200]
 BF16 = torch.bfloat16

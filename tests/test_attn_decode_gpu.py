@@ -12,7 +12,8 @@ import attn_decode_ref as R
 pytestmark = pytest.mark.gpu
 
 B, H, CAP = 2, 3, 200
-HEAD_DIMS = [32, 64, 96, 128, 256]
+# every instance of launch_chunks (csrc/attn_decode.hip:218-229, D / 32 float4 per lane): 1 .. 8
+HEAD_DIMS = [32, 64, 96, 128, 160, 192, 224, 256]
 # the ends, the 32-key passes of a workgroup (31 / 32 / 33) and every boundary of the 64-key chunks below the capacity
 # (63 / 64 / 65, 127 / 128 / 129, 191 / 192 / 193): n = 64 c is the first position whose new row opens chunk c
 APPEND_N = [0, 1, 31, 32, 33, 63, 64, 65, 127, 128, 129, 191, 192, 193, 199]

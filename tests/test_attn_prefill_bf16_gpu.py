@@ -13,7 +13,8 @@ import attn_prefill_ref as P
 pytestmark = pytest.mark.gpu
 
 B, H, CAP = 2, 2, 200
-HEAD_DIMS = [32, 64, 96, 128, 256]
+# every instance of the prefill kernel (csrc/attn_prefill.hip:293-305, launch_chunks over D / 32): 1 .. 8
+HEAD_DIMS = [32, 64, 96, 128, 160, 192, 224, 256]
 # the cases of tests/test_attn_prefill_gpu.py (see there for the last two)
 CASES = [(0, 1), (0, 33), (0, 65), (1, 31), (63, 2), (64, 64), (65, 65), (130, 70), (199, 1), (6, 64), (70, 64)]
 BF16 = torch.bfloat16

@@ -14,7 +14,8 @@ import attn_prefill_ref as P
 pytestmark = pytest.mark.gpu
 
 B, H, CAP = 2, 2, 200
-HEAD_DIMS = [32, 64, 96, 128, 256]
+# every instance of the prefill kernel (csrc/attn_prefill.hip:293-305, launch_chunks over D / 32): 1 .. 8
+HEAD_DIMS = [32, 64, 96, 128, 160, 192, 224, 256]
 # (p0, n): one row; one and two passes of 32 keys; rows and positions on either side of the 64-key chunks and the
 # 16-row blocks; a call that ends at the capacity; and two calls, (6, 64) and (70, 64), in which a group of rows that is
 # NOT the last of its 16-row block has rows that stop short of a 64-key chunk beside rows that cross it, so that some

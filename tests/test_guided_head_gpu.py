@@ -2,7 +2,13 @@
 of tests/guided_head_ref.py: the LayerNorm at the NCH switch points of the mixed LayerNorm's dispatch and a row count
 that leaves a partial last workgroup, with f32 rows, bf16 rows and without the second row, at guidance scales 3, 1 and 0;
 the GEMM at the tile and k-step edges of the bf16 GEMM tests, with and without a bias, into a canvas wider than the
-result.  Plus the refusals (nothing written) and ops.guided_logits's launches."""
+result.  Plus the refusals (nothing written) and ops.guided_logits's launches.
+
+The GEMM has two stores, chosen by AMK_GEMM16_F32OUT at every call (csrc/gemm_bf16.hip:574-599): unset, the result goes
+through LDS; "direct", every lane stores 16 bytes straight from its accumulators (gemm_bf16_kernel<false, 4>).  The GEMM
+test and the op test run under both: the tests of the default store keep their names, their twins end in _direct_store.
+Shapes, families, bounds and the canvas check are the same -- with ldc = N + 12 the canvas is where a direct store that
+ran past a row's end would show."""
 import ctypes
 
 import pytest
@@ -12,9 +18,19 @@ import guided_head_ref as ref
 
 pytestmark = pytest.mark.gpu
 
-LN_SHAPES = [(1, 4), (5, 252), (257, 260), (64, 1024), (3, 4096)]
+# (3, 1028): NCH = 8 of AMK_MX_DISPATCH (csrc/mixed_bf16.hip:300-307), which no other width here selects
+LN_SHAPES = [(1, 4), (5, 252), (257, 260), (64, 1024), (3, 4096), (3, 1028)]
 GEMM_SHAPES = [(1, 136, 1368), (127, 8, 24), (128, 1024, 8), (129, 120, 40), (383, 264, 96)]
 EINVAL, EUNSUPPORTED = -1, -2
+STORE_ENV = "AMK_GEMM16_F32OUT"
+
+
+def _set_store(monkeypatch, store):
+    """store None: the variable unset (the default store through LDS); "direct": the direct store."""
+    if store is None:
+        monkeypatch.delenv(STORE_ENV, raising=False)
+    else:
+        monkeypatch.setenv(STORE_ENV, store)
 
 
 def _P(t):
@@ -31,17 +47,18 @@ def _L():
     return lib.load()
 
 
-def _cfg_ln(device, hc, hn, gamma, beta, s, bf16):
-    """The kernel's y (M, D) bf16 through the C ABI, written into a NaN canvas with one more row (which must stay NaN)."""
+def _cfg_ln(device, hc, hn, gamma, beta, s, bf16, n_bf16=None):
+    """The kernel's y (M, D) bf16 through the C ABI, written into a NaN canvas with one more row (which must stay NaN).
+    bf16: the dtype of both rows; n_bf16: that of the second row where it differs."""
     from amk import lib
 
-    dt = torch.bfloat16 if bf16 else torch.float32
+    n_bf16 = bf16 if n_bf16 is None else n_bf16
     M, D = hc.shape
-    c = hc.to(device=device, dtype=dt)
-    n = hn.to(device=device, dtype=dt) if hn is not None else None
+    c = hc.to(device=device, dtype=torch.bfloat16 if bf16 else torch.float32)
+    n = hn.to(device=device, dtype=torch.bfloat16 if n_bf16 else torch.float32) if hn is not None else None
     g, b = gamma.to(device), beta.to(device)
     y = torch.full((M + 1, D), float("nan"), device=device, dtype=torch.bfloat16)
-    rc = _L().amk_cfg_layernorm_bf16(_P(c), int(bf16), _P(n), int(bf16), _P(g), _P(b), s, M, D, ref.LN_EPS, _P(y), _S())
+    rc = _L().amk_cfg_layernorm_bf16(_P(c), int(bf16), _P(n), int(n_bf16), _P(g), _P(b), s, M, D, ref.LN_EPS, _P(y), _S())
     lib.check(rc, "amk_cfg_layernorm_bf16")
     torch.cuda.synchronize()
     assert torch.isnan(y[M].float()).all(), "wrote past its M rows"
@@ -63,6 +80,21 @@ def test_cfg_layernorm_bounds(device, family, M, D, inputs):
         assert ok.all(), f"{family} M{M} D{D} {inputs} s={s}: {int((~ok).sum())} of {ok.numel()} elements outside the interval"
         if s == 1.0 or hn is None:
             assert torch.equal(y, one), f"s={s}: not bitwise the one-input kernel"
+
+
+@pytest.mark.parametrize("M,D", LN_SHAPES, ids=lambda v: str(v))
+@pytest.mark.parametrize("c_bf16", [True, False], ids=["bf16_f32", "f32_bf16"])
+def test_cfg_layernorm_bounds_rows_of_two_dtypes(device, M, D, c_bf16):
+    """The two rows in different dtypes -- cfg_ln_bf16_kernel<NCH, true, false, true> and <NCH, false, true, true>, the
+    `cb` / `nb` branches of csrc/mixed_bf16.hip:349-350, which rows of one dtype never take -- at every NCH, held to the
+    same intervals: both rows hold bf16 values, so the reference is that of the bf16 case."""
+    for family in ref.LN_FAMILIES[:2]:
+        hc, hn, gamma, beta = ref.make_cfg_ln(family, M, D, 100 + D, bf16=True)
+        for s in (3.0, 0.0):
+            y = _cfg_ln(device, hc, hn, gamma, beta, s, c_bf16, n_bf16=not c_bf16)
+            ok = ref.inside(y, ref.ref_cfg_ln(hc, hn, gamma, beta, s))
+            assert ok.all(), f"{family} M{M} D{D} s={s}: {int((~ok).sum())} of {ok.numel()} elements outside the interval"
+            assert torch.equal(y, _cfg_ln(device, hc, hn, gamma, beta, s, True)), "not bitwise the kernel on two bf16 rows"
 
 
 @pytest.mark.parametrize("bf16", [False, True], ids=["f32", "bf16"])
@@ -88,18 +120,34 @@ def _gemm(device, a, w, bias, pad=0, poison=float("nan")):
     return c
 
 
-@pytest.mark.parametrize("M,N,K", GEMM_SHAPES, ids=lambda v: str(v))
-@pytest.mark.parametrize("family", ref.GEMM_FAMILIES)
-@pytest.mark.parametrize("with_bias", [False, True], ids=["nobias", "bias"])
-def test_gemm_f32out_bounds(device, family, M, N, K, with_bias):
+def _gemm_cases(fn):
+    for mark in (pytest.mark.parametrize("with_bias", [False, True], ids=["nobias", "bias"]),
+                 pytest.mark.parametrize("family", ref.GEMM_FAMILIES),
+                 pytest.mark.parametrize("M,N,K", GEMM_SHAPES, ids=lambda v: str(v))):
+        fn = mark(fn)
+    return fn
+
+
+@_gemm_cases
+def test_gemm_f32out_bounds(device, monkeypatch, family, M, N, K, with_bias):
+    _gemm_f32out_bounds(device, monkeypatch, None, family, M, N, K, with_bias)
+
+
+@_gemm_cases
+def test_gemm_f32out_bounds_direct_store(device, monkeypatch, family, M, N, K, with_bias):
+    _gemm_f32out_bounds(device, monkeypatch, "direct", family, M, N, K, with_bias)
+
+
+def _gemm_f32out_bounds(device, monkeypatch, store, family, M, N, K, with_bias):
+    _set_store(monkeypatch, store)
     a, w, b = ref.make_gemm(family, M, N, K, 300 + K)
     bias = b if with_bias else None
     c = _gemm(device, a, w, bias, pad=12)
     rest = torch.ones_like(c, dtype=torch.bool)
     rest[:M, :N] = False
-    assert torch.isnan(c[rest]).all(), "wrote outside its result region (ldc > N)"
+    assert torch.isnan(c[rest]).all(), f"store {store}: wrote outside its result region (ldc > N)"
     bad = ref.outside_gemm(c[:M, :N], ref.ref_gemm_f32(a, w, bias))
-    assert bad == 0, f"{family} {M}x{N}x{K}: {bad} elements outside n u32 S"
+    assert bad == 0, f"{family} {M}x{N}x{K} store {store}: {bad} elements outside n u32 S"
 
 
 def test_refusals_write_nothing(device):
@@ -126,10 +174,20 @@ def test_refusals_write_nothing(device):
     assert torch.isnan(y.float()).all() and torch.isnan(c).all(), "a refused call wrote"
 
 
-def test_guided_logits_op(device):
+def test_guided_logits_op(device, monkeypatch):
+    _guided_logits_op(device, monkeypatch, None)
+
+
+def test_guided_logits_op_direct_store(device, monkeypatch):
+    _guided_logits_op(device, monkeypatch, "direct")
+
+
+def _guided_logits_op(device, monkeypatch, store):
     """Under autocast: exactly the two kernels, the result bitwise the two C calls' and within the bounds; outside autocast
     the gate is False."""
     from amk import ops
+
+    _set_store(monkeypatch, store)
 
     M, D, V = 150, 64, 256
     hc, hn, gamma, beta = ref.make_cfg_ln("unit", M, D, 60)

@@ -360,6 +360,10 @@ def _tie_logits(name, g):
         return q(257, 33), 2
     if name == "ties_E64_k8":
         return q(129, 64), 8
+    if name == "ties_E40_k6":                                                      # route_topk_kernel<6>, <7>: launch_topk's
+        return q(129, 40), 6                                                       # switch over k, csrc/moe.hip:1369-1378
+    if name == "ties_E33_k7":
+        return q(131, 33), 7
     if name == "boundary_31_32":
         lg = q(130, 96)
         lg[:, 31] = lg[:, 32] = lg[:, 63] = lg[:, 64] = 9.0                        # ties across the staging chunks
@@ -390,7 +394,7 @@ def _tie_logits(name, g):
 
 
 @pytest.mark.parametrize("name", ["ties_E33_k2", "ties_E64_k8", "boundary_31_32", "kth_tie", "all_equal", "neg_inf", "k_eq_E",
-                                  "E1", "E1024_k8"])
+                                  "E1", "E1024_k8", "ties_E40_k6", "ties_E33_k7"])
 def test_topk_and_route(device, name):
     """ids against a stable descending sort (lowest index first on ties), the gate under its bound, offsets and perm
     exact; every output and workspace between guards."""

@@ -1,6 +1,9 @@
 """No kernel writes or reads outside the buffers amk allocates: every case of tests/test_stale_memory_gpu.py -- every
-autograd entry point of amk.ops and the plain entry points next to them, on every forced path -- run under the red-zone
-allocator of tests/redzone.py, once per fill, under the case's own switches.  Every torch.empty / empty_like /
+autograd entry point of amk.ops and the plain entry points next to them (the prefill attention on both cache types and the
+guided logits head under both stores of its GEMM among them), on every forced path -- run under the red-zone allocator of
+tests/redzone.py, once per fill, under the case's own switches and environment.  CASES is imported, so a family added to
+the stale-memory sweep -- its guard, test_every_launcher_is_swept there, asks for one per new launcher -- runs here too.  Every torch.empty / empty_like /
+
 empty_strided / new_empty of amk, and every input the case moves to the device, lies between two canary margins that begin
 at the buffer's first and last byte.  For every case
 
@@ -22,7 +25,7 @@ import torch
 
 from poison import assert_fill_independent
 from redzone import redzoned_empty, run_both
-from test_stale_memory_gpu import _PAIR_BOUND, _switches, ATOMIC, CASES      # the names only: no test function is imported
+from test_stale_memory_gpu import _PAIR_BOUND, _env, _switches, ATOMIC, CASES      # the names only: no test function is imported
 
 pytestmark = pytest.mark.gpu
 
@@ -34,7 +37,7 @@ def test_no_access_outside_the_buffers(device, case):
     with pytest.MonkeyPatch.context() as mp:
         mp.setattr(torch.backends.cudnn, "benchmark", False)
         mp.setattr(ops, "_SAMPLE_CALLS", ops._SAMPLE_CALLS)      # (the seeded sampling cases set it: put back afterwards)
-        with _switches(**case.switches):
+        with _switches(**case.switches), _env(case.env):
             nan_run, big_run = run_both(lambda: case.fn(device))      # check() inside, under each fill
             row = ATOMIC[case.atomic] if case.atomic else None
             assert_fill_independent(nan_run, big_run, case.id, tolerant=row["tensors"] if row else (),
